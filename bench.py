@@ -1,8 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the node2vec hot path on MI355X: 2nd-order walk + SGNS (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline does not need:
+the side measurements at N = 1 (negatives shared per centre word, reference-exact and on-the-fly walks), the
+stand-alone all-reduce behind `overlap_fraction` at N > 1 and the CPU baselines.  `--dump-outputs DIR` writes what the
+timed steps compute reproducibly as DIR/<name>.npy (at most 64 MB in all): the last step's walks (a fixed, seeded
+sample of rows) and the training pass's own counts (SGNS pairs; BiNE rows), all bit-identical from run to run.  The
+trained tables are not written, since the passes let wavefronts race on shared rows and two runs with
+the same inputs end with different tables; the run fails instead if a sample of them is not finite or is all zero.
 
 One "step" = one pass of the hot path over one batch: `rounds` walks of length 80 from every
 start vertex of this rank's shard (walk kernel), then one SGNS pass over those walks (SGNS
@@ -40,8 +48,38 @@ CONFIGS = {
 }
 
 
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this many bytes in all
+
+
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def row_sample(n, k, seed=0):
+    """A fixed, seeded, sorted choice of min(n, k) of n row indices: the same rows in every run with the same arguments."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs`: writes each of `arrays` (name -> tensor or array) as out_dir/<name>.npy in float64, which holds
+    the int32 vertex ids and lengths exactly."""
+    host = {name: np.asarray(a.cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("[bench] wrote %s (%.1f MB): %s" % (out_dir, total / 1e6, ", ".join(sorted(host))))
+
+
+def check_trained(name, rows):
+    """`--dump-outputs`: a racing pass leaves no reproducible table to write, so a sample of its rows is checked instead:
+    finite, and not all zero (an untrained SGNS syn1neg is all zero)."""
+    if not bool(torch.isfinite(rows).all()) or not bool((rows != 0).any()):
+        raise SystemExit("--dump-outputs: %s after the timed steps is not finite or is all zero" % name)
 
 
 def cpu_baselines(cg, p, q, walks_sample, lens_sample, counts, dim, budget_s=12.0):
@@ -164,6 +202,12 @@ def bench_bine(args):
     pa.iters, pa.warmup_iters, pa.backend = args.steps, max(1, args.warmup), args.backend
     out = bine_probe.run(pa, ctx=ctx, emit=False)
     e, tr = out.pop("engine"), out["train"]
+    if ctx.rank == 0 and args.dump_outputs:
+        rows = torch.from_numpy(row_sample(e.g.n, 65536)).to(e.emb.device)
+        check_trained("the embedding table", e.emb[rows, : e.dim])
+        check_trained("the context table", e.ctx[rows, : e.dim])
+        # rows the passes read + wrote and rows the reference's access pattern would move: integer sums
+        dump_outputs(args.dump_outputs, {"train_rows": e.state[4:6]})
     if ctx.rank != 0:
         ctx.close()
         return
@@ -196,7 +240,7 @@ def bench_bine(args):
                                    "own access pattern (every skip_gram call re-reads and re-writes all its rows) "
                                    "would move %.3g B per launch" % (tr["reference_pattern_rows_per_iteration"] * e.dim * 8)},
     }
-    if not args.no_cpu_baseline and ctx.world == 1:
+    if args.full and not args.no_cpu_baseline and ctx.world == 1:
         result["cpu_baseline"] = bine_cpu_baseline(e)
     print(json.dumps(result), flush=True)
     ctx.close()
@@ -254,10 +298,16 @@ def main():
     ap.add_argument("--merge-timers", action="store_true",
                     help="N > 1, --merge tsum: time the merges with events (runs the eager Python loop instead of replaying "
                          "the captured HIP graph of a base interval: slower, but merge_seconds is measured)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: side measurements, stand-alone all-reduce, "
+                         "CPU baselines (the --no-* options below drop parts of it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-shared-negatives", action="store_true", help="skip the extra opt-in SGNS variant pass")
     ap.add_argument("--no-reference-exact", action="store_true", help="skip the extra reference-exact walk pass")
     ap.add_argument("--backend", default="auto", choices=["auto", "nccl", "gloo"])
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's walks (seeded row sample) and the pass's pair / row counts as "
+                         "DIR/<name>.npy (<= 64 MB); the racing tables are checked, not written")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -288,7 +338,8 @@ def main():
     t_pre = time.perf_counter() - t0
     eng = g._engine
     t_pre_alloc = float(getattr(eng, "alloc_seconds", 0.0))    # host time of the table allocation (driver-side; see engine.py)
-    # a second call: the tables come back from the allocator's cache, what remains is index plumbing + the kernels
+    # a second call: the tables come back from the allocator's cache, what remains is index plumbing + the kernels (kept in
+    # a plain run: the timed walks read the tables this call leaves, as they always have)
     t0 = time.perf_counter()
     g.preprocess_transition_probs()
     torch.cuda.synchronize()
@@ -380,7 +431,7 @@ def main():
         merge_secs["wait"] += sec["wait"]
         merge_secs["n"] += mg.n_merges if isinstance(mg.n_merges, int) else sum(mg.n_merges)   # tsum: all tiers' merges
     comm_probe = None
-    if world > 1 and mergers:
+    if args.full and world > 1 and mergers:
         # what one merge's all-reduce costs when nothing runs beside it (for overlap_fraction): the wire buffer that
         # carries the bulk of the rows — the synchronous tier's unless most rows are in the delayed tier
         buf = mergers[-1].probe_buffer()
@@ -401,10 +452,20 @@ def main():
         comm.all_reduce_sum(sums)
     t_total, t_walk, t_sgns = [float(x) for x in stats.tolist()]
     steps_all, pairs_all = [float(x) for x in sums.tolist()]
+    if rank == 0 and args.dump_outputs:
+        # the last timed step's walks of this rank (a sample of rows, with their lengths) and the pairs the timed SGNS
+        # passes trained (an integer sum): bit-identical from run to run.  Not the SGNS tables: racing rows make them
+        # differ between two runs with the same inputs, so a sample of them is checked instead.
+        log("[bench] dumping the walks of seed %d (step %d)" % (1000 + args.warmup + args.steps - 1, args.warmup + args.steps - 1))
+        vrows = torch.from_numpy(row_sample(N, 65536)).to(dev)
+        check_trained("SGNS syn0", model.vectors()[vrows])
+        check_trained("SGNS syn1neg", model.syn1neg[vrows, : args.dim])
+        wrows = torch.from_numpy(row_sample(n_local, 65536)).to(dev)
+        dump_outputs(args.dump_outputs, {"walks": walks[wrows], "walk_lens": lens[wrows], "sgns_pairs": model.pair_count})
 
     # opt-in variant, reported separately: negatives shared per centre word (one pass, N=1 only)
     shared = None
-    if world == 1 and not args.no_shared_negatives:
+    if args.full and world == 1 and not args.no_shared_negatives:
         ms = sgns.SgnsModel(N, dim=args.dim, window=window, negative=negative, seed=1, device=dev, share_negatives=True,
                             allow_out_of_band=True)     # reported separately and labelled as not gensim's sampling
         ms.build_vocab(counts=counts)
@@ -422,7 +483,7 @@ def main():
     # the reference-exact mode, reported separately (N=1): numpy's global MT19937 stream regenerated
     # on the device, end to end (uniform generation + walk), same walks as the reference for this seed
     exact = None
-    if world == 1 and not args.no_reference_exact:
+    if args.full and world == 1 and not args.no_reference_exact:
         g.rng = "numpy"
         np.random.seed(123)
         g.simulate_walks(args.rounds, L)             # warm-up at full size (jump polynomials, the allocator's 12.6 GB buffer)
@@ -444,7 +505,7 @@ def main():
     # the reference's memory-saving mode (ON_THE_FLY = True, src/settings.py:18, is main_link's default): no stored edge
     # tables, every step rebuilds — or proves it does not need — its alias table (one round of the same walks, N=1)
     otf = None
-    if world == 1 and not args.no_reference_exact:
+    if args.full and world == 1 and not args.no_reference_exact:
         eng.walk_on_the_fly(eng.start_order, 1, L, rng="philox", seed=3)      # warm-up (scratch rows)
         o0, o1 = ev(), ev()
         o0.record()
@@ -547,7 +608,7 @@ def main():
                           "request_ceiling_steps_per_s": 5.05e10,
                           "frac_of_request_ceiling": float(steps_done.item()) / K / walk_launch_s / 5.05e10},
     }
-    if not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:      # the CPU baseline is timed at N = 1 only
         t0 = time.perf_counter()
         ns = min(32000, n_local)
         result.update(cpu_baselines(cg, p, q, walks[:ns].cpu().numpy(), lens[:ns].cpu().numpy(),

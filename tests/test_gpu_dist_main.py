@@ -97,7 +97,7 @@ def test_two_rank_merges_identical_with_and_without_overlap(tmp_path):
 
 def test_bench_two_ranks_strong_scaling_reports_merge_timers(tmp_path):
     """bench.py --gpus 2 (strong scaling = BASELINE config C4's split) rehearsed on the one GPU over gloo: the JSON
-    line carries merge_seconds and overlap_fraction."""
+    line carries merge_seconds and (--full: the stand-alone all-reduce) overlap_fraction."""
     import json
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -106,7 +106,7 @@ def test_bench_two_ranks_strong_scaling_reports_merge_timers(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C2",
            "--rounds", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--backend", "gloo", "--merge", "hot",
-           "--allow-out-of-band"]          # 100 000 rows: merge=hot is fenced above 32 768 (n2v_hip/sgns.py)
+           "--allow-out-of-band", "--full"]          # 100 000 rows: merge=hot is fenced above 32 768 (n2v_hip/sgns.py)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
