@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define N2V_ABI_VERSION 2
+#define N2V_ABI_VERSION 3
 
 #define N2V_OK 0
 #define N2V_ERR_INVALID (-1)   /* bad argument (null pointer, negative size, limit exceeded) */
@@ -75,27 +75,22 @@ int n2v_alias_setup_tables(int64_t n_tables, const int64_t* tab_off, n2v_alias_s
 int n2v_build_node_tables(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col,
                           const double* w, n2v_alias_slot* slots, int32_t* status, void* stream);
 
-/* Edge tables (src/node2vec.py:133-152,193-199): for CSR entries e in
- * [e_begin, e_end) — or, if `order` != NULL, for order[i], i in [e_begin, e_end) — the
- * table of (src -> dst=col[e]) is written to slots[edge_off[e] ...], deg(dst) slots.
- * edge_off: int64[nnz+1], exclusive prefix sum of deg(col[e]).  `src_of`: int32[nnz], the
- * row of each CSR entry.  `order` lets the caller bin tables by size (one lane builds one
- * table, so lanes of a wave should get similar sizes).  symmetric != 0 declares the CSR
- * symmetric (undirected graph): G.has_edge(nbr, src) is then looked up in src's own row.   */
-int n2v_build_edge_tables(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col,
-                          const double* w, const int32_t* src_of, double p, double q,
-                          int32_t symmetric, const int64_t* edge_off, const int32_t* order, int64_t e_begin,
-                          int64_t e_end, n2v_alias_slot* slots, int32_t* status, void* stream);
-
-/* The same tables (same bits) built by ONE WAVEFRONT per table, with coalesced row reads; tables of up to 512 slots
- * are staged in LDS, of larger ones only the two Vose stacks are kept (in `scratch`) and finished slots go straight to the
- * output; every output slot is written once, in the layout the walk reads: exactly one of `thin` (16-B slots at
- * thin[edge_off[e] ...]) and `fat` (32-B n2v_fat_slot at fat[edge_off[e] ...], needs the walk records `recs` of
- * n2v_build_edge_recs, whose table indices address `fat`) is non-NULL.  With `fat` no thin copy of the edge tables has
- * to exist.  work_counter: uint64[1] set to 0 by the caller — tables are then handed to the wavefronts dynamically
- * (sizes differ by three orders of magnitude on a power-law graph), and `order` is not needed; NULL: static assignment.
- * max_degree: largest out-degree of the graph; scratch: n2v_edge_tables_wave_scratch_bytes(max_degree) bytes, 64-B
- * aligned (0 bytes / NULL when max_degree <= 512).  src/node2vec.py:133-152,240-269.                              */
+/* Edge tables (src/node2vec.py:133-152,193-199): for CSR entries e in [e_begin, e_end) — or, if `order` != NULL,
+ * for order[i], i in [e_begin, e_end) — the table of (src -> dst=col[e]) is built, deg(dst) slots, by ONE WAVEFRONT
+ * per table with coalesced row reads.  edge_off: int64[nnz+1], exclusive prefix sum of deg(col[e]).  `src_of`:
+ * int32[nnz], the row of each CSR entry.  symmetric != 0 declares the CSR symmetric (undirected graph):
+ * G.has_edge(nbr, src) is then looked up in src's own row.  Tables of up to 512 slots are staged in LDS, of larger
+ * ones only the two Vose stacks are kept (in `scratch`) and finished slots go straight to the output; every output slot
+ * is written once, in the layout the walk reads: exactly one of `thin` (16-B slots at thin[edge_off[e] ...]) and `fat`
+ * (32-B n2v_fat_slot at fat[edge_off[e] ...], needs the walk records `recs` of n2v_build_edge_recs, whose table indices
+ * address `fat`) is non-NULL.  With `fat` no thin copy of the edge tables has to exist.  work_counter: uint64[1] set
+ * to 0 by the caller — tables are then handed to the wavefronts dynamically (sizes differ by three orders of magnitude
+ * on a power-law graph), and `order` is not needed; NULL: static assignment.
+ * max_degree: an upper bound of deg(dst) over the tables built.  scratch: 64-B aligned, 48 * R bytes per workgroup
+ * launched (4 wavefronts x R x 12 B), R = max_degree rounded up to a multiple of 16; the launch has
+ * min(ceil((e_end - e_begin) / 64), every resident workgroup of the chip) workgroups, so a one-table launch needs
+ * 48 * R bytes and n2v_edge_tables_wave_scratch_bytes(max_degree) is the bound for any range.  No scratch (NULL,
+ * 0 bytes) when max_degree <= 512.  src/node2vec.py:133-152,240-269.                                                 */
 struct n2v_fat_slot;
 int64_t n2v_edge_tables_wave_scratch_bytes(int64_t max_degree);
 int n2v_build_edge_tables_wave(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col, const double* w,

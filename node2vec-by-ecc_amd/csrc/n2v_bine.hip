@@ -29,21 +29,10 @@ constexpr double kLn10 = 2.302585092994046;  // math.log(10, math.e), src/bine_t
 constexpr int kMaxTrials = 1 << 16;          // proposal cap of a walk step (exit condition)
 constexpr int kPoolTrials = 16;
 
-__device__ __forceinline__ void philox4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                        uint32_t (&out)[4]) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
-}
+using n2v::philox4x32_10;
+using n2v::u53;
+using n2v::uni;
+using n2v::uni64;
 
 // xor-butterfly exchange of a double with lane ^ M: DPP quad permutes for M = 1, 2, ds_swizzle for 4, 8, 16
 // (no address register, unlike ds_bpermute), a full shuffle for 32.
@@ -87,16 +76,6 @@ __device__ __forceinline__ double wave_sum_d(double x) {
     double v[1] = {x};
     wave_sum_n<1>(v);
     return v[0];
-}
-
-// Values that are equal in all 64 lanes but reach us through vector registers (shuffles, vector loads):
-// v_readfirstlane makes them scalar, so addresses derived from them live in SGPRs and loads from them
-// become scalar loads — the training kernel's row data then has the VGPRs to itself.
-__device__ __forceinline__ int32_t uni(int32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t uni64(int64_t v) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)v);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 
 // ------------------------------------------------------------------------------------ HITS
@@ -184,7 +163,7 @@ __global__ void __launch_bounds__(256) walk_len_kernel(const int64_t* __restrict
     if (paths - (re - rb) > 0) {  // some two-hop path leaves the vertex (each middle vertex offers one path back)
         for (uint32_t t = 0; len < max_len; ++t) {
             uint32_t r[4];
-            philox4(seed, (uint32_t)gw, (uint32_t)(gw >> 32), t, 0u, r);
+            philox4x32_10(seed, (uint32_t)gw, (uint32_t)(gw >> 32), t, 0u, r);
             if (u53(r[0], r[1]) > percentage) ++len;  // `while ... random.random() > percentage`
             else break;
         }
@@ -241,7 +220,7 @@ __global__ void __launch_bounds__(256) bine_walk_kernel(const int64_t* __restric
             int32_t next = cur;
             for (int trial = 0; trial < kMaxTrials; ++trial) {
                 uint32_t r[4];
-                philox4(seed, (uint32_t)gw, (uint32_t)(gw >> 32), (uint32_t)t, 1u + (uint32_t)trial, r);
+                philox4x32_10(seed, (uint32_t)gw, (uint32_t)(gw >> 32), (uint32_t)t, 1u + (uint32_t)trial, r);
                 int64_t pick = (int64_t)floor(u53(r[0], r[1]) * (double)paths);
                 if (pick >= paths) pick = paths - 1;
                 int64_t lo = rb, hi = re - 1;  // the CSR entry whose path range holds `pick`
@@ -306,7 +285,7 @@ __global__ void __launch_bounds__(256) neg_pool_kernel(const int64_t* __restrict
         int64_t c = v;
         for (int trial = 0; trial <= kPoolTrials; ++trial) {
             uint32_t r[4];
-            philox4(seed, (uint32_t)v, (uint32_t)s, (uint32_t)trial, 0u, r);
+            philox4x32_10(seed, (uint32_t)v, (uint32_t)s, (uint32_t)trial, 0u, r);
             int64_t k = (int64_t)floor(u53(r[0], r[1]) * side_n);
             if (k >= side_hi - side_lo) k = side_hi - side_lo - 1;
             c = side_lo + k;
@@ -336,7 +315,7 @@ __global__ void __launch_bounds__(256) bine_init_kernel(double* __restrict__ emb
         double x = 0.0;
         if (c < dim) {
             uint32_t r[4];
-            philox4(seed, (uint32_t)row, (uint32_t)((uint64_t)row >> 32), (uint32_t)(c >> 1), table, r);
+            philox4x32_10(seed, (uint32_t)row, (uint32_t)((uint64_t)row >> 32), (uint32_t)(c >> 1), table, r);
             x = (c & 1) ? u53(r[2], r[3]) : u53(r[0], r[1]);
         }
         out[c] = x;
@@ -434,9 +413,9 @@ __device__ __forceinline__ void node_block(const TrainArgs& a, int32_t c, double
     const uint32_t n_occ = (uint32_t)uni((int32_t)(a.occ_ptr[c + 1] - ob));
     const uint32_t m = n_occ < 10u ? n_occ : 10u;
     uint32_t ra[4], rb4[4], rc[4];
-    philox4(a.seed_occ, (uint32_t)c, (uint32_t)a.iteration, 0u, 0u, ra);
-    philox4(a.seed_occ, (uint32_t)c, (uint32_t)a.iteration, 1u, 0u, rb4);
-    philox4(a.seed_occ, (uint32_t)c, (uint32_t)a.iteration, 2u, 0u, rc);
+    philox4x32_10(a.seed_occ, (uint32_t)c, (uint32_t)a.iteration, 0u, 0u, ra);
+    philox4x32_10(a.seed_occ, (uint32_t)c, (uint32_t)a.iteration, 1u, 0u, rb4);
+    philox4x32_10(a.seed_occ, (uint32_t)c, (uint32_t)a.iteration, 2u, 0u, rc);
     const uint32_t my_occ = floyd_sample(n_occ, m, lane, [&](uint32_t k) {
         uint32_t w0 = ra[0], w1 = rb4[0], w2 = rc[0];
 #pragma unroll
@@ -460,8 +439,8 @@ __device__ __forceinline__ void node_block(const TrainArgs& a, int32_t c, double
         const int32_t mytok = lane < nwin ? a.tokens[s + lane] : -1;
         // negatives: distinct pool slots; dropped when in the window or already taken
         uint32_t rn0[4], rn1[4];
-        philox4(a.seed_neg, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), 0u, 0u, rn0);
-        philox4(a.seed_neg, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), 1u, 0u, rn1);
+        philox4x32_10(a.seed_neg, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), 0u, 0u, rn0);
+        philox4x32_10(a.seed_neg, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), 1u, 0u, rn1);
         const uint32_t m2 = (uint32_t)a.ns < (uint32_t)a.pool_size ? (uint32_t)a.ns : (uint32_t)a.pool_size;
         const uint32_t my_slot = floyd_sample((uint32_t)a.pool_size, m2, lane, [&](uint32_t q) {
             uint32_t w0 = rn0[0], w1 = rn1[0];

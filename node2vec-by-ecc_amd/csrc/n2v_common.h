@@ -32,12 +32,10 @@ inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 
 
 // ---- device helpers shared by the walk and table kernels -----------------------------------------
 
-// Philox4x32-10 (Salmon et al., SC'11), key = seed, counter = (walk lo, walk hi, step, 0): the two uniforms of
-// step `step` of the walk with GLOBAL index `walk` in throughput mode.  53-bit doubles built exactly like
-// MT19937's genrand_res53 (numpy random_sample), so they play the role of the two np.random.rand() calls of
-// alias_draw (src/node2vec.py:277-278).
-__device__ __forceinline__ void philox_uniforms(uint64_t seed, uint64_t walk, uint32_t step, double& u1, double& u2) {
-    uint32_t c0 = (uint32_t)walk, c1 = (uint32_t)(walk >> 32), c2 = step, c3 = 0u;
+// Philox4x32-10 (Salmon et al., SC'11): key = seed, counter = (c0, c1, c2, c3).  The one copy behind every stream
+// of the library (walk steps, BiNE, LSH, SGNS init); each stream keeps its own counter layout.
+__device__ __forceinline__ void philox4x32_10(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                              uint32_t (&out)[4]) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
@@ -46,8 +44,43 @@ __device__ __forceinline__ void philox_uniforms(uint64_t seed, uint64_t walk, ui
         c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
     }
-    u1 = ((double)(c0 >> 5) * 67108864.0 + (double)(c1 >> 6)) / 9007199254740992.0;
-    u2 = ((double)(c2 >> 5) * 67108864.0 + (double)(c3 >> 6)) / 9007199254740992.0;
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// 53-bit double in [0, 1) from two words, built exactly like MT19937's genrand_res53 (numpy random_sample)
+__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
+    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
+}
+
+// The two uniforms of step `step` of the walk with GLOBAL index `walk` in throughput mode: counter =
+// (walk lo, walk hi, step, 0).  They play the role of the two np.random.rand() calls of alias_draw
+// (src/node2vec.py:277-278).
+__device__ __forceinline__ void philox_uniforms(uint64_t seed, uint64_t walk, uint32_t step, double& u1, double& u2) {
+    uint32_t r[4];
+    philox4x32_10(seed, (uint32_t)walk, (uint32_t)(walk >> 32), step, 0u, r);
+    u1 = u53(r[0], r[1]);
+    u2 = u53(r[2], r[3]);
+}
+
+// wave-uniform values that arrive through vector registers: make them scalar for the compiler, so loops branch on SCC,
+// keep their counters in SGPRs and loads from addresses derived from them become scalar loads
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ int64_t uni64(int64_t v) {
+    return ((int64_t)uni((int)(v >> 32)) << 32) | (uint32_t)uni((int)v);
+}
+
+// Fat slot {q, rec_k, rec_J} (include/n2v_hip.h, n2v_fat_slot): q[k] and the walk records of both outcomes of the draw,
+// neighbour k and neighbour J[k].  rec = {slot_lo, base, dst, deg_hi}; the row base is not needed any more.
+__device__ __forceinline__ void write_fat_slot(n2v_fat_slot* out, double q, const n2v_edge_rec* rec_k,
+                                               const n2v_edge_rec* rec_J) {
+    const uint4 ra = *reinterpret_cast<const uint4*>(rec_k);
+    const uint4 rb = *reinterpret_cast<const uint4*>(rec_J);
+    uint4 lo, hi;
+    lo.x = (uint32_t)__double2loint(q); lo.y = (uint32_t)__double2hiint(q);
+    lo.z = ra.x; lo.w = ra.w;
+    hi.x = ra.z; hi.y = rb.x; hi.z = rb.w; hi.w = rb.z;
+    uint4* o = reinterpret_cast<uint4*>(out);
+    o[0] = lo;
+    o[1] = hi;
 }
 
 // G.has_edge(u, v) on the sorted CSR (src/node2vec.py:145): binary search of v in row u.

@@ -30,23 +30,9 @@ constexpr int kTrees = N2V_LSH_TREES;     // 8
 constexpr int kDepth = kPerm / kTrees;    // 16
 constexpr int kSetSlots = 512;            // LDS hash per wavefront; k <= 256
 
-__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
-__device__ __forceinline__ void philox4(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                        uint32_t (&out)[4]) {
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ double u53(uint32_t a, uint32_t b) {
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6)) / 9007199254740992.0;
-}
+using n2v::philox4x32_10;
+using n2v::u53;
+using n2v::uni;
 
 // ------------------------------------------------------------------------------------ SHA-1 (FIPS 180-4)
 __device__ __forceinline__ uint32_t rotl(uint32_t x, int s) { return (x << s) | (x >> (32 - s)); }
@@ -287,7 +273,7 @@ __global__ void __launch_bounds__(64) lsh_pool_kernel(const int32_t* __restrict_
         } else {
             for (uint32_t rnd = 0; cnt < pool_size; ++rnd) {
                 uint32_t r[4];
-                philox4(seed, (uint32_t)l, rnd, (uint32_t)lane, 0u, r);
+                philox4x32_10(seed, (uint32_t)l, rnd, (uint32_t)lane, 0u, r);
                 int32_t c = (int32_t)floor(u53(r[0], r[1]) * (double)n_side);
                 c = c < n_side ? c : n_side - 1;
                 bool ok = !bit_test(bm, c);

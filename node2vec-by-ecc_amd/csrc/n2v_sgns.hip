@@ -486,10 +486,6 @@ __global__ void __launch_bounds__(256) sgns_kernel(SgnsArgs a_in) {
                 }
                 if constexpr (MODE == kAtomic) {
                     add_row<VPL>(a.syn0, xj, a.row_stride, lane, work);
-#ifdef N2V_SGNS_LAB_CONTEXT_ADD
-                } else if constexpr (MODE == kAgent) {
-                    add_row_packed<VPL>(a.syn0, xj, a.row_stride, lane, work);
-#endif
                 } else {
 #pragma unroll
                     for (int v = 0; v < VPL; ++v) h.v[v] += work.v[v];
@@ -623,10 +619,6 @@ __global__ void __launch_bounds__(256) sgns_shared_kernel(SgnsArgs a_in) {
                 }
                 if constexpr (MODE == kAtomic) {
                     add_row<VPL>(a.syn0, xj, a.row_stride, lane, work);
-#ifdef N2V_SGNS_LAB_CONTEXT_ADD
-                } else if constexpr (MODE == kAgent) {
-                    add_row_packed<VPL>(a.syn0, xj, a.row_stride, lane, work);
-#endif
                 } else {
 #pragma unroll
                     for (int v = 0; v < VPL; ++v) h.v[v] += work.v[v];
@@ -655,16 +647,8 @@ sgns_init_kernel(float* syn0, float* syn1neg, int64_t n_words, int32_t dim, int3
     const int64_t row = idx / blocks_per_row;
     const int cb = (int)(idx - row * blocks_per_row);
     if (row >= n_words) return;
-    uint32_t c0 = (uint32_t)row, c1 = (uint32_t)(row >> 32), c2 = (uint32_t)cb, c3 = 0x5EEDu;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const uint32_t rr[4] = {c0, c1, c2, c3};
+    uint32_t rr[4];
+    n2v::philox4x32_10(seed, (uint32_t)row, (uint32_t)(row >> 32), (uint32_t)cb, 0x5EEDu, rr);
     float4 o, z = make_float4(0.f, 0.f, 0.f, 0.f);
     float* po = &o.x;
 #pragma unroll

@@ -163,17 +163,7 @@ fat_expand_kernel(int64_t n_tables, const int64_t* __restrict__ tab_off, const i
     const int K = (int)(row_ptr[node + 1] - base);
     for (int k = lane; k < K; k += 64) {
         const n2v_alias_slot s = thin[t0 + k];
-        const uint4 ra = *reinterpret_cast<const uint4*>(recs + base + k);
-        const uint4 rb = *reinterpret_cast<const uint4*>(recs + base + s.J);
-        uint4 lo, hi;  // rec = {slot_lo, base, dst, deg_hi}; the row base is not needed any more
-        lo.x = (uint32_t)__double2loint(s.q);
-        lo.y = (uint32_t)__double2hiint(s.q);
-        lo.z = ra.x; lo.w = ra.w;
-        hi.x = ra.z;
-        hi.y = rb.x; hi.z = rb.w; hi.w = rb.z;
-        uint4* o = reinterpret_cast<uint4*>(fat + t0 + k);
-        o[0] = lo;
-        o[1] = hi;
+        n2v::write_fat_slot(fat + t0 + k, s.q, recs + base + k, recs + base + s.J);
     }
 }
 

@@ -21,10 +21,9 @@
 
 namespace {
 
-#ifndef N2V_OTF_LDS_SLOTS
-#define N2V_OTF_LDS_SLOTS 256   /* 6 KiB per wave -> 6 workgroups per CU: C3 2.1 -> 2.6e8 steps/s vs 512 slots / 4 workgroups; 128: 2.5e8 */
-#endif
-constexpr int kLdsSlots = N2V_OTF_LDS_SLOTS;  // 16 B per slot and wave, plus the feed and row cache of n2v_wave_table.h
+// 16 B per slot and wave, plus the feed and row cache of n2v_wave_table.h.  6 KiB per wave -> 6 workgroups per CU:
+// C3 2.1 -> 2.6e8 steps/s vs 512 slots / 4 workgroups; 128: 2.5e8
+constexpr int kLdsSlots = 256;
 constexpr int kOtfRow = 256;   // two row buffers per wave: the row of `prev` (searched) and the row of `cur` (it is the next step's `prev`)
 constexpr int kLdsPerWg = 4 * (kLdsSlots * 16 + n2v::kFeed * 8 + 2 * kOtfRow * 4);
 constexpr int kWgPerCu = (160 * 1024 / kLdsPerWg) < 8 ? (160 * 1024 / kLdsPerWg) : 8;
@@ -95,9 +94,6 @@ struct OtfWave {
         int pk = kk;
         if (K <= 64 && a.draw_first) {                                // the table in registers, one slot per lane
             pk = n2v::wave_draw_le64(a.g, ws, prev, base, nb0, K, kk, u2, a.draw_first == 2 && a.exact_sum, a.wp, a.wq, lane);
-#ifdef N2V_OTF_LAB_ALWAYS_ACCEPT   /* timing ceiling of the fast path only: WRONG walks */
-            pk = pk < 0 ? pk : kk;
-#endif
             if (pk < 0) return -1;
         } else {
             bool drawn = false;
@@ -106,9 +102,6 @@ struct OtfWave {
                                                reinterpret_cast<int32_t*>(Tl), kLdsSlots * 4, reinterpret_cast<int32_t*>(ws.feed), lane);
                 if (d >= 0) { pk = d; drawn = true; }   // -2: more common neighbours than the sweep's list holds -> build
             }
-#ifdef N2V_OTF_LAB_ALWAYS_ACCEPT
-            drawn = true;
-#endif
             if (!drawn) {
                 n2v_alias_slot* T = K <= kLdsSlots ? Tl : Tg;
                 double norm;
@@ -347,9 +340,6 @@ int launch_otf(const char* who, bool hybrid, const int64_t* row_ptr, const int32
     // grid: as many resident waves as the scratch rows allow (4 workgroups of 4 waves per CU by LDS)
     int64_t blocks = (n_local + 3) / 4;
     if (blocks > 256 * kWgPerCu) blocks = 256 * kWgPerCu;   // every resident workgroup slot (LDS-bound), once
-#ifdef N2V_OTF_LAB_GRID_DIV
-    blocks = (blocks + N2V_OTF_LAB_GRID_DIV - 1) / N2V_OTF_LAB_GRID_DIV;
-#endif
     if (max_degree > kLdsSlots) {
         if (!scratch) return n2v::fail(N2V_ERR_INVALID, "%s: scratch needed (max degree %lld > %d)", who,
                                        (long long)max_degree, kLdsSlots);
@@ -361,11 +351,8 @@ int launch_otf(const char* who, bool hybrid, const int64_t* row_ptr, const int32
     // 2^-20 up to 2^10, degrees < 2^21
     const double wp = 1.0 / p, wq = 1.0 / q;
     auto dyadic = [](double x) { return x > 0.0 && x <= 1024.0 && x * 1048576.0 == (double)(int64_t)(x * 1048576.0); };
-    int32_t draw_first = (!w && symmetric) ? 2 : 1;
+    const int32_t draw_first = (!w && symmetric) ? 2 : 1;
     const int32_t exact_sum = dyadic(wp) && dyadic(wq) && max_degree < (1 << 21);
-#ifdef N2V_OTF_LAB_DRAW_FIRST   /* tools/lab/otf_variants.sh: 0 = always build the table, 1 = never count */
-    draw_first = N2V_OTF_LAB_DRAW_FIRST < draw_first ? N2V_OTF_LAB_DRAW_FIRST : draw_first;
-#endif
     OtfArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric}, starts, n_starts, pos_begin, pos_count, round_begin, n_local, walk_length,
               rng_mode, uniforms, walk_uoff, seed, scratch, max_degree, node_fat, fat, recs, walks, lens, status, draw_first, exact_sum, wp, wq};
     hipStream_t st = (hipStream_t)stream;

@@ -16,12 +16,6 @@ __device__ __forceinline__ void wave_sync() {  // order this wave's LDS / global
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
-// wave-uniform values that arrive through vector registers: make them scalar for the compiler, so the serial
-// loops branch on SCC and keep their counters in SGPRs
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ int64_t uni64(int64_t v) {
-    return ((int64_t)uni((int)(v >> 32)) << 32) | (uint32_t)uni((int)v);
-}
 __device__ __forceinline__ double unid(double v) {
     return __hiloint2double(uni(__double2hiint(v)), uni(__double2loint(v)));
 }
@@ -39,12 +33,6 @@ struct RowCtx {
     double p, q;
     int32_t symmetric;    // undirected graph: has_edge(nbr, src) == nbr in row(src), one shared row
 };
-
-#ifdef N2V_TAB_STAMPS   // diagnostic build only (tools/lab/tab_stamps.sh): shader cycles per phase, summed over waves
-#define N2V_STAMP(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); stamps[i] += now_ - t_last_; t_last_ = now_; } while (0)
-#else
-#define N2V_STAMP(i) do { } while (0)
-#endif
 
 // Per-wave LDS work area.
 //   feed: 64 doubles.  The left-to-right sum consumes its operands from here by broadcast reads (every lane reads the
@@ -248,20 +236,15 @@ struct AosSink {                           // q of a stream entry is already in 
 // to 0 (the reference raises ZeroDivisionError, :150 / :187).
 template <typename Slot>
 __device__ __forceinline__ bool wave_build_table(const RowCtx& a, Slot* T, const WaveScratch ws, int32_t src, int64_t base,
-                                                 int K, int lane, unsigned long long* stamps = nullptr) {
-#ifdef N2V_TAB_STAMPS
-    unsigned long long t_last_ = __builtin_amdgcn_s_memtime();
-#endif
+                                                 int K, int lane) {
     // ---- 1. unnormalised weights in parallel (:142-148)
     for (int k = lane; k < K; k += 64) T[k].q = step_weight(a, ws, src, base, k);
     wave_sync();
-    N2V_STAMP(0);
     // ---- 2. norm = sum(unnormalized_probs), strictly left to right (:149)
     double norm = 0.0;
     for (int c = 0; c < K; c += 64)
         norm = wave_sum_in_order(ws, norm, (c + lane < K) ? T[c + lane].q : 0.0, min(64, K - c), lane);
     norm = unid(norm);
-    N2V_STAMP(1);
     if (norm == 0.0) return false;
     // ---- 3. q = K * (u / norm) (:150 then :253, two roundings) and the two index stacks in index order
     //         (:252-257): `smaller` grows up from position 0, `larger` down from position K-1
@@ -287,12 +270,10 @@ __device__ __forceinline__ bool wave_build_table(const RowCtx& a, Slot* T, const
     ns = uni(ns);
     nl = uni(nl);
     wave_sync();
-    N2V_STAMP(2);
     // ---- 4. pairing (:259-268)
     AosSink<Slot> sink{T, lane};
     wave_pair(AosTable<Slot>{T}, sink, K, ns, nl, lane);
     wave_sync();
-    N2V_STAMP(3);
     return true;
 }
 
@@ -300,7 +281,7 @@ __device__ __forceinline__ bool wave_build_table(const RowCtx& a, Slot* T, const
 // alias_setup only ever rewrites q[large] (:264): a slot it classifies as `smaller` (q = K * prob < 1, :253-255) keeps
 // that q for good.  When the step's first uniform lands on such a slot kk and the second accepts it (u2 < q[kk], :278),
 // alias_draw returns kk without looking at J or at any other slot: the step needs the K weights, their left-to-right
-// sum and ONE division — not the classification, the stacks or the pairing (54-60 % of a table's cycles, tab_stamps).
+// sum and ONE division — not the classification, the stacks or the pairing (54-60 % of a table's cycles).
 // wave_weights_and_norm = phases 1-2 of wave_build_table; wave_finish_table = phases 3-4.
 template <typename Slot>
 __device__ __forceinline__ bool wave_weights_and_norm(const RowCtx& a, Slot* T, const WaveScratch ws, int32_t src, int64_t base,
@@ -698,17 +679,12 @@ struct QueueSink {
 
 template <typename Emit>
 __device__ __forceinline__ bool wave_build_stream(const RowCtx& a, const StreamStacks S, const WaveScratch ws,
-                                                  QueueSink<Emit>& sink, int32_t src, int64_t base, int K, int lane,
-                                                  unsigned long long* stamps = nullptr) {
-#ifdef N2V_TAB_STAMPS
-    unsigned long long t_last_ = __builtin_amdgcn_s_memtime();
-#endif
+                                                  QueueSink<Emit>& sink, int32_t src, int64_t base, int K, int lane) {
     // ---- 1 + 2. weights (:142-148) straight into the left-to-right sum (:149); nothing is stored
     double norm = 0.0;
     for (int c = 0; c < K; c += 64)
         norm = wave_sum_in_order(ws, norm, (c + lane < K) ? step_weight(a, ws, src, base, c + lane) : 0.0, min(64, K - c), lane);
     norm = unid(norm);
-    N2V_STAMP(1);
     if (norm == 0.0) return false;
     // ---- 3. the same weights again, q = K * (u / norm) (:150, :253), {k, q} onto the stack q selects (:252-257)
     const double Kd = (double)K;
@@ -732,11 +708,9 @@ __device__ __forceinline__ bool wave_build_stream(const RowCtx& a, const StreamS
     ns = uni(ns);
     nl = uni(nl);
     wave_sync();
-    N2V_STAMP(2);
     // ---- 4. pairing (:259-268); finished slots leave through the queue
     wave_pair(S, sink, K, ns, nl, lane);
     sink.finish();
-    N2V_STAMP(3);
     return true;
 }
 

@@ -29,8 +29,6 @@ SIGNATURES = {
     "n2v_last_error": (C.c_char_p, []),
     "n2v_alias_setup_tables": (C.c_int, [_i64, _ptr, _ptr, _ptr]),
     "n2v_build_node_tables": (C.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
-    "n2v_build_edge_tables": (C.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _f64, _f64, _i32, _ptr, _ptr, _i64, _i64,
-                                        _ptr, _ptr, _ptr]),
     "n2v_build_edge_tables_wave": (C.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _f64, _f64, _i32, _ptr, _ptr, _i64, _i64,
                                              _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr]),
     "n2v_edge_tables_wave_scratch_bytes": (C.c_int64, [_i64]),

@@ -62,7 +62,7 @@ class WalkEngine:
     def _stream(self):
         return _lib.stream_ptr(self.device)
 
-    def preprocess(self, first_order_shortcut=True, fat="auto", builder="wave", budget_bytes=None):
+    def preprocess(self, first_order_shortcut=True, fat="auto", budget_bytes=None):
         """preprocess_transition_probs (src/node2vec.py:176-204) on device.
 
         With p == q == 1 every (src,dst) table is bit-identical to dst's node table
@@ -72,8 +72,6 @@ class WalkEngine:
         fat: "auto" (fat 32-B slots if they fit, else thin 16-B slots), True, False, or "both" (tests / probes:
         thin and fat side by side).  The edge tables exist ONCE: the wave-per-table kernel writes the chosen
         layout directly; (J, q) of a stored fat table are recovered by `thin_view` for the dict-like views.
-        builder: "wave" (n2v_build_edge_tables_wave) or "lane" (round 1's one-lane-per-table kernel, kept as a
-        cross-check of the same bits).
         budget_bytes: tables under a memory budget — the middle path between stored tables and the reference's
         rebuild-every-step fallback (src/node2vec.py:34-53, src/settings.py:18).  If the fat edge tables exceed it,
         only the tables of entries (src -> dst) with deg(dst) <= D are stored (D = the largest cut that fits: every
@@ -99,7 +97,7 @@ class WalkEngine:
                 # host arithmetic (no device reduction before the big allocation)
                 from .csr import degree_cut_for_budget
                 self.stored_degree_cut, total = degree_cut_for_budget(csr, budget_bytes, FAT_BYTES)
-                self.partial, fat, builder = True, True, "wave"
+                self.partial, fat = True, True
             self.total_slots = total
             if fat == "auto":
                 fat = (nnz + (0 if self.first_order else total)) * FAT_BYTES < free - (8 << 30)
@@ -159,43 +157,28 @@ class WalkEngine:
                 # size-ordered list
                 src_of = torch.repeat_interleave(torch.arange(N, dtype=torch.int32, device=d), self.deg)
                 sym = 0 if csr.directed else 1
-                order = None
-                if builder == "lane":        # one lane per table: lanes of a wave should get tables of similar size
-                    order = torch.argsort(kdst, descending=True).to(torch.int32)
                 work = torch.zeros(2, dtype=torch.int64, device=d)
                 # per-wave stacks of the tables that do not fit the wave's LDS slots (C3: 0.8 GB for max degree 16 614)
                 built_max = self.stored_degree_cut if self.partial else self.max_degree
                 n_build = int(stored_entries.numel()) if self.partial else nnz
-                sbytes = int(self.lib.n2v_edge_tables_wave_scratch_bytes(built_max)) if builder == "wave" else 0
+                sbytes = int(self.lib.n2v_edge_tables_wave_scratch_bytes(built_max))
                 scratch = torch.empty(max(sbytes, 64) // 8, dtype=torch.int64, device=d)
                 tick("src_of")
                 if want_thin:
-                    if builder == "lane":
-                        _lib.check(self.lib.n2v_build_edge_tables(
-                            N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
-                            self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(order), 0, nnz,
-                            _lib.ptr(self.edge_slots), _lib.ptr(status), self._stream()))
-                    else:
-                        _lib.check(self.lib.n2v_build_edge_tables_wave(
-                            N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
-                            self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(stored_entries), 0, n_build, None,
-                            _lib.ptr(self.edge_slots), None, _lib.ptr(status), work[0:].data_ptr(), built_max,
-                            _lib.ptr(scratch), sbytes, self._stream()))
+                    _lib.check(self.lib.n2v_build_edge_tables_wave(
+                        N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
+                        self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(stored_entries), 0, n_build, None,
+                        _lib.ptr(self.edge_slots), None, _lib.ptr(status), work[0:].data_ptr(), built_max,
+                        _lib.ptr(scratch), sbytes, self._stream()))
                     tick("edge_tables_thin")
                 if want_fat:
-                    if builder == "lane":
-                        assert want_thin, "the lane builder writes thin tables; fat ones are expanded from them"
-                        _lib.check(self.lib.n2v_build_fat_slots(
-                            nnz, _lib.ptr(self.edge_off), _lib.ptr(self.col), _lib.ptr(self.row_ptr),
-                            _lib.ptr(self.edge_slots), _lib.ptr(self.recs), _lib.ptr(self.edge_fat), self._stream()))
-                    else:
-                        _lib.check(self.lib.n2v_build_edge_tables_wave(
-                            N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
-                            self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(stored_entries), 0, n_build,
-                            _lib.ptr(self.recs), None, _lib.ptr(self.edge_fat), _lib.ptr(status), work[1:].data_ptr(),
-                            built_max, _lib.ptr(scratch), sbytes, self._stream()))
+                    _lib.check(self.lib.n2v_build_edge_tables_wave(
+                        N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
+                        self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(stored_entries), 0, n_build,
+                        _lib.ptr(self.recs), None, _lib.ptr(self.edge_fat), _lib.ptr(status), work[1:].data_ptr(),
+                        built_max, _lib.ptr(scratch), sbytes, self._stream()))
                     tick("edge_tables_fat")
-                del order, src_of, kdst, scratch
+                del src_of, kdst, scratch
             if want_fat and nnz > 0:
                 self.node_fat = torch.empty((max(nnz, 1), 4), dtype=torch.int64, device=d)
                 _lib.check(self.lib.n2v_build_fat_slots(
@@ -224,25 +207,6 @@ class WalkEngine:
             self.timings[name] = self.timings.get(name, 0.0) + now - t[0]
             t[0] = now
         return tick
-
-    def build_fat(self):
-        """Expand stored THIN tables into 32-byte fat slots (probes; preprocess() writes fat tables directly)."""
-        if self.edge_slots is None:
-            raise RuntimeError("no thin edge tables to expand (preprocess(fat=False) first)")
-        csr, d = self.csr, self.device
-        N, nnz = csr.n_nodes, csr.nnz
-        with torch.cuda.device(d):
-            self.node_fat = torch.empty((max(nnz, 1), 4), dtype=torch.int64, device=d)
-            _lib.check(self.lib.n2v_build_fat_slots(
-                N, _lib.ptr(self.row_ptr), None, _lib.ptr(self.row_ptr), _lib.ptr(self.node_slots),
-                _lib.ptr(self.recs), _lib.ptr(self.node_fat), self._stream()))
-            if self.first_order:
-                self.edge_fat = self.node_fat
-            else:
-                self.edge_fat = torch.empty((max(self.total_slots, 1), 4), dtype=torch.int64, device=d)
-                _lib.check(self.lib.n2v_build_fat_slots(
-                    nnz, _lib.ptr(self.edge_off), _lib.ptr(self.col), _lib.ptr(self.row_ptr),
-                    _lib.ptr(self.edge_slots), _lib.ptr(self.recs), _lib.ptr(self.edge_fat), self._stream()))
 
     @property
     def ready(self):
@@ -330,8 +294,9 @@ class WalkEngine:
 
     def build_one_edge_table(self, e):
         """get_alias_edge (src/node2vec.py:133-152) for one CSR entry e = (src -> dst), built on demand by the
-        same kernel that fills the stored tables (one-table launch: the kernel reads src_of[e] and edge_off[e]
-        only, so one-element arrays are passed with their base shifted by -e)."""
+        same kernel that fills the stored tables (one-table launch: the kernel reads order[0], src_of[e] and
+        edge_off[e] only, so one-element arrays are passed with their base shifted by -e; a table of more than 512
+        slots needs the scratch of one workgroup, 48 B per slot rounded up to 16 slots)."""
         dst = int(self.csr.col[e])
         K = int(self.csr.row_ptr[dst + 1] - self.csr.row_ptr[dst])
         src = int(np.searchsorted(self.csr.row_ptr, e, side="right") - 1)
@@ -342,10 +307,12 @@ class WalkEngine:
             off = torch.zeros(1, dtype=torch.int64, device=d)
             src_of = torch.tensor([src], dtype=torch.int32, device=d)
             order = torch.tensor([e], dtype=torch.int64, device=d).to(torch.int32)
-            _lib.check(self.lib.n2v_build_edge_tables(
+            sbytes = 0 if K <= 512 else 48 * ((K + 15) // 16 * 16)
+            scratch = torch.empty(max(sbytes, 64) // 8, dtype=torch.int64, device=d)
+            _lib.check(self.lib.n2v_build_edge_tables_wave(
                 self.csr.n_nodes, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), src_of.data_ptr() - 4 * e,
-                self.p, self.q, 0 if self.csr.directed else 1, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1,
-                _lib.ptr(slots), _lib.ptr(status), self._stream()))
+                self.p, self.q, 0 if self.csr.directed else 1, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1, None,
+                _lib.ptr(slots), None, _lib.ptr(status), None, K, _lib.ptr(scratch), sbytes, self._stream()))
             if int(status.item()) & _lib.N2V_STATUS_ZERO_NORM:
                 raise ZeroDivisionError("float division by zero")
         s = slots[:K]

@@ -135,6 +135,18 @@ def test_tools_never_import_oracle():
             assert "oracle" not in txt, f
 
 
+def test_kernel_sources_have_no_build_switches():
+    """What the library builds is what it ships: no preprocessor conditionals (headers use #pragma once) and no lab
+    switches in node2vec-by-ecc_amd/csrc/."""
+    csrc = os.path.join(ROOT, "node2vec-by-ecc_amd", "csrc")
+    files = [f for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))]
+    assert any(f.endswith(".hip") for f in files)
+    for f in files:
+        txt = open(os.path.join(csrc, f)).read()
+        assert not re.search(r"^\s*#\s*(if|ifdef|ifndef|elif|else|endif)\b", txt, re.M), f
+        assert "LAB" not in txt, f
+
+
 def test_main_binds_the_rank_to_its_device_before_allocating(monkeypatch, tmp_path):
     """One process per GPU: main() must create the RankContext (which calls set_device(LOCAL_RANK)) BEFORE the graph
     and tables are allocated and hand that device to node2vec.Graph — otherwise every rank's tables land on cuda:0."""

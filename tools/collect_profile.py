@@ -31,7 +31,7 @@ if stats:
 
 def short(name):
     for key in ("sgns_kernel", "sgns_shared_kernel", "walk_fat2_kernel", "walk_fat_kernel", "walk_kernel",
-                "edge_tables_wave_kernel", "edge_tables_kernel", "fat_expand_kernel", "node_tables_kernel",
+                "edge_tables_wave_kernel", "fat_expand_kernel", "node_tables_kernel",
                 "edge_recs_kernel", "merge_snapshot_kernel", "merge_hot_apply_kernel", "merge_flush_kernel"):
         if key in name:
             return key

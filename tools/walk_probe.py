@@ -36,14 +36,10 @@ def main():
         g._engine = eng
         torch.cuda.synchronize()
         t = time.perf_counter()
-        eng.preprocess(fat=False)
+        eng.preprocess(fat="both")
         torch.cuda.synchronize()
-        t_thin = time.perf_counter() - t
-        t = time.perf_counter()
-        eng.build_fat()
-        torch.cuda.synchronize()
-        print(name, "preprocess thin %.3fs + fat expansion %.3fs  slots=%d (thin %.1f GB, fat %.1f GB) first_order=%s" % (
-            t_thin, time.perf_counter() - t, eng.total_slots, eng.total_slots * 16 / 1e9, eng.total_slots * 32 / 1e9,
+        print(name, "preprocess thin + fat %.3fs  slots=%d (thin %.1f GB, fat %.1f GB) first_order=%s" % (
+            time.perf_counter() - t, eng.total_slots, eng.total_slots * 16 / 1e9, eng.total_slots * 32 / 1e9,
             eng.first_order), flush=True)
         L = 80
         for layout in ("thin", "fat"):
