@@ -135,8 +135,9 @@ int n2v_bine_init(double* emb, double* ctx, int64_t n, int32_t dim, int32_t row_
  * visited_v dictionaries: a vertex is handled at its first rating, :462,475), then the KL update.
  * Skip-gram block of vertex c: min(#occurrences, 10) distinct occurrences of c in its side's
  * walks (random.sample, :465); per occurrence the window contexts z != c (window ws, within the
- * walk) and up to ns negatives — distinct slots of pool[c], dropped when empty (-1: a pool shorter than pool_size),
- * inside the window or repeated (src/bine_graph_utils.py:163-187) — then skip_gram(c, z, negs) for every z.
+ * walk) and up to ns negatives — min(ns, valid) distinct slots of the valid prefix of pool[c] (a pool row holds
+ * `valid` vertices, then -1 up to pool_size; random.sample(negs, min(num_negs, len(negs))), src/bine_graph_utils.py:185),
+ * dropped when inside the window or repeated (:163-187) — then skip_gram(c, z, negs) for every z.
  * Occurrence index: occ_ptr int64[n+1], occ_pos int64[n_tokens] (token positions of each vertex,
  * ascending), tokens int32[n_tokens], tok_walk int32[n_tokens] (walk of each token), walk_off
  * int64[n_walks+1]; both sides in one token array (walks of users, then walks of items).
@@ -148,8 +149,9 @@ int n2v_bine_init(double* emb, double* ctx, int64_t n, int32_t dim, int32_t row_
  * (n2v_bine_lambda_step resets it).
  * mode N2V_BINE_SEQUENTIAL: one wavefront walks the list in order with plain loads/stores — the
  * reference's exact update order (used for parity tests, small inputs).  N2V_BINE_PARALLEL:
- * wavefronts take ratings e, e+W, ...; rows are read at agent scope and updated with fp64 atomic
- * adds (no update lost; Hogwild ordering).  N2V_BINE_PARALLEL_STORE: the same, except that the context rows
+ * wavefronts take chunks of 16 consecutive ratings from the counter in state[6] (a range of at most 16
+ * ratings is one chunk: one wavefront, the sequential order); rows are read at agent scope and updated with
+ * fp64 atomic adds (no update lost; Hogwild ordering).  N2V_BINE_PARALLEL_STORE: the same, except that the context rows
  * of an occurrence (its centre and negatives) are written back whole with agent-scope stores — the fp64
  * atomic rate is what bounds the pass, and these rows are shared only when a vertex happens to be another
  * wavefront's negative at that moment (that racing update is then lost).  Ratings [e_begin, e_end) are

@@ -428,6 +428,17 @@ __device__ __forceinline__ void node_block(const TrainArgs& a, int32_t c, double
         return k < 4u ? w0 : (k < 8u ? w1 : w2);
     });
     const int stride = a.row_stride;
+    // the pool row holds `valid` vertices, then -1 (an LSH pool of a side smaller than pool_size); negatives are
+    // min(ns, valid) distinct slots of that prefix, random.sample(negs, min(num_negs, len(negs))) of
+    // src/bine_graph_utils.py:185.  A full row is the common case: its last slot decides it.
+    const int32_t* prow = a.pool + (int64_t)c * a.pool_size;
+    uint32_t valid = (uint32_t)a.pool_size;
+    if (uni(prow[a.pool_size - 1]) < 0) {
+        valid = 0;
+        for (int32_t s0 = 0; s0 < a.pool_size; s0 += 64)
+            valid += (uint32_t)__popcll(__ballot(s0 + lane < a.pool_size && prow[s0 + lane] >= 0));
+    }
+    const uint32_t m2 = (uint32_t)a.ns < valid ? (uint32_t)a.ns : valid;
     for (uint32_t k = 0; k < m; ++k) {
         const uint32_t idx = (uint32_t)uni(__shfl((int)my_occ, (int)k));
         const int64_t o = uni64(a.occ_pos[ob + idx]);
@@ -437,12 +448,11 @@ __device__ __forceinline__ void node_block(const TrainArgs& a, int32_t c, double
         const int64_t e = o + a.ws + 1 < w1 ? o + a.ws + 1 : w1;    // min(len, iter + win_size + 1)
         const int nwin = (int)(e - s);
         const int32_t mytok = lane < nwin ? a.tokens[s + lane] : -1;
-        // negatives: distinct pool slots; dropped when in the window or already taken
+        // negatives: distinct slots of the pool's valid prefix; dropped when in the window or already taken
         uint32_t rn0[4], rn1[4];
         philox4x32_10(a.seed_neg, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), 0u, 0u, rn0);
         philox4x32_10(a.seed_neg, (uint32_t)o, (uint32_t)((uint64_t)o >> 32), 1u, 0u, rn1);
-        const uint32_t m2 = (uint32_t)a.ns < (uint32_t)a.pool_size ? (uint32_t)a.ns : (uint32_t)a.pool_size;
-        const uint32_t my_slot = floyd_sample((uint32_t)a.pool_size, m2, lane, [&](uint32_t q) {
+        const uint32_t my_slot = floyd_sample(valid, m2, lane, [&](uint32_t q) {
             uint32_t w0 = rn0[0], w1 = rn1[0];
 #pragma unroll
             for (int z = 1; z < 4; ++z) {
@@ -452,7 +462,7 @@ __device__ __forceinline__ void node_block(const TrainArgs& a, int32_t c, double
             return q < 4u ? w0 : w1;
         });
         int32_t my_neg = -1;
-        if (lane < (int)m2) my_neg = a.pool[(int64_t)c * a.pool_size + my_slot];
+        if (lane < (int)m2) my_neg = prow[my_slot];
         int32_t tgt[NT];
 #pragma unroll
         for (int z = 0; z < NT; ++z) tgt[z] = -1;
@@ -462,7 +472,8 @@ __device__ __forceinline__ void node_block(const TrainArgs& a, int32_t c, double
         for (int q = 0; q < NT - 1; ++q) {
             if (q < (int)m2) {
                 const int32_t cand = uni(__shfl(my_neg, q));
-                bool drop = cand < 0 || __ballot(mytok == cand) != 0ull;  // empty slot; in the window (src/bine_graph_utils.py:179-180)
+                // in the window (src/bine_graph_utils.py:179-180); cand < 0 only guards a row that breaks the prefix rule
+                bool drop = cand < 0 || __ballot(mytok == cand) != 0ull;
 #pragma unroll
                 for (int z = 0; z < NT; ++z) drop = drop || (z < nt && tgt[z] == cand);  // I_z is a dict: one entry per vertex
                 if (!drop) {

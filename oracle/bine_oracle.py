@@ -14,6 +14,11 @@ draw from an unseeded `random.Random()` default argument (src/bine_graph.py:169,
      (training).
 tests/ check (P) == HIP exactly and (P) ~ (L) statistically (chi-square on next-vertex and length
 distributions), so the chain reference-text -> (L) -> (P) -> HIP is closed without the reference running.
+
+Negatives of a short pool follow the reference's rule: a pool row holds a prefix of `valid` vertices, then -1
+(LSH pools of a side smaller than pool_size), and an occurrence draws min(ns, valid) distinct slots of that prefix,
+as `random.sample(negs, min(num_negs, len(negs)))` does (src/bine_graph_utils.py:185).  A full row draws exactly
+the slots it always did.
 """
 import math
 
@@ -205,21 +210,35 @@ def sample_occurrences(c, n_occ, iteration, seed_occ):
     return floyd_sample(n_occ, m, words)
 
 
-def occurrence_context(o, c, tokens, tok_walk, walk_off, pool_row, ws, ns, seed_neg):
+def pool_valid(pool_row):
+    """Number of vertices in a pool row: a prefix of non-negative entries, then -1 up to pool_size."""
+    row = [int(x) for x in pool_row]
+    valid = sum(1 for x in row if x >= 0)
+    if any(x < 0 for x in row[:valid]):
+        raise ValueError("pool row is not a valid prefix followed by -1")
+    return valid
+
+
+def occurrence_context(o, c, tokens, tok_walk, walk_off, pool_row, ws, ns, seed_neg, stats=None):
     """Contexts and negatives of the occurrence at token position o of vertex c
     (src/bine_graph_utils.py:169-187: window within the walk, tokens equal to the centre skipped; negatives
-    = distinct pool slots, dropped when empty, inside the window or repeated)."""
+    = min(ns, valid) distinct slots of the pool's valid prefix, dropped when inside the window or repeated).
+    `stats` (optional dict): counts negatives dropped for being in the window ("neg_in_window")."""
     wk = int(tok_walk[o])
     w0, w1 = int(walk_off[wk]), int(walk_off[wk + 1])
     s, e = max(w0, o - ws), min(w1, o + ws + 1)
     window = [int(x) for x in tokens[s:e]]
     contexts = [z for z in window if z != c]
     words = list(_philox(seed_neg, o, o >> 32, 0, 0)) + list(_philox(seed_neg, o, o >> 32, 1, 0))
-    m2 = min(ns, len(pool_row))
+    valid = pool_valid(pool_row)
     negs = []
-    for slot in floyd_sample(len(pool_row), m2, words):
+    for slot in floyd_sample(valid, min(ns, valid), words):
         cand = int(pool_row[slot])
-        if cand < 0 or cand in window or cand in negs or cand == c:   # -1: empty slot of a short pool
+        if cand in window:
+            if stats is not None:
+                stats["neg_in_window"] = stats.get("neg_in_window", 0) + 1
+            continue
+        if cand in negs or cand == c:
             continue
         negs.append(cand)
     return contexts, negs
@@ -260,11 +279,23 @@ def kl_divergence(e_ij, u, v, emb, lam, gamma):
 
 
 def train(edge_u, edge_v, edge_w, emb, ctx, occ_ptr, occ_pos, tokens, tok_walk, walk_off, pool, ws, ns, alpha, beta,
-          gamma, lam, max_iter, seed_occ, seed_neg, epsilon=1e-3, first=None):
+          gamma, lam, max_iter, seed_occ, seed_neg, epsilon=1e-3, first=None, stats=None):
     """The loop of src/bine_train.py:452-504 over the rating list, with the device's sampling rule for the
     occurrences / negatives (the reference uses the global `random`).  emb, ctx: float64 [N, d], updated in
     place.  `first` (optional, uint8 per rating: bit 0 user, bit 1 item) replaces the visited dictionaries when
-    only a sample of the rating list is passed.  Returns (lam, per-iteration losses)."""
+    only a sample of the rating list is passed.  Returns (lam, per-iteration losses).
+
+    `stats` (optional dict) is filled with counts over all iterations: "rows_ref", the rows the reference's
+    access pattern moves (2 + 2 * (1 + len(negs)) per skip_gram call, 4 per KL update: what the kernel adds to
+    state[5]), and what the data exercised: "blocks", "empty" (blocks of a vertex without occurrences), "capped"
+    (blocks of more than 10 occurrences), "occurrences", "max_window" (tokens in the widest window),
+    "repeat_context" (context lists holding one vertex twice in a row, a walk z c z), "short_pool" (occurrences
+    drawing from a pool with -1 slots), "negs_cut" (occurrences whose pool holds fewer vertices than ns) and
+    "neg_in_window"."""
+    if stats is not None:
+        for k in ("rows_ref", "blocks", "empty", "capped", "occurrences", "max_window", "repeat_context",
+                  "short_pool", "negs_cut", "neg_in_window"):
+            stats.setdefault(k, 0)
     last_loss = 0.0
     losses = []
     for it in range(max_iter):
@@ -281,13 +312,30 @@ def train(edge_u, edge_v, edge_w, emb, ctx, occ_ptr, occ_pos, tokens, tok_walk, 
                 seen.add(c)
                 ob = int(occ_ptr[c])
                 n_occ = int(occ_ptr[c + 1]) - ob
+                if stats is not None:
+                    stats["blocks"] += 1
+                    stats["empty"] += n_occ == 0
+                    stats["capped"] += n_occ > 10
                 for idx in sample_occurrences(c, n_occ, it, seed_occ):
                     o = int(occ_pos[ob + idx])
-                    contexts, negs = occurrence_context(o, c, tokens, tok_walk, walk_off, pool[c], ws, ns, seed_neg)
+                    contexts, negs = occurrence_context(o, c, tokens, tok_walk, walk_off, pool[c], ws, ns, seed_neg,
+                                                        stats)
+                    if stats is not None:
+                        wk = int(tok_walk[o])
+                        valid = pool_valid(pool[c])
+                        stats["occurrences"] += 1
+                        stats["max_window"] = max(stats["max_window"],
+                                                  min(int(walk_off[wk + 1]), o + ws + 1) - max(int(walk_off[wk]), o - ws))
+                        stats["repeat_context"] += any(x == y for x, y in zip(contexts[:-1], contexts[1:]))
+                        stats["short_pool"] += valid < len(pool[c])
+                        stats["negs_cut"] += valid < ns
+                        stats["rows_ref"] += len(contexts) * (2 + 2 * (1 + len(negs)))
                     for z in contexts:
                         tmp_z, tmp_loss = skip_gram(c, z, negs, emb, ctx, lam, pa)
                         emb[z] += tmp_z
                         loss += tmp_loss
+            if stats is not None:
+                stats["rows_ref"] += 4
             update_u, update_v, tmp_loss = kl_divergence(w, u, v, emb, lam, gamma)
             loss += tmp_loss
             emb[u] += update_u

@@ -7,6 +7,7 @@ DISTINCT two-hop vertices, geometric walk lengths, HITS direction."""
 import math
 import os
 import random
+import re
 import sys
 
 import numpy as np
@@ -265,3 +266,92 @@ def test_bine_replica_merge_with_fp32_wire():
     assert torch.allclose(eng.emb, base + 2e-3, rtol=0, atol=1e-9) and eng.emb.dtype == torch.float64
     want = base.clone(); want[1] -= 0.5
     assert torch.equal(eng.ctx, want) and eng.state[1].item() == -4.0
+
+
+def _old_negatives(o, c, window, pool_row, ns, seed_neg):
+    """The negative rule before short pools drew from their valid prefix: Floyd over the whole row, -1 slots dropped."""
+    words = list(bo._philox(seed_neg, o, o >> 32, 0, 0)) + list(bo._philox(seed_neg, o, o >> 32, 1, 0))
+    negs = []
+    for slot in bo.floyd_sample(len(pool_row), min(ns, len(pool_row)), words):
+        cand = int(pool_row[slot])
+        if cand < 0 or cand in window or cand in negs or cand == c:
+            continue
+        negs.append(cand)
+    return negs
+
+
+def _one_walk(n_tok=9):
+    tokens = np.arange(n_tok)                       # one walk of distinct vertices 0..n_tok-1
+    return tokens, np.zeros(n_tok, dtype=np.int64), np.array([0, n_tok])
+
+
+def test_short_pool_draws_min_ns_valid_negatives():
+    """A pool row of `valid` vertices then -1: with no pool entry in the window an occurrence gets exactly
+    min(ns, valid) distinct negatives, all from the prefix (random.sample(negs, min(num_negs, len(negs))))."""
+    tokens, tok_walk, walk_off = _one_walk()
+    for valid in (0, 1, 3, 5, 11):
+        row = np.full(12, -1, dtype=np.int32)
+        row[:valid] = 100 + np.arange(valid)
+        assert bo.pool_valid(row) == valid
+        for ns in range(8):
+            for o in range(9):
+                contexts, negs = bo.occurrence_context(o, int(tokens[o]), tokens, tok_walk, walk_off, row, 2, ns,
+                                                       seed_neg=77 + o)
+                assert len(negs) == min(ns, valid), (valid, ns, o, negs)
+                assert len(set(negs)) == len(negs) and set(negs) <= set(row[:valid].tolist())
+                assert contexts == [int(x) for x in tokens[max(0, o - 2):o + 3] if x != o]
+    with pytest.raises(ValueError):
+        bo.pool_valid(np.array([3, -1, 4]))
+
+
+def test_full_pool_rows_keep_their_slots():
+    """Every full row (all Jaccard pools, LSH pools of large sides) draws exactly what the old rule drew."""
+    tokens, tok_walk, walk_off = _one_walk()
+    rs = np.random.RandomState(4)
+    seen_drop = False
+    for trial in range(400):
+        size = int(rs.randint(1, 30))
+        row = rs.randint(0, 14, size=size)          # repeats and in-window vertices (0..8) included
+        ns = int(rs.randint(0, 8))
+        o = int(rs.randint(0, 9))
+        window = [int(x) for x in tokens[max(0, o - 3):o + 4]]
+        _, negs = bo.occurrence_context(o, o, tokens, tok_walk, walk_off, row, 3, ns, seed_neg=1000 + trial)
+        assert negs == _old_negatives(o, o, window, row, ns, 1000 + trial)
+        seen_drop = seen_drop or len(negs) < min(ns, size)
+    assert seen_drop
+
+
+def test_training_restatement_counts_rows_ref():
+    """stats on a hand-checked case.  Vertices 0, 1, 3 are users, 2 an item; walks [0 1 0] and [2]; ns = 2.
+    Rating (0, 2): block of 0 = two occurrences, each one context (1) and negatives [3] (1 is in the window):
+    2 x (2 + 2 x 2); block of 2: no context; KL 4.  Rating (1, 2): block of 1 = one occurrence, contexts [0, 0]
+    (walk z c z), negatives [3] from a pool of one vertex: 2 x 6; KL 4.  Rating (3, 2): block of 3 without
+    occurrences; KL 4.  rows_ref = 12 + 4 + 12 + 4 + 4."""
+    tokens = np.array([0, 1, 0, 2])
+    tok_walk = np.array([0, 0, 0, 1])
+    walk_off = np.array([0, 3, 4])
+    occ_pos = np.argsort(tokens, kind="stable")
+    occ_ptr = np.concatenate([[0], np.cumsum(np.bincount(tokens, minlength=4))])
+    pool = np.array([[3, 1], [3, -1], [2, 3], [0, 1]])
+    rs = np.random.RandomState(0)
+    emb, ctx = rs.random_sample((4, 3)), rs.random_sample((4, 3))
+    stats = {}
+    bo.train(np.array([0, 1, 3]), np.array([2, 2, 2]), np.ones(3), emb, ctx, occ_ptr, occ_pos, tokens, tok_walk,
+             walk_off, pool, 5, 2, 0.01, 0.01, 0.1, 0.01, 1, 3, 4, stats=stats)
+    assert stats == dict(rows_ref=36, blocks=4, empty=1, capped=0, occurrences=4, max_window=3, repeat_context=1,
+                         short_pool=1, negs_cut=1, neg_in_window=3)
+    # per iteration: two iterations count twice (the learning-rate step does not change what is moved)
+    stats2 = {}
+    emb, ctx = rs.random_sample((4, 3)), rs.random_sample((4, 3))
+    _, losses = bo.train(np.array([0, 1, 3]), np.array([2, 2, 2]), np.ones(3), emb, ctx, occ_ptr, occ_pos, tokens,
+                         tok_walk, walk_off, pool, 5, 2, 0.01, 0.01, 0.1, 0.01, 2, 3, 4, epsilon=0.0, stats=stats2)
+    assert len(losses) == 2 and stats2["rows_ref"] == 72 and stats2["blocks"] == 8
+
+
+def test_train_kernel_hands_out_chunks_of_16():
+    """tests/test_gpu_bine_exact.py runs the parallel modes deterministically by launching ranges of at most 16
+    ratings: one such range is one chunk of the work counter, taken whole by one wavefront."""
+    src = open(os.path.join(ROOT, "node2vec-by-ecc_amd", "csrc", "n2v_bine.hip")).read()
+    assert re.findall(r"constexpr\s+int64_t\s+kChunk\s*=\s*(\d+)\s*;", src) == ["16"]
+    import test_gpu_bine_exact as ex
+    assert ex.KCHUNK == 16

@@ -3,8 +3,9 @@
 Bit-exact: walk lengths, walks, negative pools (all integer work, Philox-driven).  fp64 rounding: HITS
 scores, initial rows, and the sequential training mode against the numpy restatement of
 src/bine_train.py:243-309,452-504 (tolerance 1e-9 relative: numpy's BLAS dot and the wave butterfly sum in a
-different order; exp/log differ by <= 1 ulp).  The parallel mode is checked against the sequential one
-through its loss trajectory.  The reference's own BiNE code cannot run (oracle header): parity unpinned at
+different order; exp/log differ by <= 1 ulp).  Multi-wave parallel runs are checked against the sequential mode
+through their loss trajectories; every training kernel variant, the parallel ones included, is pinned to the
+restatement by tests/test_gpu_bine_exact.py.  The reference's own BiNE code cannot run (oracle header): parity unpinned at
 the bit level, closed statistically by tests/test_bine_host.py."""
 import numpy as np
 import pytest

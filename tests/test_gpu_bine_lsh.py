@@ -96,8 +96,10 @@ def test_lsh_pools_equal_restatement(n_u, n_v, k, pool_size, seed):
 
 
 def test_integer_labels_and_training_with_short_pools():
-    """Integer labels hash as their decimal text; a side smaller than the pool leaves -1 slots that the training
-    pass skips (random.sample(negs, min(num_negs, len(negs))), src/bine_graph_utils.py:185)."""
+    """Integer labels hash as their decimal text; a side smaller than the pool leaves -1 slots after a valid prefix,
+    and the training pass draws min(ns, valid) negatives from that prefix (random.sample(negs, min(num_negs,
+    len(negs))), src/bine_graph_utils.py:185): the pass equals the restatement of oracle/bine_oracle.py."""
+    from oracle import bine_oracle as bo
     from n2v_hip import bine
     g0 = clustered_graph(60, 20, 5)
     users = np.array([int(str(x)[1:]) for x in g0.user_labels])[g0.edge_u]
@@ -114,9 +116,20 @@ def test_integer_labels_and_training_with_short_pools():
     e.build_occurrences()
     e.init_embeddings(d=16)
     before = e.emb.clone()
+    emb, ctx = e.emb[:, :16].cpu().numpy().copy(), e.ctx[:, :16].cpu().numpy().copy()
     e.reset_schedule()
     e.train_pass(0, mode="sequential")
     assert bool(np.isfinite(e.emb.cpu().numpy()).all()) and not bool((e.emb == before).all())
+    stats = {}
+    _, losses = bo.train(g.edge_u, g.edge_v, g.edge_w, emb, ctx, e.occ_ptr.cpu().numpy(), e.occ_pos.cpu().numpy(),
+                         e.tokens.cpu().numpy(), e.tok_walk.cpu().numpy(), e.walk_off.cpu().numpy(), e.pool.cpu().numpy(),
+                         5, 4, 0.01, 0.01, 0.1, 0.01, 1, bine.derive_seed(e.seed, bine.SEED_OCC),
+                         bine.derive_seed(e.seed, bine.SEED_NEG), stats=stats)
+    assert stats["short_pool"] > 0
+    assert e.state[1].item() == pytest.approx(losses[0], rel=1e-9)
+    assert e.state[5].item() == stats["rows_ref"]
+    assert np.allclose(e.emb[:, :16].cpu().numpy(), emb, rtol=1e-9, atol=1e-12)
+    assert np.allclose(e.ctx[:, :16].cpu().numpy(), ctx, rtol=1e-9, atol=1e-12)
 
 
 def test_pools_never_hold_similar_vertices_on_a_larger_graph():
