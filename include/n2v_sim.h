@@ -64,7 +64,9 @@ int n2v_sim_topk_scan(const float* A, int64_t row_begin, int64_t row_end, const 
  *   n2v_sim_rows_fill : cols/vals at out_off[r] .. (out_off: int64[n_rows], exclusive prefix of counts)
  *   n2v_sim_rows_topk : the k largest of every row — all scores above the k-th largest value plus the first
  *                       ties of it in column order, i.e. exactly sorted(..., key=-score)[:k] as a SET
- *                       (:379-394,426-440); cols/vals: [n_rows][k].  NaN ranks lowest.  k <= n_cols.       */
+ *                       (:379-394,426-440); cols/vals: [n_rows][k].  NaN ranks lowest.  k <= n_cols.
+ *                       -0.0 and +0.0 tie, as they do for Python's sort (column order decides between them);
+ *                       a selected -0.0 is returned as -0.0.                                                */
 int n2v_sim_rows_count(const float* scores, int64_t n_rows, int64_t n_cols, int64_t ld, float thre,
                        int64_t* counts, void* stream);
 int n2v_sim_rows_fill(const float* scores, int64_t n_rows, int64_t n_cols, int64_t ld, float thre,

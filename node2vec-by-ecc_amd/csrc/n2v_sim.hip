@@ -286,9 +286,10 @@ rows_fill_kernel(const float* __restrict__ scores, int64_t n_cols, int64_t ld, f
     }
 }
 
-// order-preserving key: larger float <=> larger key; NaN lowest
+// order-preserving key: larger float <=> larger key; NaN lowest; -0.0 and +0.0 compare equal and share a key
 __device__ __forceinline__ uint32_t order_key(float v) {
     if (v != v) return 0u;
+    if (v == 0.f) return 0x80000000u;
     const uint32_t u = __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }

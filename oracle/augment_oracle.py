@@ -7,10 +7,17 @@ these functions; the text was restated by reading it."""
 import numpy as np
 
 
+def unitvec(x):
+    """gensim matutils.unitvec: x / norm, a vector of norm 0 returned as it is (include/n2v_sim.h, "COS"; the comment in
+    sim_prepare_kernel of csrc/n2v_sim.hip) — so the similarity with a zero vector is 0, not NaN."""
+    nrm = np.linalg.norm(x)
+    return x / nrm if nrm > 0 else x
+
+
 def similarity(emb, a, b):
     """gensim KeyedVectors.similarity: dot of the unit vectors (float32), src/main_link.py:359-360."""
     x, y = np.asarray(emb[a], dtype=np.float32), np.asarray(emb[b], dtype=np.float32)
-    return float(np.dot(x / np.linalg.norm(x), y / np.linalg.norm(y)))
+    return float(np.dot(unitvec(x), unitvec(y)))
 
 
 def js(p, q):                                                       # :351-356

@@ -11,10 +11,16 @@ import numpy as np
 KS = [1, 10, 50, 100, 500, 1000]   # default `ks` of link_prediction (:123)
 
 
+def unitvec(x):
+    """gensim matutils.unitvec: a vector of norm 0 is returned as it is (include/n2v_sim.h, "COS"): similarity 0, not NaN."""
+    nrm = np.linalg.norm(x)
+    return x / nrm if nrm > 0 else x
+
+
 def similarity(emb, a, b):
     """gensim KeyedVectors.similarity (link_method "cos", :44-49): float32 dot of the unit vectors."""
     x, y = np.asarray(emb[a], dtype=np.float32), np.asarray(emb[b], dtype=np.float32)
-    return float(np.dot(x / np.linalg.norm(x), y / np.linalg.norm(y)))
+    return float(np.dot(unitvec(x), unitvec(y)))
 
 
 def precision_at_k(pred_k, test_edges):                                   # :62-67
@@ -96,7 +102,7 @@ def link_prediction_vectorised(unseparated, g, emb, train_edges, test_edges, ks=
     else:
         cols = [x for x in names if x.startswith('9999999')]
         rows = [x for x in names if not x.startswith('9999999')]
-    unit = lambda n: np.stack([np.asarray(emb[x], np.float32) / np.linalg.norm(np.asarray(emb[x], np.float32)) for x in n])
+    unit = lambda n: np.stack([unitvec(np.asarray(emb[x], np.float32)) for x in n])
     S = unit(rows) @ unit(cols).T
     if unseparated:
         S[np.tril_indices(len(rows))] = -np.inf

@@ -26,6 +26,8 @@ def test_selection_matches_restatement(torch_cuda, mode, ratio, thre, sim_method
     rs = np.random.RandomState(5)
     n, d = 157, 48
     vec = rs.normal(size=(n, d)).astype(np.float32)
+    if sim_method == "cos":
+        vec[11] = 0.0      # gensim unitvec leaves a zero vector alone: every score with it is 0, on both sides
     users = [int(x) for x in rs.permutation(1000)[:n]]
     emb = {u: vec[i] for i, u in enumerate(users)}
     want = augment_oracle.add_user_edge(users, emb, mode, ratio, thre, sim_method)
@@ -67,7 +69,11 @@ def test_rows_topk_with_ties_is_the_stable_sort_prefix(torch_cuda):
     sc[3, 17] = np.nan
     sc[4] = rs.normal(size=n_cols).astype(np.float32)
     dev = torch.from_numpy(sc).cuda()
-    for k in (1, 2, 255, 256, 257, 999, 1000):
+    # a k inside row 2's run of zeros (+0.0 and -0.0 tie there: Python's sort keeps their column order)
+    n_pos, n_zero = int((sc[2] > 0).sum()), int((sc[2] == 0).sum())
+    k_zero = n_pos + n_zero // 2
+    assert n_pos < k_zero < n_pos + n_zero and np.signbit(sc[2][sc[2] == 0]).any() and not np.signbit(sc[2][sc[2] == 0]).all()
+    for k in (1, 2, 255, 256, 257, k_zero, 999, 1000):
         cols, vals = simsel.rows_topk(dev, n_cols, k)
         cols, vals = cols.cpu().numpy(), vals.cpu().numpy()
         for r in range(n_rows):
