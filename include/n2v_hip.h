@@ -29,13 +29,16 @@
 extern "C" {
 #endif
 
-#define N2V_ABI_VERSION 3
+#define N2V_ABI_VERSION 4
 
 #define N2V_OK 0
 #define N2V_ERR_INVALID (-1)   /* bad argument (null pointer, negative size, limit exceeded) */
 #define N2V_ERR_HIP (-2)       /* HIP runtime error */
 #define N2V_STATUS_ZERO_NORM 1 /* device status bit: a neighbourhood's weights sum to 0
                                   (the reference raises ZeroDivisionError, src/node2vec.py:150,187) */
+#define N2V_STATUS_ZERO_POP 2  /* device status bit of the pop-rule entry points: a popularity-weighted neighbourhood could
+                                  not be normalised — a neighbour without out-edges (division by len(G[nbr]) = 0,
+                                  src/node2vec.py:21,166-170,218) or a zero sum; ZeroDivisionError in the reference */
 
 /* One alias slot: (J[k], q[k]) of src/node2vec.py:240-269, 16 B so a draw is one
  * aligned 16-B load.  `aux` is scratch during construction (Vose's two stacks), then 0. */
@@ -75,6 +78,16 @@ int n2v_alias_setup_tables(int64_t n_tables, const int64_t* tab_off, n2v_alias_s
 int n2v_build_node_tables(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col,
                           const double* w, n2v_alias_slot* slots, int32_t* status, void* stream);
 
+/* Pop node tables (src/node2vec.py:13-25 with popwalk == "pop", :213-221) of the nodes [v_begin, v_end): the weight of
+ * neighbour k of v is w / (row_ptr[nbr+1] - row_ptr[nbr]) — divided by the neighbour's (out-)degree — unless plain[v] != 0
+ * (uint8[n_nodes]: the nodes whose label starts with 9999999, which keep the plain weights; the caller computes the flags).
+ * The table of v is written to slots[row_ptr[v] - row_ptr[v_begin] ...]: v_begin = 0 gives the layout of
+ * n2v_build_node_tables, [v, v+1) one table on demand at slots[0 ...].  row_ptr and col are the whole graph's in both
+ * cases (the neighbours' degrees are read).  status: N2V_STATUS_ZERO_POP / N2V_STATUS_ZERO_NORM.                      */
+int n2v_build_node_tables_pop(int64_t v_begin, int64_t v_end, const int64_t* row_ptr, const int32_t* col,
+                              const double* w, const uint8_t* plain, n2v_alias_slot* slots, int32_t* status,
+                              void* stream);
+
 /* Edge tables (src/node2vec.py:133-152,193-199): for CSR entries e in [e_begin, e_end) — or, if `order` != NULL,
  * for order[i], i in [e_begin, e_end) — the table of (src -> dst=col[e]) is built, deg(dst) slots, by ONE WAVEFRONT
  * per table with coalesced row reads.  edge_off: int64[nnz+1], exclusive prefix sum of deg(col[e]).  `src_of`:
@@ -99,6 +112,17 @@ int n2v_build_edge_tables_wave(int64_t n_nodes, const int64_t* row_ptr, const in
                                const n2v_edge_rec* recs, n2v_alias_slot* thin, struct n2v_fat_slot* fat,
                                int32_t* status, uint64_t* work_counter, int64_t max_degree, void* scratch,
                                int64_t scratch_bytes, void* stream);
+
+/* get_alias_edge_pop (src/node2vec.py:154-174) by the same wavefront-per-table builder: the weight of neighbour x of dst
+ * is w / (p * pop(x)) for x == src and w / pop(x) otherwise, pop(x) = row_ptr[x+1] - row_ptr[x]; q does not enter and
+ * there is no exemption for item labels.  Thin output only (thin[edge_off[e] ...]) and static hand-out: meant for the
+ * one-table-on-demand call; the reference never stores these tables (its precomputed popularity mode keeps the plain
+ * edge tables, :223-232).  Other arguments, scratch included, as for n2v_build_edge_tables_wave.  status:
+ * N2V_STATUS_ZERO_POP.                                                                                                */
+int n2v_build_edge_tables_wave_pop(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col, const double* w,
+                                   const int32_t* src_of, double p, const int64_t* edge_off, const int32_t* order,
+                                   int64_t e_begin, int64_t e_end, n2v_alias_slot* thin, int32_t* status,
+                                   int64_t max_degree, void* scratch, int64_t scratch_bytes, void* stream);
 
 /* Walk records.  edge_off == NULL: first-order shortcut (p == q == 1), every record
  * points at dst's node table, slot = slot_base + row_ptr[dst].  Otherwise
@@ -220,6 +244,21 @@ int n2v_walk_on_the_fly(const int64_t* row_ptr, const int32_t* col, const double
                         const int64_t* walk_uoff, uint64_t seed, n2v_alias_slot* scratch,
                         int64_t scratch_slots, int32_t* walks, int32_t* lens, int32_t* status,
                         void* stream);
+
+/* The same walk with popwalk == "pop" (src/node2vec.py:13-53,154-174): the first step draws from the pop node table of
+ * n2v_build_node_tables_pop (plain: its exemption flags, uint8[n_nodes]), every later step from get_alias_edge_pop. q is
+ * accepted and ignored, as in the reference; p must be non-zero.  No counting shortcut and no has_edge search apply: every
+ * step sums its K weights left to right, each after one gather of the neighbour's row bounds; the `smaller`-slot
+ * shortcut, the register path (K <= 64), the LDS window and the scratch rows are those of n2v_walk_on_the_fly.  A walk
+ * that meets a neighbour without out-edges (or a zero sum) stops: status gets N2V_STATUS_ZERO_POP and lens[lw] =
+ * -(number of nodes written), so the caller knows which walks failed.  NOT the walk of the precomputed popularity mode,
+ * which keeps the plain edge tables (:223-232).                                                                       */
+int n2v_walk_on_the_fly_pop(const int64_t* row_ptr, const int32_t* col, const double* w, double p, double q,
+                            int32_t symmetric, int64_t max_degree, const uint8_t* plain, const int32_t* starts,
+                            int64_t n_starts, int64_t pos_begin, int64_t pos_count, int64_t round_begin,
+                            int64_t round_count, int32_t walk_length, int32_t rng_mode, const double* uniforms,
+                            const int64_t* walk_uoff, uint64_t seed, n2v_alias_slot* scratch, int64_t scratch_slots,
+                            int32_t* walks, int32_t* lens, int32_t* status, void* stream);
 
 /* Tables under a memory budget — the middle path between n2v_walk_fat and n2v_walk_on_the_fly (the reference's own
  * answer to sum-of-deg^2 memory is to rebuild EVERY table per step, src/node2vec.py:34-53, src/settings.py:18).  The

@@ -49,6 +49,42 @@ node_tables_kernel(int64_t n_nodes, const int64_t* __restrict__ row_ptr, const d
     n2v::vose_pair<n2v::kWeight>(T, K, norm);  // prob = u / norm (:187), q = K * prob (:253), pairing
 }
 
+// The pop node tables of preprocess_transition_probs_popularity / get_alias_nodes_cur with popwalk == "pop"
+// (src/node2vec.py:13-25, :213-221): weight * 1.0 / len(G[nbr]) — or the plain weight when plain[v] is set (a node whose
+// label starts with 9999999, :18, :215; the test looks at v, not at the neighbour).  Nodes [v_begin, v_end); the table of v
+// lands at slots[row_ptr[v] - row_ptr[v_begin]], so the same kernel serves all nodes (v_begin = 0) and one table on demand.
+__global__ void __launch_bounds__(256)
+node_tables_pop_kernel(int64_t v_begin, int64_t v_end, const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                       const double* __restrict__ w, const uint8_t* __restrict__ plain, n2v_alias_slot* __restrict__ slots,
+                       int32_t* __restrict__ status) {
+    const int64_t v = v_begin + (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= v_end) return;
+    const int64_t b = row_ptr[v], K = row_ptr[v + 1] - b;
+    if (K == 0) return;
+    n2v_alias_slot* T = slots + (b - row_ptr[v_begin]);
+    const bool exempt = plain[v] != 0;
+    double norm = 0.0;
+    for (int64_t k = 0; k < K; ++k) {
+        double u = w ? w[b + k] : 1.0;
+        if (!exempt) {
+            const int32_t nb = col[b + k];
+            const int64_t pop = row_ptr[nb + 1] - row_ptr[nb];
+            if (pop == 0) {                      // ZeroDivisionError in the reference (:21, :218)
+                atomicOr(status, N2V_STATUS_ZERO_POP);
+                return;
+            }
+            u = u / (double)pop;                 // w * 1.0 is w
+        }
+        T[k].q = u;
+        norm = norm + u;                         // sum(), :22 / :219
+    }
+    if (norm == 0.0 || norm != norm) {
+        atomicOr(status, N2V_STATUS_ZERO_NORM);
+        return;
+    }
+    n2v::vose_pair<n2v::kWeight>(T, K, norm);
+}
+
 }  // namespace
 
 extern "C" int n2v_alias_setup_tables(int64_t n_tables, const int64_t* tab_off, n2v_alias_slot* slots, void* stream) {
@@ -70,6 +106,18 @@ extern "C" int n2v_build_node_tables(int64_t n_nodes, const int64_t* row_ptr, co
     hipLaunchKernelGGL(node_tables_kernel, dim3(n2v::grid_for(n_nodes, 256)), dim3(256), 0, (hipStream_t)stream,
                        n_nodes, row_ptr, w, slots, status);
     return n2v::check_launch("n2v_build_node_tables");
+}
+
+extern "C" int n2v_build_node_tables_pop(int64_t v_begin, int64_t v_end, const int64_t* row_ptr, const int32_t* col,
+                                         const double* w, const uint8_t* plain, n2v_alias_slot* slots, int32_t* status,
+                                         void* stream) {
+    if (v_begin < 0 || v_end < v_begin || !row_ptr || !status)
+        return n2v::fail(N2V_ERR_INVALID, "n2v_build_node_tables_pop: null pointer or bad node range");
+    if (v_end == v_begin) return N2V_OK;
+    if (!slots || !col || !plain) return n2v::fail(N2V_ERR_INVALID, "n2v_build_node_tables_pop: null pointer");
+    hipLaunchKernelGGL(node_tables_pop_kernel, dim3(n2v::grid_for(v_end - v_begin, 256)), dim3(256), 0, (hipStream_t)stream,
+                       v_begin, v_end, row_ptr, col, w, plain, slots, status);
+    return n2v::check_launch("n2v_build_node_tables_pop");
 }
 
 extern "C" int n2v_abi_version(void) { return N2V_ABI_VERSION; }

@@ -73,7 +73,9 @@ struct ThinEmit {
     }
 };
 
-template <bool FAT>
+// RULE: n2v::kRuleNone, get_alias_edge (:133-152) — or n2v::kRulePop, get_alias_edge_pop (:154-174): no has_edge search, so no
+// source row is staged.
+template <bool FAT, int RULE>
 __global__ void __launch_bounds__(256) edge_tables_wave_kernel(TabArgs a) {
     __shared__ n2v_alias_slot lds[4 * kLdsSlots];
     __shared__ double feed[4 * n2v::kFeed];
@@ -120,12 +122,12 @@ __global__ void __launch_bounds__(256) edge_tables_wave_kernel(TabArgs a) {
                              (uint32_t)__builtin_amdgcn_readlane((int)h_base, j);
         const int64_t t0 = ((int64_t)__builtin_amdgcn_readlane((int)(h_t0 >> 32), j) << 32) |
                            (uint32_t)__builtin_amdgcn_readlane((int)h_t0, j);
-        if (src != cached_src) {
+        if (RULE == n2v::kRuleNone && src != cached_src) {
             ws.row_n = n2v::wave_cache_row(a.g, my_row, src, lane);
             cached_src = src;
         }
         if (K <= kLdsSlots) {
-            if (!n2v::wave_build_table(a.g, Tl, ws, src, base, K, lane)) { zero = true; continue; }
+            if (!n2v::wave_build_table<RULE>(a.g, Tl, ws, src, base, K, lane)) { zero = true; continue; }
             if (FAT) emit_fat(a, Tl, t0, base, K, lane);
             else for (int k = lane; k < K; k += 64) { n2v_alias_slot s = Tl[k]; s.aux = 0; a.thin[t0 + k] = s; }
             __builtin_amdgcn_wave_barrier();   // the LDS slice is reused by the next table
@@ -137,17 +139,17 @@ __global__ void __launch_bounds__(256) edge_tables_wave_kernel(TabArgs a) {
             bool ok;
             if (FAT) {
                 n2v::QueueSink<FatEmit> sink{qi, qi + 128, reinterpret_cast<double*>(qi + 256), FatEmit{a.recs + base, a.fat + t0}, lane};
-                ok = n2v::wave_build_stream(a.g, S, ws, sink, src, base, K, lane);
+                ok = n2v::wave_build_stream<RULE>(a.g, S, ws, sink, src, base, K, lane);
             } else {
                 n2v::QueueSink<ThinEmit> sink{qi, qi + 128, reinterpret_cast<double*>(qi + 256), ThinEmit{a.thin + t0}, lane};
-                ok = n2v::wave_build_stream(a.g, S, ws, sink, src, base, K, lane);
+                ok = n2v::wave_build_stream<RULE>(a.g, S, ws, sink, src, base, K, lane);
             }
             if (!ok) { zero = true; continue; }
             __builtin_amdgcn_wave_barrier();   // the LDS slice is reused by the next table
         }
       }
     }
-    if (zero && lane == 0) atomicOr(a.status, N2V_STATUS_ZERO_NORM);
+    if (zero && lane == 0) atomicOr(a.status, RULE == n2v::kRulePop ? N2V_STATUS_ZERO_POP : N2V_STATUS_ZERO_NORM);
 }
 
 }  // namespace
@@ -165,12 +167,14 @@ extern "C" int64_t n2v_edge_tables_wave_scratch_bytes(int64_t max_degree) {
     return max_degree < 0 ? -1 : kMaxBlocks * 4 * scratch_k(max_degree) * 12;
 }
 
-extern "C" int n2v_build_edge_tables_wave(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col, const double* w,
-                                          const int32_t* src_of, double p, double q, int32_t symmetric,
-                                          const int64_t* edge_off, const int32_t* order, int64_t e_begin, int64_t e_end,
-                                          const n2v_edge_rec* recs, n2v_alias_slot* thin, n2v_fat_slot* fat,
-                                          int32_t* status, uint64_t* work_counter, int64_t max_degree, void* scratch,
-                                          int64_t scratch_bytes, void* stream) {
+namespace {
+template <int RULE>
+int launch_edge_tables(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col, const double* w,
+                       const int32_t* src_of, double p, double q, int32_t symmetric,
+                       const int64_t* edge_off, const int32_t* order, int64_t e_begin, int64_t e_end,
+                       const n2v_edge_rec* recs, n2v_alias_slot* thin, n2v_fat_slot* fat,
+                       int32_t* status, uint64_t* work_counter, int64_t max_degree, void* scratch,
+                       int64_t scratch_bytes, void* stream) {
     if (n_nodes < 0 || e_begin < 0 || e_end < e_begin || max_degree < 0)
         return n2v::fail(N2V_ERR_INVALID, "n2v_build_edge_tables_wave: bad range [%lld, %lld)", (long long)e_begin, (long long)e_end);
     if (e_end == e_begin) return N2V_OK;
@@ -188,9 +192,37 @@ extern "C" int n2v_build_edge_tables_wave(int64_t n_nodes, const int64_t* row_pt
     if (need > 0 && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 63) != 0))
         return n2v::fail(N2V_ERR_INVALID, "n2v_build_edge_tables_wave: max degree %lld needs %lld bytes of 64-byte aligned scratch "
                          "for %lld workgroups, got %lld", (long long)max_degree, (long long)need, (long long)blocks, (long long)scratch_bytes);
-    TabArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric}, src_of, edge_off, order, e_begin, e_end, recs, thin, fat, status,
+    TabArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric, nullptr}, src_of, edge_off, order, e_begin, e_end, recs, thin, fat, status,
               reinterpret_cast<unsigned long long*>(work_counter), reinterpret_cast<unsigned char*>(scratch), scratch_k(max_degree)};
-    if (fat) hipLaunchKernelGGL((edge_tables_wave_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL((edge_tables_wave_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if constexpr (RULE == n2v::kRuleNone) {
+        if (fat) {
+            hipLaunchKernelGGL((edge_tables_wave_kernel<true, RULE>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+            return n2v::check_launch("n2v_build_edge_tables_wave");
+        }
+    }
+    hipLaunchKernelGGL((edge_tables_wave_kernel<false, RULE>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return n2v::check_launch("n2v_build_edge_tables_wave");
+}
+}  // namespace
+
+extern "C" int n2v_build_edge_tables_wave(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col, const double* w,
+                                          const int32_t* src_of, double p, double q, int32_t symmetric,
+                                          const int64_t* edge_off, const int32_t* order, int64_t e_begin, int64_t e_end,
+                                          const n2v_edge_rec* recs, n2v_alias_slot* thin, n2v_fat_slot* fat,
+                                          int32_t* status, uint64_t* work_counter, int64_t max_degree, void* scratch,
+                                          int64_t scratch_bytes, void* stream) {
+    return launch_edge_tables<n2v::kRuleNone>(n_nodes, row_ptr, col, w, src_of, p, q, symmetric, edge_off, order, e_begin, e_end, recs,
+                                              thin, fat, status, work_counter, max_degree, scratch, scratch_bytes, stream);
+}
+
+// get_alias_edge_pop (src/node2vec.py:154-174): the same launch with the pop rule, thin output only (the reference never
+// stores pop-rule edge tables: its precomputed mode keeps the plain ones, :223-232)
+extern "C" int n2v_build_edge_tables_wave_pop(int64_t n_nodes, const int64_t* row_ptr, const int32_t* col, const double* w,
+                                              const int32_t* src_of, double p, const int64_t* edge_off, const int32_t* order,
+                                              int64_t e_begin, int64_t e_end, n2v_alias_slot* thin, int32_t* status,
+                                              int64_t max_degree, void* scratch, int64_t scratch_bytes, void* stream) {
+    if (!thin) return n2v::fail(N2V_ERR_INVALID, "n2v_build_edge_tables_wave_pop: null output");
+    if (p == 0.0) return n2v::fail(N2V_ERR_INVALID, "n2v_build_edge_tables_wave_pop: p must be non-zero");
+    return launch_edge_tables<n2v::kRulePop>(n_nodes, row_ptr, col, w, src_of, p, 1.0, 0, edge_off, order, e_begin, e_end, nullptr,
+                                             thin, nullptr, status, nullptr, max_degree, scratch, scratch_bytes, stream);
 }

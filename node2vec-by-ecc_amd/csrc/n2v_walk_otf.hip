@@ -70,14 +70,16 @@ struct OtfWave {
     // alias_draw (:277-281) on the table of the step prev -> cur (row at `base`, K neighbours) for the slot kk = int(u1*K)
     // and the second uniform u2: the picked slot, or -1 when the weights sum to 0 (:150).  All 64 lanes call it with
     // wave-uniform arguments.  keep_row: cur is the next call's prev (one walk per wave) — stage its row for that call.
-    template <bool WANT_NODE>
+    // RULE: the step-weight rule (n2v_wave_table.h).  kRulePop needs neither prev's row (no has_edge search) nor the
+    // dyadic counting shortcut (pop weights are not three classes); it returns -1 too when a neighbour has pop 0.
+    template <bool WANT_NODE, int RULE>
     __device__ __forceinline__ int pick(const OtfArgs& a, int32_t prev, int64_t base, int K, int kk, double u2, int lane,
                                         bool keep_row) {
         int32_t* P = rows2 + pb * kOtfRow;
         int32_t* C = rows2 + (pb ^ 1) * kOtfRow;
         // has_edge(nbr, prev) searches prev's row in LDS.  It was `cur` one step ago, so the row staged then is reused; it
         // is fetched only after a stored-table step, for another walk, or when it did not fit.
-        if (prev >= 0 && a.g.symmetric) {
+        if (RULE == n2v::kRuleNone && prev >= 0 && a.g.symmetric) {
             if (cached_node != prev) { cached_n = n2v::wave_cache_row(a.g, P, prev, lane, kOtfRow); cached_node = prev; }
             ws.row = P;
             ws.row_n = cached_n;
@@ -85,7 +87,7 @@ struct OtfWave {
             ws.row_n = -1;
         }
         const int32_t nb0 = lane < K ? a.g.col[base + lane] : -1;   // the row's first 64 entries, one per lane
-        const bool staged = keep_row && a.g.symmetric && K <= kOtfRow;
+        const bool staged = RULE == n2v::kRuleNone && keep_row && a.g.symmetric && K <= kOtfRow;
         if (staged) {
             if (lane < K) C[lane] = nb0;
             for (int i = 64 + lane; i < K; i += 64) C[i] = a.g.col[base + i];
@@ -93,11 +95,11 @@ struct OtfWave {
         }
         int pk = kk;
         if (K <= 64 && a.draw_first) {                                // the table in registers, one slot per lane
-            pk = n2v::wave_draw_le64(a.g, ws, prev, base, nb0, K, kk, u2, a.draw_first == 2 && a.exact_sum, a.wp, a.wq, lane);
+            pk = n2v::wave_draw_le64<RULE>(a.g, ws, prev, base, nb0, K, kk, u2, a.draw_first == 2 && a.exact_sum, a.wp, a.wq, lane);
             if (pk < 0) return -1;
         } else {
             bool drawn = false;
-            if (a.draw_first == 2) {         // dyadic weights: the pick from counts and a sweep over the three weight classes
+            if (RULE == n2v::kRuleNone && a.draw_first == 2) {         // dyadic weights: the pick from counts and a sweep over the three weight classes
                 const int d = n2v::dyadic_draw(a.g, ws, prev, base, K, kk, u2, a.wp, a.wq, a.exact_sum != 0,
                                                reinterpret_cast<int32_t*>(Tl), kLdsSlots * 4, reinterpret_cast<int32_t*>(ws.feed), lane);
                 if (d >= 0) { pk = d; drawn = true; }   // -2: more common neighbours than the sweep's list holds -> build
@@ -105,7 +107,7 @@ struct OtfWave {
             if (!drawn) {
                 n2v_alias_slot* T = K <= kLdsSlots ? Tl : Tg;
                 double norm;
-                if (!n2v::wave_weights_and_norm(a.g, T, ws, prev, base, K, lane, norm)) return -1;
+                if (!n2v::wave_weights_and_norm<RULE>(a.g, T, ws, prev, base, K, lane, norm)) return -1;
                 if (a.draw_first == 1) {     // slot kk `smaller` (its q is final, :253-255) and accepted (:278)?
                     const double q0 = (double)K * (T[kk].q / norm);
                     drawn = q0 < 1.0 && u2 < q0;
@@ -146,7 +148,10 @@ struct OtfWave {
 // ---- one wavefront per walk: every step without a stored table (all of them when HYBRID is false) ------------------
 // HYBRID: small launches of the budgeted walk (fewer walks than lanes on the chip) — one walk per wave keeps more rebuilds
 // in flight than the lane-per-walk kernel below, which serves its 64 lanes' rebuilds one after the other.
-template <bool HYBRID>
+// RULE kRulePop (n2v_walk_on_the_fly_pop): node2vec_walk_on_the_fly with popwalk == "pop" (:34-53) — the pop node table for
+// the first step, get_alias_edge_pop for every later one.  A walk that meets a neighbour of pop 0 (or a zero sum) stops
+// there with lens = -(nodes written): the caller tells which walks failed, not only that one did.
+template <bool HYBRID, int RULE>
 __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
     N2V_OTF_WAVE_STATE(W);
     const int32_t L = a.L;
@@ -160,6 +165,7 @@ __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
         if (a.rng_mode == N2V_RNG_UNIFORMS)
             up = a.uniforms + (a.walk_uoff ? a.walk_uoff[lw] : (int64_t)2 * (L - 1) * lw);
         if (lane == 0) out[0] = cur;
+        if (RULE == n2v::kRulePop) W.ws.plain_row = uni((int)a.g.plain[cur]);   // read by the first step only (src < 0)
         int32_t len = 1;
         bool failed = false;
         // hybrid: the stored table of the step about to be taken (first step: the node table), or N2V_NO_TABLE
@@ -191,7 +197,7 @@ __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
                 K = uni((int)(deg_hi & 0xFFFFFFu));
                 arr = a.fat;
             } else {
-                const int pick = W.pick<!HYBRID>(a, prev, base, K, kk, u2, lane, true);
+                const int pick = W.pick<!HYBRID, RULE>(a, prev, base, K, kk, u2, lane, true);
                 if (pick < 0) { failed = true; break; }
                 prev = cur;
                 W.set_cached(prev);
@@ -207,9 +213,9 @@ __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
             }
             if (lane == 0) out[len] = cur;
         }
-        if (failed && lane == 0) atomicOr(a.status, N2V_STATUS_ZERO_NORM);
+        if (failed && lane == 0) atomicOr(a.status, RULE == n2v::kRulePop ? N2V_STATUS_ZERO_POP : N2V_STATUS_ZERO_NORM);
         if (lane == 0) {
-            a.lens[lw] = len;
+            a.lens[lw] = (RULE == n2v::kRulePop && failed) ? -len : len;
             for (int32_t i = len; i < L; ++i) out[i] = -1;
         }
     }
@@ -267,7 +273,7 @@ __global__ void __launch_bounds__(256) walk_hybrid_lanes_kernel(OtfArgs a) {
                 const int s_K = __builtin_amdgcn_readlane((int)K, j), s_kk = __builtin_amdgcn_readlane((int)kk, j);
                 const double s_u2 = n2v::readlane_f64(u2, j);
                 const int64_t base = uni64(a.g.row_ptr[s_cur]);
-                const int pk = W.pick<false>(a, s_prev, base, s_K, s_kk, s_u2, lane, false);
+                const int pk = W.pick<false, n2v::kRuleNone>(a, s_prev, base, s_K, s_kk, s_u2, lane, false);
                 if (pk < 0) { if (lane == j) failed = true; continue; }
                 const uint4 r = *reinterpret_cast<const uint4*>(a.recs + base + pk);   // {slot_lo, base, dst, deg_hi}
                 if (lane == j) { slot_lo = r.x; deg_hi = r.w; dst = r.z; }
@@ -313,7 +319,7 @@ __global__ void __launch_bounds__(256) walk_hybrid_lanes_kernel(OtfArgs a) {
 }  // namespace
 
 namespace {
-int launch_otf(const char* who, bool hybrid, const int64_t* row_ptr, const int32_t* col, const double* w, double p, double q,
+int launch_otf(const char* who, bool hybrid, const uint8_t* plain, const int64_t* row_ptr, const int32_t* col, const double* w, double p, double q,
                int32_t symmetric, int64_t max_degree, const n2v_fat_slot* node_fat, const n2v_fat_slot* fat,
                const n2v_edge_rec* recs, const int32_t* starts, int64_t n_starts, int64_t pos_begin,
                int64_t pos_count, int64_t round_begin, int64_t round_count, int32_t walk_length,
@@ -331,6 +337,8 @@ int launch_otf(const char* who, bool hybrid, const int64_t* row_ptr, const int32
         return n2v::fail(N2V_ERR_INVALID, "%s: the stored tables and the walk records are needed", who);
     if (hybrid && ((((uintptr_t)node_fat | (uintptr_t)fat) & 31) != 0))
         return n2v::fail(N2V_ERR_INVALID, "%s: fat slots not 32-byte aligned", who);
+    const bool pop = plain != nullptr;     // the pop rule never reads q (src/node2vec.py:154-174)
+    if (pop) q = 1.0;
     if (!(p == p) || !(q == q) || p == 0.0 || q == 0.0)
         return n2v::fail(N2V_ERR_INVALID, "%s: p and q must be non-zero numbers", who);
     if (rng_mode != N2V_RNG_UNIFORMS && rng_mode != N2V_RNG_PHILOX)
@@ -351,9 +359,9 @@ int launch_otf(const char* who, bool hybrid, const int64_t* row_ptr, const int32
     // 2^-20 up to 2^10, degrees < 2^21
     const double wp = 1.0 / p, wq = 1.0 / q;
     auto dyadic = [](double x) { return x > 0.0 && x <= 1024.0 && x * 1048576.0 == (double)(int64_t)(x * 1048576.0); };
-    const int32_t draw_first = (!w && symmetric) ? 2 : 1;
+    const int32_t draw_first = (!w && symmetric && !pop) ? 2 : 1;
     const int32_t exact_sum = dyadic(wp) && dyadic(wq) && max_degree < (1 << 21);
-    OtfArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric}, starts, n_starts, pos_begin, pos_count, round_begin, n_local, walk_length,
+    OtfArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric, plain}, starts, n_starts, pos_begin, pos_count, round_begin, n_local, walk_length,
               rng_mode, uniforms, walk_uoff, seed, scratch, max_degree, node_fat, fat, recs, walks, lens, status, draw_first, exact_sum, wp, wq};
     hipStream_t st = (hipStream_t)stream;
     // budgeted walk: one lane per walk once the launch is large enough to fill half the lanes of the resident waves
@@ -373,9 +381,11 @@ int launch_otf(const char* who, bool hybrid, const int64_t* row_ptr, const int32
         else N2V_LAUNCH_LANES(N2V_RNG_PHILOX);
 #undef N2V_LAUNCH_LANES
     } else if (hybrid) {
-        hipLaunchKernelGGL(walk_otf_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((walk_otf_kernel<true, n2v::kRuleNone>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+    } else if (pop) {
+        hipLaunchKernelGGL((walk_otf_kernel<false, n2v::kRulePop>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     } else {
-        hipLaunchKernelGGL(walk_otf_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+        hipLaunchKernelGGL((walk_otf_kernel<false, n2v::kRuleNone>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     }
     return n2v::check_launch(who);
 }
@@ -390,7 +400,7 @@ extern "C" int n2v_walk_on_the_fly(const int64_t* row_ptr, const int32_t* col, c
                                    int32_t rng_mode, const double* uniforms, const int64_t* walk_uoff, uint64_t seed,
                                    n2v_alias_slot* scratch, int64_t scratch_slots, int32_t* walks, int32_t* lens,
                                    int32_t* status, void* stream) {
-    return launch_otf("n2v_walk_on_the_fly", false, row_ptr, col, w, p, q, symmetric, max_degree, nullptr, nullptr, nullptr, starts,
+    return launch_otf("n2v_walk_on_the_fly", false, nullptr, row_ptr, col, w, p, q, symmetric, max_degree, nullptr, nullptr, nullptr, starts,
                       n_starts, pos_begin, pos_count, round_begin, round_count, walk_length, rng_mode, uniforms, walk_uoff,
                       seed, scratch, scratch_slots, walks, lens, status, stream);
 }
@@ -402,7 +412,20 @@ extern "C" int n2v_walk_hybrid(const int64_t* row_ptr, const int32_t* col, const
                                int32_t rng_mode, const double* uniforms, const int64_t* walk_uoff, uint64_t seed,
                                n2v_alias_slot* scratch, int64_t scratch_slots, int32_t* walks, int32_t* lens,
                                int32_t* status, void* stream) {
-    return launch_otf("n2v_walk_hybrid", true, row_ptr, col, w, p, q, symmetric, max_degree, node_fat, fat, recs, starts,
+    return launch_otf("n2v_walk_hybrid", true, nullptr, row_ptr, col, w, p, q, symmetric, max_degree, node_fat, fat, recs, starts,
                       n_starts, pos_begin, pos_count, round_begin, round_count, walk_length, rng_mode, uniforms, walk_uoff,
                       seed, scratch, scratch_slots, walks, lens, status, stream);
+}
+
+// simulate_walks_on_the_fly / node2vec_walk_on_the_fly with popwalk == "pop" (src/node2vec.py:13-53, 154-174)
+extern "C" int n2v_walk_on_the_fly_pop(const int64_t* row_ptr, const int32_t* col, const double* w, double p, double q,
+                                       int32_t symmetric, int64_t max_degree, const uint8_t* plain, const int32_t* starts,
+                                       int64_t n_starts, int64_t pos_begin, int64_t pos_count, int64_t round_begin,
+                                       int64_t round_count, int32_t walk_length, int32_t rng_mode, const double* uniforms,
+                                       const int64_t* walk_uoff, uint64_t seed, n2v_alias_slot* scratch, int64_t scratch_slots,
+                                       int32_t* walks, int32_t* lens, int32_t* status, void* stream) {
+    if (!plain && pos_count * round_count != 0) return n2v::fail(N2V_ERR_INVALID, "n2v_walk_on_the_fly_pop: null exemption flags");
+    return launch_otf("n2v_walk_on_the_fly_pop", false, plain, row_ptr, col, w, p, q, symmetric, max_degree, nullptr, nullptr, nullptr,
+                      starts, n_starts, pos_begin, pos_count, round_begin, round_count, walk_length, rng_mode, uniforms,
+                      walk_uoff, seed, scratch, scratch_slots, walks, lens, status, stream);
 }

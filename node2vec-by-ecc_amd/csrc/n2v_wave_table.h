@@ -32,7 +32,21 @@ struct RowCtx {
     const double* w;      // NULL: all weights 1
     double p, q;
     int32_t symmetric;    // undirected graph: has_edge(nbr, src) == nbr in row(src), one shared row
+    const uint8_t* plain; // pop rule only: plain[v] != 0 exempts v's FIRST step from the popularity division (:18-19, :215-216)
 };
+
+// The step-weight rule, a compile-time parameter of step_weight_of and of everything that instantiates it.
+//   kRuleNone: get_alias_edge (:133-152) — w/p back to src, w to a common neighbour, w/q elsewhere.
+//   kRulePop:  get_alias_edge_pop (:154-174) — w/(p*pop(nbr)) back to src, w/pop(nbr) elsewhere; q is never read and
+//              there is no has_edge search.  pop(x) = len(G[x]) = row_ptr[x+1] - row_ptr[x], one 16-B gather per
+//              neighbour.  The first step (src < 0) is the pop node table (:13-21): w*1.0/pop(nbr), or the plain w for
+//              an exempt node.  pop == 0 (ZeroDivisionError in the reference) yields NaN: the left-to-right sum is then
+//              NaN and every builder stops before it normalises — no inf or NaN reaches the pairing.
+enum : int { kRuleNone = 0, kRulePop = 1 };
+template <int RULE>
+__device__ __forceinline__ bool norm_fails(double norm) {
+    return RULE == kRulePop ? (norm == 0.0 || norm != norm) : norm == 0.0;
+}
 
 // Per-wave LDS work area.
 //   feed: 64 doubles.  The left-to-right sum consumes its operands from here by broadcast reads (every lane reads the
@@ -48,6 +62,7 @@ struct WaveScratch {
     double* feed;          // LDS [kFeed]
     const int32_t* row;    // LDS [row_n] or nullptr
     int row_n;
+    int plain_row = 0;     // pop rule, first step: the row's node is exempt (RowCtx::plain)
 };
 
 // fills ws_row[0..S) with row(src) when it fits; returns the row_n to pass on (all lanes call it)
@@ -72,15 +87,24 @@ __device__ __forceinline__ bool lds_row_contains(const int32_t* row, int n, int3
 }
 
 // unnormalised transition weight of neighbour k of the row at `base` for a step arriving from `src` (:142-148)
+template <int RULE>
 __device__ __forceinline__ double step_weight_of(const RowCtx& a, const WaveScratch& ws, int32_t src, int32_t nb, double wt) {
+    if (RULE == kRulePop) {
+        if (src < 0 && ws.plain_row) return wt;
+        const int64_t pop = a.row_ptr[nb + 1] - a.row_ptr[nb];
+        if (pop == 0) return __longlong_as_double(0x7FF8000000000000LL);
+        if (src >= 0 && nb == src) return wt / (a.p * (double)pop);
+        return wt / (double)pop;
+    }
     if (src < 0) return wt;
     if (nb == src) return wt / a.p;
     const bool adj = ws.row_n >= 0 ? lds_row_contains(ws.row, ws.row_n, nb)
                      : a.symmetric ? row_contains(a.row_ptr, a.col, src, nb) : row_contains(a.row_ptr, a.col, nb, src);
     return adj ? wt : wt / a.q;
 }
+template <int RULE>
 __device__ __forceinline__ double step_weight(const RowCtx& a, const WaveScratch& ws, int32_t src, int64_t base, int k) {
-    return step_weight_of(a, ws, src, a.col[base + k], a.w ? a.w[base + k] : 1.0);
+    return step_weight_of<RULE>(a, ws, src, a.col[base + k], a.w ? a.w[base + k] : 1.0);
 }
 
 // norm = norm + v[0] + v[1] + ... strictly left to right (:149): the wave's 64 values are parked in LDS and added in
@@ -234,18 +258,18 @@ struct AosSink {                           // q of a stream entry is already in 
 // (src < 0: the first step, i.e. the node table of src/node2vec.py:184-188) in T[0..K): afterwards T[k].q / T[k].J
 // are q[k] / J[k] of alias_setup.  All 64 lanes of the wave call it together.  Returns false when the weights sum
 // to 0 (the reference raises ZeroDivisionError, :150 / :187).
-template <typename Slot>
+template <int RULE, typename Slot>
 __device__ __forceinline__ bool wave_build_table(const RowCtx& a, Slot* T, const WaveScratch ws, int32_t src, int64_t base,
                                                  int K, int lane) {
     // ---- 1. unnormalised weights in parallel (:142-148)
-    for (int k = lane; k < K; k += 64) T[k].q = step_weight(a, ws, src, base, k);
+    for (int k = lane; k < K; k += 64) T[k].q = step_weight<RULE>(a, ws, src, base, k);
     wave_sync();
     // ---- 2. norm = sum(unnormalized_probs), strictly left to right (:149)
     double norm = 0.0;
     for (int c = 0; c < K; c += 64)
         norm = wave_sum_in_order(ws, norm, (c + lane < K) ? T[c + lane].q : 0.0, min(64, K - c), lane);
     norm = unid(norm);
-    if (norm == 0.0) return false;
+    if (norm_fails<RULE>(norm)) return false;
     // ---- 3. q = K * (u / norm) (:150 then :253, two roundings) and the two index stacks in index order
     //         (:252-257): `smaller` grows up from position 0, `larger` down from position K-1
     const double Kd = (double)K;
@@ -283,16 +307,16 @@ __device__ __forceinline__ bool wave_build_table(const RowCtx& a, Slot* T, const
 // alias_draw returns kk without looking at J or at any other slot: the step needs the K weights, their left-to-right
 // sum and ONE division — not the classification, the stacks or the pairing (54-60 % of a table's cycles).
 // wave_weights_and_norm = phases 1-2 of wave_build_table; wave_finish_table = phases 3-4.
-template <typename Slot>
+template <int RULE, typename Slot>
 __device__ __forceinline__ bool wave_weights_and_norm(const RowCtx& a, Slot* T, const WaveScratch ws, int32_t src, int64_t base,
                                                       int K, int lane, double& norm_out) {
-    for (int k = lane; k < K; k += 64) T[k].q = step_weight(a, ws, src, base, k);
+    for (int k = lane; k < K; k += 64) T[k].q = step_weight<RULE>(a, ws, src, base, k);
     wave_sync();
     double norm = 0.0;
     for (int c = 0; c < K; c += 64)
         norm = wave_sum_in_order(ws, norm, (c + lane < K) ? T[c + lane].q : 0.0, min(64, K - c), lane);
     norm_out = unid(norm);
-    return norm_out != 0.0;
+    return !norm_fails<RULE>(norm_out);
 }
 template <typename Slot>
 __device__ __forceinline__ void wave_finish_table(Slot* T, int K, double norm, int lane) {
@@ -567,11 +591,12 @@ __device__ __forceinline__ int dyadic_draw(const RowCtx& a, const WaveScratch& w
 //   nb: the lane's neighbour col[base + lane] (lanes < K), already loaded by the caller.
 //   wp, wq: 1/p, 1/q (used when exact_sum: the weight classes are lane masks and the sum is a count, as in dyadic_draw).
 // Slot kk is tested BEFORE the other lanes normalise (one fp64 division instead of 64 lanes' worth of them).
+template <int RULE>
 __device__ __forceinline__ int wave_draw_le64(const RowCtx& a, const WaveScratch& ws, int32_t src, int64_t base, int32_t nb, int K,
                                               int kk, double u2, bool exact_sum, double wp, double wq, int lane) {
     const bool valid = lane < K;
     double w, norm, w_kk;
-    if (exact_sum) {
+    if (RULE == kRuleNone && exact_sum) {
         const bool isp = valid && src >= 0 && nb == src;
         const bool adj = valid && src >= 0 && !isp &&
                          (ws.row_n >= 0 ? lds_row_contains(ws.row, ws.row_n, nb) : row_contains(a.row_ptr, a.col, src, nb));
@@ -584,9 +609,9 @@ __device__ __forceinline__ int wave_draw_le64(const RowCtx& a, const WaveScratch
             w = isp ? wp : (adj ? 1.0 : wq);
         }
     } else {
-        w = valid ? step_weight_of(a, ws, src, nb, a.w ? a.w[base + lane] : 1.0) : 0.0;
+        w = valid ? step_weight_of<RULE>(a, ws, src, nb, a.w ? a.w[base + lane] : 1.0) : 0.0;
         norm = unid(wave_sum_in_order(ws, 0.0, w, K, lane));
-        if (norm == 0.0) return -1;
+        if (norm_fails<RULE>(norm)) return -1;
         w_kk = readlane_f64(w, kk);
     }
     double q_kk = (double)K * (w_kk / norm);                     // :150 then :253
@@ -677,15 +702,15 @@ struct QueueSink {
     }
 };
 
-template <typename Emit>
+template <int RULE, typename Emit>
 __device__ __forceinline__ bool wave_build_stream(const RowCtx& a, const StreamStacks S, const WaveScratch ws,
                                                   QueueSink<Emit>& sink, int32_t src, int64_t base, int K, int lane) {
     // ---- 1 + 2. weights (:142-148) straight into the left-to-right sum (:149); nothing is stored
     double norm = 0.0;
     for (int c = 0; c < K; c += 64)
-        norm = wave_sum_in_order(ws, norm, (c + lane < K) ? step_weight(a, ws, src, base, c + lane) : 0.0, min(64, K - c), lane);
+        norm = wave_sum_in_order(ws, norm, (c + lane < K) ? step_weight<RULE>(a, ws, src, base, c + lane) : 0.0, min(64, K - c), lane);
     norm = unid(norm);
-    if (norm == 0.0) return false;
+    if (norm_fails<RULE>(norm)) return false;
     // ---- 3. the same weights again, q = K * (u / norm) (:150, :253), {k, q} onto the stack q selects (:252-257)
     const double Kd = (double)K;
     int ns = 0, nl = 0;
@@ -693,7 +718,7 @@ __device__ __forceinline__ bool wave_build_stream(const RowCtx& a, const StreamS
         const int k = c + lane;
         const bool valid = k < K;
         double qk = 0.0;
-        if (valid) qk = Kd * (step_weight(a, ws, src, base, k) / norm);
+        if (valid) qk = Kd * (step_weight<RULE>(a, ws, src, base, k) / norm);
         const bool is_small = valid && (qk < 1.0);
         const unsigned long long ms = __ballot(is_small), ml = __ballot(valid && !is_small);
         const unsigned long long below = (1ULL << lane) - 1ULL;

@@ -46,6 +46,9 @@ def parse_args(argv=None):
         ap.set_defaults(**{on: False})
     ap.add_argument("--rng", default="numpy", choices=["numpy", "philox"],
                     help="numpy: consume numpy's global MT19937 stream like the reference; philox: in-kernel RNG")
+    ap.add_argument("--popwalk", default="none", choices=["none", "pop", "both"],
+                    help="popularity-biased walks (src/main_link_multi.py:87): pop = first step by weight / degree of the "
+                         "neighbour; both = half the rounds plain, then half popularity-biased")
     ap.add_argument("--seed", type=int, default=1, help="seed of the philox walk RNG and of the SGNS trainer")
     ap.add_argument("--merge", default="tsum", choices=["tsum", "hot"],
                     help="more than one GPU: how the ranks' replicas are merged (n2v_hip/merge.py: tiered pure sums, or "
@@ -121,10 +124,17 @@ def main(args_):
     nx_G = read_graph()
     G = node2vec.Graph(nx_G, args.directed, args.p, args.q, rng=getattr(args, "rng", "numpy"),
                        seed=getattr(args, "seed", 1), device=None if ctx is None else ctx.device)
-    G.preprocess_transition_probs()
+    popwalk = getattr(args, "popwalk", "none")
     if ctx is None:
-        walks = G.simulate_walks(args.num_walks, args.walk_length)
+        from n2v_hip import linkpred as _linkpred
+        walks = _linkpred.simulate_walk_popularity(G, popwalk, args.num_walks, args.walk_length)
         return learn_embeddings(walks)
+    if popwalk == "both":
+        raise ValueError("--popwalk both runs on one GPU (two table sets, one after the other)")
+    if popwalk == "pop":
+        G.preprocess_transition_probs_popularity()
+    else:
+        G.preprocess_transition_probs()
     # launched by torch.distributed.run: walks shard by start vertex, every rank ends with the same merged
     # embedding (BASELINE config C4)
     assert G._engine.device == ctx.device, (G._engine.device, ctx.device)

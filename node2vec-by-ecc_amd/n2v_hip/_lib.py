@@ -15,6 +15,7 @@ SO_PATH = os.environ.get("N2V_HIP_LIB") or os.path.join(_HERE, "libn2v_hip.so") 
 
 N2V_OK = 0
 N2V_STATUS_ZERO_NORM = 1
+N2V_STATUS_ZERO_POP = 2
 RNG_UNIFORMS = 0
 RNG_PHILOX = 1
 RNG_UNIFORMS_TILED = 2
@@ -29,6 +30,11 @@ SIGNATURES = {
     "n2v_last_error": (C.c_char_p, []),
     "n2v_alias_setup_tables": (C.c_int, [_i64, _ptr, _ptr, _ptr]),
     "n2v_build_node_tables": (C.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_build_node_tables_pop": (C.c_int, [_i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_build_edge_tables_wave_pop": (C.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _f64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _i64,
+                                                 _ptr, _i64, _ptr]),
+    "n2v_walk_on_the_fly_pop": (C.c_int, [_ptr, _ptr, _ptr, _f64, _f64, _i32, _i64, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64,
+                                          _i32, _i32, _ptr, _ptr, _u64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
     "n2v_build_edge_tables_wave": (C.c_int, [_i64, _ptr, _ptr, _ptr, _ptr, _f64, _f64, _i32, _ptr, _ptr, _i64, _i64,
                                              _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr]),
     "n2v_edge_tables_wave_scratch_bytes": (C.c_int64, [_i64]),

@@ -186,6 +186,18 @@ def read_edgelist(path, weighted=False, directed=False):
     return from_edges(src, dst, w if weighted else None, directed)
 
 
+def popwalk_exempt_flags(labels):
+    """uint8[N]: 1 where ``str(label).startswith('9999999')`` — the item labels of src/utils.py:392, which keep the plain
+    weights in the popularity-biased node tables (src/node2vec.py:18, :215).  Integer arithmetic: a non-negative label
+    starts with those seven digits exactly when dropping some number of trailing digits leaves 9999999 (an int64 has at
+    most 19 digits, so at most 12 are dropped); a negative label starts with '-'."""
+    lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+    flags = np.zeros(len(lab), dtype=bool)
+    for k in range(13):
+        flags |= (lab // np.int64(10 ** k)) == 9999999      # floor division keeps negative labels negative
+    return flags.astype(np.uint8)
+
+
 def degree_cut_for_budget(csr, budget_bytes, bytes_per_slot=32):
     """Tables under a memory budget (WalkEngine.preprocess(budget_bytes=...)): the largest degree D such that the
     edge tables of all entries (src -> dst) with deg(dst) <= D fit in `budget_bytes`, and the number of slots they

@@ -57,13 +57,26 @@ class WalkEngine:
         self.node_fat = self.edge_fat = None
         self.first_order = False
         self.partial = False          # tables under a memory budget: only entries with deg(dst) <= stored_degree_cut
+        self.pop_tables = False       # the stored node tables are the popularity-biased ones (preprocess(pop=True))
+        self._plain = None
+
+    @property
+    def plain(self):
+        """uint8[N] on the device: the nodes the popularity rule exempts (csr.popwalk_exempt_flags), computed once."""
+        if self._plain is None:
+            from .csr import popwalk_exempt_flags
+            self._plain = torch.from_numpy(popwalk_exempt_flags(self.csr.labels)).to(self.device)
+        return self._plain
 
     # ------------------------------------------------------------------ tables
     def _stream(self):
         return _lib.stream_ptr(self.device)
 
-    def preprocess(self, first_order_shortcut=True, fat="auto", budget_bytes=None):
-        """preprocess_transition_probs (src/node2vec.py:176-204) on device.
+    def preprocess(self, first_order_shortcut=True, fat="auto", budget_bytes=None, pop=False):
+        """preprocess_transition_probs (src/node2vec.py:176-204) on device — with pop=True
+        preprocess_transition_probs_popularity (:206-237): the NODE tables (the first step of a walk) are the
+        popularity-biased ones, the edge tables and walk records are the plain ones, as in the reference; with
+        p == q == 1, where the records point at node tables, those stay the plain node tables (kept beside the pop ones).
 
         With p == q == 1 every (src,dst) table is bit-identical to dst's node table
         (w/1 == w), so the Σdeg² edge tables are not materialised unless
@@ -82,6 +95,8 @@ class WalkEngine:
         self.timings = {}
         tick = self._phase_timer()
         self.node_slots = self.edge_slots = self.recs = self.node_fat = self.edge_fat = None
+        self.pop_tables = bool(pop)
+        plain_node_slots = None       # pop and first order: the tables the records point at
         with torch.cuda.device(d):
             self.first_order = bool(first_order_shortcut and self.p == 1.0 and self.q == 1.0)
             total = nnz if self.first_order else self.total_edge_slots
@@ -124,9 +139,15 @@ class WalkEngine:
             tick("alloc")
             status = torch.zeros(1, dtype=torch.int32, device=d)
             self.node_slots = torch.zeros((max(nnz, 1), 2), dtype=torch.int64, device=d)
-            _lib.check(self.lib.n2v_build_node_tables(
-                N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(self.node_slots),
-                _lib.ptr(status), self._stream()))
+            if pop and nnz > 0:
+                _lib.check(self.lib.n2v_build_node_tables_pop(
+                    0, N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(self.plain),
+                    _lib.ptr(self.node_slots), _lib.ptr(status), self._stream()))
+            if not pop or self.first_order:
+                plain_node_slots = torch.zeros_like(self.node_slots) if pop else self.node_slots
+                _lib.check(self.lib.n2v_build_node_tables(
+                    N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(plain_node_slots),
+                    _lib.ptr(status), self._stream()))
             tick("node_tables")
             rec_off = None
             if self.first_order:
@@ -151,7 +172,7 @@ class WalkEngine:
                 self.max_degree, total, _lib.ptr(self.recs), self._stream()))
             tick("offsets_recs")
             if self.first_order:
-                self.edge_slots = self.node_slots
+                self.edge_slots = plain_node_slots
             else:
                 # nothing is sorted here: the wave kernel takes its tables from a shared counter instead of a
                 # size-ordered list
@@ -186,9 +207,14 @@ class WalkEngine:
                     _lib.ptr(self.recs), _lib.ptr(self.node_fat), self._stream()))
                 if self.first_order:
                     self.edge_fat = self.node_fat
+                    if pop:
+                        self.edge_fat = torch.empty_like(self.node_fat)
+                        _lib.check(self.lib.n2v_build_fat_slots(
+                            N, _lib.ptr(self.row_ptr), None, _lib.ptr(self.row_ptr), _lib.ptr(plain_node_slots),
+                            _lib.ptr(self.recs), _lib.ptr(self.edge_fat), self._stream()))
             st = int(status.item())
             tick("node_fat")
-        if st & _lib.N2V_STATUS_ZERO_NORM:
+        if st & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP):
             self.node_slots = self.edge_slots = self.recs = self.node_fat = self.edge_fat = None
             raise ZeroDivisionError("float division by zero")
 
@@ -236,7 +262,9 @@ class WalkEngine:
 
     def edge_table(self, e):
         if self.first_order:
-            return self.node_table(int(self.csr.col[e]))
+            dense = int(self.csr.col[e])      # edge_slots ARE the plain node tables (also after preprocess(pop=True))
+            s = self.edge_slots[int(self.csr.row_ptr[dense]):int(self.csr.row_ptr[dense + 1])]
+            return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
         if self.partial and not bool(self.stored_mask[e].item()):
             return self.build_one_edge_table(e)         # not stored under the memory budget: built on demand
         off = self.edge_off[e:e + 2].cpu().tolist()
@@ -276,24 +304,31 @@ class WalkEngine:
         e2 = torch.searchsorted(keys, node * n + alias_dst)
         return e2 - self.row_ptr[node], q
 
-    def build_one_node_table(self, dense):
-        """get_alias_nodes_cur (src/node2vec.py:13-21, popwalk "none"): the table of one node, built on demand."""
+    def build_one_node_table(self, dense, pop=False):
+        """get_alias_nodes_cur (src/node2vec.py:13-25): the table of one node, built on demand — pop: with the
+        popularity rule (the whole graph's row_ptr is passed: the neighbours' degrees are read)."""
         b, e = int(self.csr.row_ptr[dense]), int(self.csr.row_ptr[dense + 1])
         d = self.device
         with torch.cuda.device(d):
             slots = torch.zeros((max(e - b, 1), 2), dtype=torch.int64, device=d)
             status = torch.zeros(1, dtype=torch.int32, device=d)
-            rp = torch.tensor([0, e - b], dtype=torch.int64, device=d)
-            w = None if self.w is None else self.w[b:e].contiguous()
-            _lib.check(self.lib.n2v_build_node_tables(1, _lib.ptr(rp), self.col[b:].data_ptr() if e > b else None,
-                                                      _lib.ptr(w), _lib.ptr(slots), _lib.ptr(status), self._stream()))
-            if int(status.item()) & _lib.N2V_STATUS_ZERO_NORM:
+            if pop:
+                if e > b:
+                    _lib.check(self.lib.n2v_build_node_tables_pop(
+                        dense, dense + 1, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w),
+                        _lib.ptr(self.plain), _lib.ptr(slots), _lib.ptr(status), self._stream()))
+            else:
+                rp = torch.tensor([0, e - b], dtype=torch.int64, device=d)
+                w = None if self.w is None else self.w[b:e].contiguous()
+                _lib.check(self.lib.n2v_build_node_tables(1, _lib.ptr(rp), self.col[b:].data_ptr() if e > b else None,
+                                                          _lib.ptr(w), _lib.ptr(slots), _lib.ptr(status), self._stream()))
+            if int(status.item()) & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP):
                 raise ZeroDivisionError("float division by zero")
         s = slots[: e - b]
         return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
 
-    def build_one_edge_table(self, e):
-        """get_alias_edge (src/node2vec.py:133-152) for one CSR entry e = (src -> dst), built on demand by the
+    def build_one_edge_table(self, e, pop=False):
+        """get_alias_edge (src/node2vec.py:133-152; pop: get_alias_edge_pop, :154-174) for one CSR entry e = (src -> dst), built on demand by the
         same kernel that fills the stored tables (one-table launch: the kernel reads order[0], src_of[e] and
         edge_off[e] only, so one-element arrays are passed with their base shifted by -e; a table of more than 512
         slots needs the scratch of one workgroup, 48 B per slot rounded up to 16 slots)."""
@@ -309,11 +344,17 @@ class WalkEngine:
             order = torch.tensor([e], dtype=torch.int64, device=d).to(torch.int32)
             sbytes = 0 if K <= 512 else 48 * ((K + 15) // 16 * 16)
             scratch = torch.empty(max(sbytes, 64) // 8, dtype=torch.int64, device=d)
-            _lib.check(self.lib.n2v_build_edge_tables_wave(
-                self.csr.n_nodes, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), src_of.data_ptr() - 4 * e,
-                self.p, self.q, 0 if self.csr.directed else 1, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1, None,
-                _lib.ptr(slots), None, _lib.ptr(status), None, K, _lib.ptr(scratch), sbytes, self._stream()))
-            if int(status.item()) & _lib.N2V_STATUS_ZERO_NORM:
+            if pop:
+                _lib.check(self.lib.n2v_build_edge_tables_wave_pop(
+                    self.csr.n_nodes, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), src_of.data_ptr() - 4 * e,
+                    self.p, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1, _lib.ptr(slots), _lib.ptr(status), K,
+                    _lib.ptr(scratch), sbytes, self._stream()))
+            else:
+                _lib.check(self.lib.n2v_build_edge_tables_wave(
+                    self.csr.n_nodes, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), src_of.data_ptr() - 4 * e,
+                    self.p, self.q, 0 if self.csr.directed else 1, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1, None,
+                    _lib.ptr(slots), None, _lib.ptr(status), None, K, _lib.ptr(scratch), sbytes, self._stream()))
+            if int(status.item()) & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP):
                 raise ZeroDivisionError("float division by zero")
         s = slots[:K]
         return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
@@ -373,15 +414,21 @@ class WalkEngine:
         return walks, lens
 
     def walk_on_the_fly(self, starts, num_rounds, walk_length, rng="philox", seed=0, uniforms=None, walk_uoff=None,
-                         pos_begin=0, pos_count=None, round_begin=0, out=None, uoff_round_stride=0, hybrid=False):
+                         pos_begin=0, pos_count=None, round_begin=0, out=None, uoff_round_stride=0, hybrid=False,
+                         pop=False, defer_failures=False):
         """Launch the on-the-fly walk kernel (no stored edge tables; src/node2vec.py:97-111).
         Same arguments and results as WalkEngine.walk.  hybrid: n2v_walk_hybrid — steps through entries whose table is
-        stored (preprocess(budget_bytes=...)) read it, the others rebuild theirs."""
+        stored (preprocess(budget_bytes=...)) read it, the others rebuild theirs.
+        pop: n2v_walk_on_the_fly_pop, the walk of popwalk == "pop" (:13-53, :154-174; q is not read).  A walk that meets a
+        neighbour without out-edges raises ZeroDivisionError, as the reference does when it gets there — unless
+        defer_failures: then such walks come back with a NEGATIVE length (-nodes written) and the caller decides (the
+        numpy-stream resolution walks some walks from guessed stream offsets first: only a failure at the true offset
+        counts)."""
         d = self.device
         L = int(walk_length)
         if L < 1:
             raise ValueError("walk_length must be >= 1")
-        if self.p == 0 or self.q == 0:
+        if self.p == 0 or (self.q == 0 and not pop):
             raise ZeroDivisionError("float division by zero")
         n_starts = int(starts.numel())
         if pos_count is None:
@@ -415,9 +462,12 @@ class WalkEngine:
             if hybrid:
                 _lib.check(self.lib.n2v_walk_hybrid(*head, _lib.ptr(self.node_fat), _lib.ptr(self.edge_fat),
                                                     _lib.ptr(self.recs), *tail))
+            elif pop:
+                _lib.check(self.lib.n2v_walk_on_the_fly_pop(*head, _lib.ptr(self.plain), *tail))
             else:
                 _lib.check(self.lib.n2v_walk_on_the_fly(*head, *tail))
-            if int(status.item()) & _lib.N2V_STATUS_ZERO_NORM:
+            st = int(status.item())
+            if st & _lib.N2V_STATUS_ZERO_NORM or (st & _lib.N2V_STATUS_ZERO_POP and not defer_failures):
                 raise ZeroDivisionError("float division by zero")
         return walks, lens
 

@@ -157,6 +157,34 @@ def run(edges, p=1.0, q=1.0, num_walks=5, walk_length=40, dimensions=128, window
     return out
 
 
+def simulate_walk_popularity(G, popwalk, num_walks, walk_length, on_the_fly=False):
+    """src/main_link.py:206-219 (precomputed tables) and :309-331 (on_the_fly) for one `node2vec.Graph`: the walks of
+    --popwalk none | pop | both as ONE WalkCorpus.  "both" runs int(num_walks / 2) rounds of the plain walk, then as many of
+    the popularity walk, and concatenates them in that order; in the numpy mode the global stream runs on from the first
+    half into the second.  The two orders are different walks: precomputed "pop" is
+    preprocess_transition_probs_popularity() + simulate_walks(), on the fly it is simulate_walks_on_the_fly() with
+    G.popwalk == "pop" (reassigned between the calls as :318-321 do, and left at the last value used)."""
+    import node2vec
+    if popwalk not in ("none", "pop", "both"):
+        raise ValueError("popwalk must be 'none', 'pop' or 'both', not %r" % (popwalk,))
+    flavours = ["none", "pop"] if popwalk == "both" else [popwalk]
+    rounds = int(num_walks / 2) if popwalk == "both" else num_walks
+    parts = []
+    for flavour in flavours:
+        if on_the_fly:
+            G.popwalk = flavour
+            parts.append(G.simulate_walks_on_the_fly(rounds, walk_length))
+        else:
+            if flavour == "pop":
+                G.preprocess_transition_probs_popularity()
+            else:
+                G.preprocess_transition_probs()
+            parts.append(G.simulate_walks(rounds, walk_length))
+    if len(parts) == 1:
+        return parts[0]
+    return node2vec.WalkCorpus(torch.cat([c.walks for c in parts]), torch.cat([c.lens for c in parts]), parts[0].labels)
+
+
 def _with_isolated_nodes(train, full):
     """Re-express the training CSR over the full graph's node set (same labels / start order),
     so nodes that lost all their edges stay in the graph with degree 0."""

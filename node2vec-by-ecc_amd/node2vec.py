@@ -1,8 +1,9 @@
 """Drop-in for the reference's ``src/node2vec.py`` on MI355X.
 
 Same surface — ``Graph(nx_G, is_directed, p, q, popwalk="none")``,
-``.preprocess_transition_probs()``, ``.simulate_walks(num_walks, walk_length, nodes=None,
-verbose=False)``, ``.simulate_walks_on_the_fly(...)``, ``.node2vec_walk(walk_length,
+``.preprocess_transition_probs()``, ``.preprocess_transition_probs_popularity()``,
+``.simulate_walks(num_walks, walk_length, nodes=None, verbose=False)``,
+``.simulate_walks_on_the_fly(...)`` (honours ``popwalk``), ``.get_alias_edge_pop(src, dst)``, ``.node2vec_walk(walk_length,
 start_node)``, module-level ``alias_setup`` / ``alias_draw`` — with the tables and the
 walks computed by the HIP kernels in ``csrc/`` through the C-ABI of ``include/n2v_hip.h``.
 
@@ -14,10 +15,9 @@ afterwards is where the reference would have left it) and the kernel consumes th
 (walk, step) index.  ``rng="philox"`` is the throughput mode: uniforms are generated in
 the kernel (Philox4x32-10 keyed by ``seed`` and the walk's global index), nothing is read
 from numpy; the walk rule is identical.
-
-Only ``popwalk="none"`` is implemented (the "pop" variants of the reference are an
-experiment knob outside the hot path).
 """
+import functools
+
 import numpy as np
 import torch
 
@@ -218,16 +218,32 @@ class Graph():
                 self._csr_cache = _csr.from_networkx(self.G)
         return self._csr_cache
 
-    def _check_popwalk(self):
-        if self.popwalk != "none":
-            raise NotImplementedError("popwalk=%r: only the 'none' walk is on the MI355X hot path" % (self.popwalk,))
+    def _pop(self):
+        """``self.popwalk`` as the on-the-fly entry points read it, at call time (src/main_link.py:318-321 reassigns it
+        between calls): True for "pop", False for "none".  Any other value is an UnboundLocalError in the reference
+        (src/node2vec.py:15-25, 28-32 bind nothing); here it is a ValueError."""
+        if self.popwalk == "none":
+            return False
+        if self.popwalk == "pop":
+            return True
+        raise ValueError("popwalk=%r: Graph knows 'none' and 'pop' ('both' is a mode of the drivers: "
+                         "n2v_hip.linkpred.simulate_walk_popularity)" % (self.popwalk,))
 
-    # src/node2vec.py:176-204
+    # src/node2vec.py:176-204.  Like the reference, neither preprocess looks at self.popwalk.
     def preprocess_transition_probs(self, budget_bytes=None):
         """budget_bytes (extension; also the attribute `table_budget_bytes`): keep the edge tables under that many
         bytes — tables that do not fit are rebuilt per step by the walk, as the reference's on-the-fly variant does
         for ALL of them (src/node2vec.py:34-53); the walks are the same."""
-        self._check_popwalk()
+        return self._preprocess(budget_bytes, pop=False)
+
+    # src/node2vec.py:206-237
+    def preprocess_transition_probs_popularity(self, budget_bytes=None):
+        """Popularity-biased NODE tables (weight / len(G[nbr]), plain weights for nodes labelled 9999999...), the plain
+        edge tables of preprocess_transition_probs: only the first step of a walk differs.  `alias_nodes` shows the
+        popularity tables, `alias_edges` is unchanged; budget_bytes as above."""
+        return self._preprocess(budget_bytes, pop=True)
+
+    def _preprocess(self, budget_bytes, pop):
         if self.p == 0 or self.q == 0:
             raise ZeroDivisionError("float division by zero")
         # the engine (graph on the device) is reused when p, q and the graph are unchanged, and its tables are released
@@ -240,7 +256,7 @@ class Graph():
             eng = WalkEngine(self._csr, self.p, self.q, device=self.device)
         if budget_bytes is None:
             budget_bytes = getattr(self, "table_budget_bytes", None)
-        eng.preprocess(budget_bytes=budget_bytes)
+        eng.preprocess(budget_bytes=budget_bytes, pop=pop)    # every table is rebuilt, in the flavour asked for
         self._engine = eng
         self.alias_nodes = _AliasNodes(self)
         self.alias_edges = _AliasEdges(self)
@@ -249,31 +265,38 @@ class Graph():
     def get_alias_edge(self, src, dst):
         """src/node2vec.py:133-152: the (J, q) alias table of the step that arrives at `dst` from `src`, built by
         the table kernel for this one pair (no stored tables needed)."""
-        self._check_popwalk()
+        return self._one_edge_table(src, dst, pop=False)
+
+    def get_alias_edge_pop(self, src, dst):
+        """src/node2vec.py:154-174: the same with the popularity rule — weight / (p * len(G[nbr])) back to `src`,
+        weight / len(G[nbr]) elsewhere; q is not read."""
+        return self._one_edge_table(src, dst, pop=True)
+
+    def _one_edge_table(self, src, dst, pop):
         try:
             du, dv = (int(x) for x in self._csr.dense_of([src, dst]))
         except (KeyError, TypeError, ValueError):
             raise KeyError((src, dst))
-        if self.p == 0 or self.q == 0:
+        if self.p == 0 or (self.q == 0 and not pop):
             raise ZeroDivisionError("float division by zero")
         eng = self._graph_engine()
         e = eng.edge_index(du, dv)
         if e < 0:
             raise KeyError((src, dst))
-        return eng.build_one_edge_table(e)
+        return eng.build_one_edge_table(e, pop=pop)
 
     def get_alias_edges_cur(self, src, dst):
-        """src/node2vec.py:27-32 (popwalk "none")."""
-        return self.get_alias_edge(src, dst)
+        """src/node2vec.py:27-32."""
+        return self._one_edge_table(src, dst, pop=self._pop())
 
     def get_alias_nodes_cur(self, cur):
-        """src/node2vec.py:13-21 (popwalk "none"): the node table of `cur`, built on demand."""
-        self._check_popwalk()
+        """src/node2vec.py:13-25: the node table of `cur`, built on demand (popwalk "pop": the popularity-biased one)."""
+        pop = self._pop()
         try:
             dc = int(self._csr.dense_of([cur])[0])
         except (KeyError, TypeError, ValueError):
             raise KeyError(cur)
-        return self._graph_engine().build_one_node_table(dc)
+        return self._graph_engine().build_one_node_table(dc, pop=pop)
 
     def _starts(self, nodes):
         c = self._csr
@@ -298,8 +321,10 @@ class Graph():
     # Needs no preprocess_transition_probs(): the (prev, cur) table is rebuilt at every step
     # by the on-the-fly kernel (no sum-of-deg^2 storage).  If the tables already exist they
     # are used instead (same walks, faster) unless `self.force_on_the_fly` is set.
+    # popwalk == "pop" is NOT the walk of preprocess_transition_probs_popularity (that one keeps the plain edge
+    # tables): every step after the first draws from get_alias_edge_pop, so stored tables are never used.
     def simulate_walks_on_the_fly(self, num_walks, walk_length, nodes=None, verbose=False):
-        self._check_popwalk()
+        self._pop()
         if verbose:
             for walk_iter in range(num_walks):
                 print(str(walk_iter + 1), '/', str(num_walks))
@@ -316,7 +341,11 @@ class Graph():
     def _otf_engine(self):
         """True if the on-the-fly kernel has to (or is asked to) run; makes sure an engine
         (graph on the device, no tables) exists."""
-        if self._engine is not None and self._engine.ready and not getattr(self, "force_on_the_fly", False):
+        if self._pop():               # never the stored tables: they hold the plain edge rule
+            self._graph_engine()
+            return True
+        if (self._engine is not None and self._engine.ready and not self._engine.pop_tables
+                and not getattr(self, "force_on_the_fly", False)):
             return False
         if self._engine is None:
             self._engine = WalkEngine(self._csr, self.p, self.q, device=self.device)
@@ -330,7 +359,6 @@ class Graph():
         return WalkCorpus(walks, lens, self._csr.labels)[0]
 
     def node2vec_walk_on_the_fly(self, walk_length, start_node):
-        self._check_popwalk()
         otf = self._otf_engine()
         walks, lens = self._simulate(1, walk_length, self._csr.dense_of([start_node]), otf=otf)
         return WalkCorpus(walks, lens, self._csr.labels)[0]
@@ -339,6 +367,9 @@ class Graph():
     def _simulate(self, num_walks, walk_length, starts_host, otf=False):
         eng = self._engine
         self._walk = eng.walk_on_the_fly if otf else eng.walk
+        self._walk_pop = bool(otf and self._pop())
+        if self._walk_pop:
+            self._walk = functools.partial(eng.walk_on_the_fly, pop=True)
         d = eng.device
         L = max(int(walk_length), 1)  # walk = [start] even for walk_length <= 1 (:63-65)
         num_walks = int(num_walks)
@@ -452,14 +483,19 @@ class Graph():
                 have_end = max(u_base + U.numel(), exact_off)
                 U = torch.cat([keep, self._global_uniforms(max(need_end - have_end, 1 << 24), d)])
                 u_base = exact_off
+            kw = {"defer_failures": True} if getattr(self, "_walk_pop", False) else {}
             w_win, l_win = self._walk(starts_all[done:hi].contiguous(), 1, L, rng="uniforms", uniforms=U,
-                                      walk_uoff=(off - u_base).contiguous())
+                                      walk_uoff=(off - u_base).contiguous(), **kw)
+            failed = l_win < 0            # pop walk: met a neighbour without out-edges (only final walks count, below)
+            l_win = l_win.abs()
             used = (l_win.to(torch.int64) - 1) * 2
             new_off = torch.cumsum(used, 0) - used + exact_off
             bad = new_off != off
             m = hi - done
             first = int(torch.nonzero(bad)[0].item()) if bool(bad.any().item()) else m
             # walks [0, first) were walked from their true offsets: final
+            if bool(failed[:first].any().item()):
+                raise ZeroDivisionError("float division by zero")
             walks[done:done + first] = w_win[:first]
             lens[done:done + first] = l_win[:first]
             exact_off = int((new_off[first - 1] + used[first - 1]).item())
