@@ -171,6 +171,35 @@ int n2v_bine_train_pass(const int32_t* edge_u, const int32_t* edge_v, const doub
  * stop = |loss - last_loss| < epsilon; last_loss = loss; loss = 0; work counter = 0.         */
 int n2v_bine_lambda_step(double* state, double epsilon, void* stream);
 
+/* ---- top_N (src/bine_train.py:311-359) and its metrics (:361-406) -------------------------------------
+ * n2v_bine_rec_topn: for every user position i < n_users the k = min(n_items, top_n) best item positions j < n_items by
+ *   score(i, j) = sum over c < dim of emb[u_idx[i]][c] * emb[v_idx[j]][c], formed in fp64 on the matrix cores tile by
+ *   tile; nothing of size n_users x n_items is stored.  emb: fp64 [n_rows][stride]; only columns [0, dim) are read (dim
+ *   need not be a multiple of anything, the padding may hold anything).  u_idx / v_idx: int32 row indices into emb; -1
+ *   (any value outside [0, n_rows)) marks a vertex the model does not know, and a pair with such an end scores exactly
+ *   0.0 (`pre = 0`, :316-322).
+ *   Order: that of `sorted(recommend_dict[u].items(), key = score, reverse=True)[:top_n]` on Python 3 — descending
+ *   score, equal scores in ascending position (the caller's item list order; Python's sort is stable also when
+ *   reversed).  -0.0 ties +0.0; NaN ranks below everything.  ranked: int32 [n_users][k] item positions, score: fp64
+ *   [n_users][k].
+ *   The item list is cut into `segments` ranges of whole 64-item tiles (0 = n2v_bine_rec_segments(n_users, n_items);
+ *   at most 64), each swept by its own workgroups, so that few users still fill the chip; the result does not depend
+ *   on it.  Work space: part_score fp64 / part_pos int32, [n_users][segments][k] each.
+ *   top_n in [1, N2V_REC_MAX_TOPN]; n_users == 0 or n_items == 0 is N2V_ERR_INVALID (nothing is launched).
+ * n2v_bine_rec_metrics: out fp64 [n_users][5] = precision, recall, AP, RR, nDCG of ranked[u][0..k) against the user's
+ *   ground truth.  truth_ptr int64[n_users+1] / truth_pos int32[]: the positions (in the item list) of the user's test
+ *   items, ascending per user; truth_len int32[n_users] = len(test_rate[u]) (>= 1), which also counts test items that are
+ *   not in the item list.  discount fp64[k] = 1 / math.log(i + 2, 2) and idcg fp64[n_users] = IDCG(truth_len[u]) come
+ *   from the host, so the kernel only adds in index order and divides: its numbers equal Python's bit for bit.        */
+#define N2V_REC_MAX_TOPN 256
+int32_t n2v_bine_rec_segments(int64_t n_users, int64_t n_items);
+int n2v_bine_rec_topn(const double* emb, int64_t n_rows, int32_t dim, int32_t stride, const int32_t* u_idx,
+                      int64_t n_users, const int32_t* v_idx, int64_t n_items, int32_t top_n, int32_t segments,
+                      double* part_score, int32_t* part_pos, int32_t* ranked, double* score, void* stream);
+int n2v_bine_rec_metrics(const int32_t* ranked, int64_t n_users, int32_t k, const int64_t* truth_ptr,
+                         const int32_t* truth_pos, const int32_t* truth_len, const double* discount,
+                         const double* idcg, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

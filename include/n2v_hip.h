@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define N2V_ABI_VERSION 4
+#define N2V_ABI_VERSION 5
 
 #define N2V_OK 0
 #define N2V_ERR_INVALID (-1)   /* bad argument (null pointer, negative size, limit exceeded) */

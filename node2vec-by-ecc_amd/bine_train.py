@@ -70,7 +70,7 @@ def train(args, gul, mode="parallel"):
         save_to_file(node_list_u, node_list_v, model_path, args)
     if args.rec and getattr(args, "test_rates", None) is not None:
         test_user, test_item, test_rate = args.test_rates
-        train.last["metrics"] = top_N(test_user, test_item, test_rate, node_list_u, node_list_v, args.top_n)
+        train.last["metrics"] = eng.recommend(test_user, test_item, test_rate, args.top_n)      # from the device tables
     return node_list_u, 0, 0
 
 
@@ -136,9 +136,12 @@ def read_data(filename):
 
 def top_N(test_u, test_v, test_rate, node_list_u, node_list_v, top_n):
     """src/bine_train.py:311-359: score every (test user, test item) by U.V (0 for unknown vertices), recommend the
-    top_n items per user, average F1 / MAP / MRR / NDCG against the user's test items.  The score matrix is one
-    library GEMM on the device; ranking ties follow torch.topk instead of Python's sort."""
+    top_n items per user, average F1 / MAP / MRR / NDCG against the user's test items.  With a GPU the tables are stacked
+    once and n2v_hip/recommend.py scores, selects and measures on the device without forming the score matrix.  Ranking
+    rule: descending score, equal scores in the order of test_v (Python 3's stable sort; -0.0 ties +0.0, NaN lowest)."""
     test_u, test_v = list(test_u), list(test_v)
+    if torch.cuda.is_available():
+        return _top_N_device(test_u, test_v, test_rate, node_list_u, node_list_v, top_n)
     d = next(iter(node_list_u.values()))["embedding_vectors"].shape[1] if len(node_list_u) else 1
     dev = "cuda" if torch.cuda.is_available() else "cpu"
 
@@ -166,6 +169,24 @@ def top_N(test_u, test_v, test_rate, node_list_u, node_list_v, top_n):
     recall = sum(recall_list) / len(recall_list)
     f1 = 2 * precison * recall / (precison + recall) if precison + recall > 0 else 0.0
     return f1, sum(ap_list) / len(ap_list), sum(rr_list) / len(rr_list), sum(ndcg_list) / len(ndcg_list)
+
+
+def _top_N_device(test_u, test_v, test_rate, node_list_u, node_list_v, top_n):
+    from n2v_hip import recommend as rec
+    test_v = rec.unique_in_order(test_v)
+    ptr, pos, lens = rec.truth_csr(test_u, test_v, test_rate)
+    rows, index = [], []
+    for labels, table in ((test_u, node_list_u), (test_v, node_list_v)):
+        idx = np.full(len(labels), -1, dtype=np.int32)
+        for i, x in enumerate(labels):
+            if x in table:
+                idx[i] = len(rows)
+                rows.append(table[x]["embedding_vectors"][0])
+        index.append(idx)
+    if not rows:
+        rows.append(np.zeros(1))
+    emb = torch.from_numpy(np.ascontiguousarray(np.stack(rows), dtype=np.float64)).cuda()
+    return rec.evaluate(emb, emb.shape[1], index[0], index[1], ptr, pos, lens, top_n)[:4]
 
 
 def nDCG(ranked_list, ground_truth):

@@ -87,6 +87,9 @@ SIGNATURES = {
                                       _ptr, _ptr, _ptr, _i32, _i32, _i32, _f64, _f64, _f64, _ptr, _i32, _u64, _u64,
                                       _i32, _i32, _ptr]),
     "n2v_bine_lambda_step": (C.c_int, [_ptr, _f64, _ptr]),
+    "n2v_bine_rec_segments": (C.c_int32, [_i64, _i64]),
+    "n2v_bine_rec_topn": (C.c_int, [_ptr, _i64, _i32, _i32, _ptr, _i64, _ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_bine_rec_metrics": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # include/n2v_sim.h
     "n2v_sim_prepare": (C.c_int, [_ptr, _i32, _i32, _ptr, _i64, _i32, _ptr, _i32, _ptr]),
     "n2v_sim_block": (C.c_int, [_ptr, _i64, _i64, _ptr, _i64, _i32, _i32, _i64, _ptr, _i64, _ptr]),

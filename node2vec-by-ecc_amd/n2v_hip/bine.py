@@ -542,6 +542,23 @@ class BineEngine:
         lo, hi = (0, self.g.n_u) if side == "u" else (self.g.n_u, self.g.n)
         return t[lo:hi, : self.dim].cpu().numpy()
 
+    def recommend(self, test_u, test_v, test_rate, top_n):
+        """top_N (src/bine_train.py:311-359) straight from the device tables: (f1, map, mrr, ndcg).  test_u / test_v are
+        taken in the order given; a label the graph does not hold is an unknown vertex (score 0 against everything); a
+        label repeated in test_v counts once, at its first place (the keys of the reference's recommend_dict[u]).  Ranking
+        rule: n2v_hip/recommend.py.  `self.last_recommend` keeps the per-user [n][5] array."""
+        from . import recommend as rec
+        if self.emb is None:
+            raise RuntimeError("recommend: no embeddings (init_embeddings / train first)")
+        test_u, test_v = list(test_u), rec.unique_in_order(list(test_v))
+        ptr, pos, lens = rec.truth_csr(test_u, test_v, test_rate)
+        u_idx = rec.label_index(self.g.user_labels, test_u)
+        v_idx = rec.label_index(self.g.item_labels, test_v)
+        v_idx = np.where(v_idx >= 0, v_idx + self.g.n_u, -1).astype(np.int32)
+        f1, mean_ap, mrr, ndcg, per_user = rec.evaluate(self.emb, self.dim, u_idx, v_idx, ptr, pos, lens, top_n)
+        self.last_recommend = per_user
+        return f1, mean_ap, mrr, ndcg
+
 
 class ReplicaMerge:
     """Sum of the replicas' changes since the last merge, applied to every replica; the pass's loss (and the
