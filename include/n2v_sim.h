@@ -74,6 +74,47 @@ int n2v_sim_rows_fill(const float* scores, int64_t n_rows, int64_t n_cols, int64
 int n2v_sim_rows_topk(const float* scores, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t k,
                       int32_t* cols, float* vals, void* stream);
 
+/* ---- EccenKNN: eccentricity-weighted k-NN rating prediction (csrc/n2v_eccknn.hip) --------------------------------
+ * Replaces src/main_rec.py:73-151 (cosine_eccen / msd_eccen, a triple Python loop over five dense n_x x n_x arrays)
+ * and :305-329 (estimate).  x is the side similarities are formed over, y the other one; ids are inner ids (first
+ * appearance in the training data).  Everything is fp64 and equals the reference's arithmetic bit for bit: every pair
+ * (xi, xj) walks the y both rated in ascending order, and every += is one rounded multiply chain and one rounded add.
+ * A NaN's sign and payload are not part of that contract (IEEE 754 leaves them to the implementation).             */
+#define N2V_ECCKNN_COSINE 0   /* prods += (ri*rj)*w[y]; sqi += ri*ri; sqj += rj*rj;  sim = prods / sqrt(sqi*sqj)     */
+#define N2V_ECCKNN_MSD 1      /* sq_diff += ((ri-rj)*w[y])^2;                        sim = 1 / (sq_diff/freq + 1)    */
+#define N2V_ECCKNN_MAX_K 256  /* largest neighbourhood n2v_eccknn_estimate keeps                                     */
+int32_t n2v_eccknn_max_k(void);
+int64_t n2v_eccknn_max_dense(void); /* largest n_x * n_y (elements) the dense form accepts: 2^31; beyond it an error */
+
+/* Ratings (x[i], y[i], r[i]), i < n, no duplicate (x, y) -> the y-major dense form the similarity kernel reads:
+ * dense: fp64[n_y][n_x], mask: uint8[n_y][n_x] (1 = rated; 0.0 is a legal rating).  Both are cleared first.        */
+int n2v_eccknn_densify(const int32_t* x, const int32_t* y, const double* r, int64_t n, int64_t n_x, int64_t n_y,
+                       double* dense, uint8_t* mask, void* stream);
+
+/* sim: fp64[n_x][n_x], symmetric, diagonal 1; 0 where freq < min_support; w: fp64[n_y].  freq (int32), prods, sqi,
+ * sqj (cosine) and sq_diff (msd) are the reference's accumulators [n_x][n_x], the diagonal included; each may be
+ * NULL.  One workgroup per 64x64 tile of the upper triangle, the mirror written from the same tile.               */
+int n2v_eccknn_sim(const double* dense, const uint8_t* mask, int64_t n_x, int64_t n_y, const double* w, int32_t method,
+                   int32_t min_support, double* sim, int32_t* freq, double* prods, double* sqi, double* sqj,
+                   double* sq_diff, void* stream);
+
+/* One wavefront per query (qx[q], qy[q]); -1 = unknown.  yr_ptr: int64[n_y + 1], yr_x: int32, yr_r: fp64 — the raters
+ * of every y in training order.  Candidates are (sim[x, x2], r) in list order; the k largest by sim are kept, equal
+ * sims in list order (heapq.nlargest with a key = a stable descending sort), -0.0 ties +0.0.  DEVIATION: a NaN sim
+ * ranks below everything — Python's result with NaN keys depends on the order of its comparisons.  The selection is
+ * walked in rank order: sim > 0 adds sim to sum_sim and sim*r to sum_ratings.  actual_k < min_k, or an unknown x or
+ * y: impossible[q] = 1 and est[q] = 0; otherwise est[q] = sum_ratings / sum_sim (before any fallback or clipping).
+ * 1 <= k <= N2V_ECCKNN_MAX_K, min_k >= 1, n_q >= 1.                                                                 */
+int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                        int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
+                        double* est, int32_t* actual_k, uint8_t* impossible, void* stream);
+
+/* surprise's AlgoBase.predict, restated from its documented behaviour: pred = global_mean where impossible, then
+ * min(hi, .) and max(lo, .) (a NaN becomes hi).  r_true (may be NULL): *rmse = sqrt(sum((r_true - pred)^2) / n_q),
+ * the sum taken in query order by one workgroup.                                                                   */
+int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,
+                       double lo, double hi, double* pred, double* rmse, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,360 @@
+// EccenKNN: eccentricity-weighted k-NN rating prediction — gfx950 (MI355X).  C-ABI: include/n2v_sim.h.
+//
+// Reference: src/main_rec.py:73-151 (cosine_eccen / msd_eccen: `for y: for xi: for xj` over five dense n_x x n_x
+// arrays) and :305-329 (estimate: heapq.nlargest over the raters of y, then a weighted mean in rank order).
+//   densify_kernel   one lane per rating: the y-major dense rating matrix and its presence mask (0 is a legal rating);
+//   sim_kernel       one workgroup per 64x64 tile of the upper triangle, 4x4 pairs per thread with their accumulators in
+//                    registers; the two 64-column panels of the dense matrix and the mask pass through LDS in chunks of
+//                    YC values of y.  Every pair walks y ascending and performs the reference's separately rounded
+//                    multiplies and adds (the library is built with -ffp-contract=off), so the accumulators and sim are
+//                    the reference's bits.  A y that one side did not rate leaves the accumulators untouched (a select,
+//                    not a multiply by zero: ratings may be anything).  No float atomics (their order is undefined) and
+//                    no v_mfma_f64 (its four products are not added one after the other).  The mirror is written from
+//                    the same tile: prods and sq_diff are symmetric bit for bit, sqi and sqj swap.
+//   estimate_kernel  one wavefront per query: gathers sim[x, x2] over the raters of y, keeps the best k of them in a
+//                    sorted LDS list under the one order of n2v_rec.hip (higher sim first, equal sims by list position,
+//                    -0.0 ties +0.0, NaN below everything) and sums in rank order.
+//   predict_kernel   one workgroup: global-mean fallback, clip to the rating scale, and the squared errors added one
+//                    after the other in query order (rmse).
+#include "n2v_common.h"
+#include "n2v_sim.h"
+
+namespace {
+
+constexpr int TB = 64;            // rows / columns of a tile
+constexpr int YC = 32;            // values of y staged per barrier
+constexpr int POS_NONE = 0x7fffffff;
+constexpr int64_t MAX_DENSE = (int64_t)1 << 31;   // elements of the dense matrix (16 GiB of fp64)
+
+// ---- densify ----------------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) densify_kernel(const int32_t* __restrict__ x, const int32_t* __restrict__ y,
+                                                      const double* __restrict__ r, int64_t n, int64_t n_x, int64_t n_y,
+                                                      double* __restrict__ dense, uint8_t* __restrict__ mask) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t xi = x[i], yi = y[i];
+    if (xi < 0 || xi >= n_x || yi < 0 || yi >= n_y) return;      // the host wrapper's contract; never out of bounds
+    dense[yi * n_x + xi] = r[i];
+    mask[yi * n_x + xi] = 1;
+}
+
+// ---- similarity -------------------------------------------------------------------------------------------------------
+
+struct SimArgs {
+    const double* dense; const uint8_t* mask; int64_t n_x; int64_t n_y; const double* w; int min_support;
+    double* sim; int32_t* freq; double* prods; double* sqi; double* sqj; double* sq_diff;
+};
+
+template <int METHOD>
+__global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
+    const int ti = blockIdx.y, tj = blockIdx.x;
+    if (tj < ti) return;                                          // upper triangle of tiles; the mirror comes from it
+    __shared__ __attribute__((aligned(16))) double ra[YC][TB];    // ratings of the tile's rows    [y][row]
+    __shared__ __attribute__((aligned(16))) double rb[YC][TB];    // ratings of the tile's columns [y][col]
+    __shared__ __attribute__((aligned(4))) uint8_t ma[YC][TB];
+    __shared__ __attribute__((aligned(4))) uint8_t mb[YC][TB];
+    __shared__ double wl[YC];
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int64_t i0 = (int64_t)ti * TB, j0 = (int64_t)tj * TB;
+
+    int32_t fr[4][4];
+    double p0[4][4], p1[4][4], p2[4][4];                          // cosine: prods, sqi, sqj; msd: sq_diff, -, -
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) { fr[u][v] = 0; p0[u][v] = 0.0; p1[u][v] = 0.0; p2[u][v] = 0.0; }
+
+    for (int64_t y0 = 0; y0 < a.n_y; y0 += YC) {
+        __syncthreads();                                          // the previous chunk has been consumed
+        for (int e = t; e < YC * TB; e += 256) {
+            const int yy = e >> 6, c = e & 63;
+            const int64_t y = y0 + yy;
+            double va = 0.0, vb = 0.0;
+            uint8_t qa = 0, qb = 0;
+            if (y < a.n_y) {
+                if (i0 + c < a.n_x) { va = a.dense[y * a.n_x + i0 + c]; qa = a.mask[y * a.n_x + i0 + c]; }
+                if (j0 + c < a.n_x) { vb = a.dense[y * a.n_x + j0 + c]; qb = a.mask[y * a.n_x + j0 + c]; }
+            }
+            ra[yy][c] = va; rb[yy][c] = vb; ma[yy][c] = qa; mb[yy][c] = qb;
+        }
+        if (t < YC) wl[t] = (y0 + t < a.n_y) ? a.w[y0 + t] : 0.0;
+        __syncthreads();
+#pragma unroll 2
+        for (int yy = 0; yy < YC; ++yy) {                         // y ascending: the order of every accumulator
+            const uint32_t mi = *reinterpret_cast<const uint32_t*>(&ma[yy][4 * ty]);
+            const uint32_t mj = *reinterpret_cast<const uint32_t*>(&mb[yy][4 * tx]);
+            if (mi == 0 || mj == 0) continue;                     // none of this thread's 16 pairs is co-rated at y
+            const double wy = wl[yy];
+            double ri[4], rj[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { ri[u] = ra[yy][4 * ty + u]; rj[u] = rb[yy][4 * tx + u]; }
+            if (METHOD == N2V_ECCKNN_COSINE) {
+                double si[4], sj[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { si[u] = ri[u] * ri[u]; sj[u] = rj[u] * rj[u]; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
+                        const double pr = (ri[u] * rj[v]) * wy;   // `ri * rj * i_dict[y]`: left to right
+                        fr[u][v] += co ? 1 : 0;
+                        p0[u][v] = co ? p0[u][v] + pr : p0[u][v];
+                        p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
+                        p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
+                    }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
+                        const double d = (ri[u] - rj[v]) * wy;
+                        fr[u][v] += co ? 1 : 0;
+                        p0[u][v] = co ? p0[u][v] + d * d : p0[u][v];
+                    }
+            }
+        }
+    }
+
+    const bool diag_tile = ti == tj;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = i0 + 4 * ty + u;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int64_t j = j0 + 4 * tx + v;
+            if (i >= a.n_x || j >= a.n_x) continue;
+            double s;
+            if (i == j) s = 1.0;
+            else if (fr[u][v] < a.min_support) s = 0.0;
+            else if (METHOD == N2V_ECCKNN_COSINE) s = p0[u][v] / sqrt(p1[u][v] * p2[u][v]);
+            else s = 1.0 / (p0[u][v] / (double)fr[u][v] + 1.0);
+            const int64_t o = i * a.n_x + j, m = j * a.n_x + i;
+            a.sim[o] = s;
+            if (a.freq) a.freq[o] = fr[u][v];
+            if (METHOD == N2V_ECCKNN_COSINE) {
+                if (a.prods) a.prods[o] = p0[u][v];
+                if (a.sqi) a.sqi[o] = p1[u][v];
+                if (a.sqj) a.sqj[o] = p2[u][v];
+            } else if (a.sq_diff) a.sq_diff[o] = p0[u][v];
+            if (diag_tile) continue;                              // a diagonal tile computed its own lower half
+            a.sim[m] = s;
+            if (a.freq) a.freq[m] = fr[u][v];
+            if (METHOD == N2V_ECCKNN_COSINE) {
+                if (a.prods) a.prods[m] = p0[u][v];
+                if (a.sqi) a.sqi[m] = p2[u][v];
+                if (a.sqj) a.sqj[m] = p1[u][v];
+            } else if (a.sq_diff) a.sq_diff[m] = p0[u][v];
+        }
+    }
+}
+
+// ---- estimate ---------------------------------------------------------------------------------------------------------
+
+// order-preserving key: larger double <=> larger key; NaN lowest; -0.0 and +0.0 share a key (order_key of n2v_rec.hip)
+__device__ __forceinline__ uint64_t order_key(double v) {
+    if (v != v) return 0ull;
+    if (v == 0.0) return 0x8000000000000000ull;
+    const uint64_t u = (uint64_t)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+// (ka, pa) comes before (kb, pb) in the ranking
+__device__ __forceinline__ bool beats(uint64_t ka, int pa, uint64_t kb, int pb) {
+    return ka > kb || (ka == kb && pa < pb);
+}
+
+// Insert (cs, cp) into the sorted list ls/lp of k entries (the last one falls out), all 64 lanes together: entry i takes
+// the candidate or entry i - 1 when it does not come before the candidate.  Chunks of 64 entries from the top down, so an
+// entry is read before the chunk below it is written.  tk/tp receive the new last entry.  (list_insert of n2v_rec.hip.)
+__device__ __forceinline__ void list_insert(double* ls, int32_t* lp, int k, double cs, int cp, uint64_t ck, int lane,
+                                            uint64_t& tk, int& tp) {
+    const int top = ((k - 1) >> 6) << 6;
+    for (int base = top; base >= 0; base -= 64) {
+        const int i = base + lane;
+        double si = __builtin_nan(""), sm = si;
+        int pi = POS_NONE, pm = POS_NONE;
+        if (i < k) {
+            si = ls[i]; pi = lp[i];
+            if (i > 0) { sm = ls[i - 1]; pm = lp[i - 1]; }
+        }
+        const bool keep = beats(order_key(si), pi, ck, cp);
+        const bool prev_before = i == 0 || beats(order_key(sm), pm, ck, cp);
+        const double ns = keep ? si : (prev_before ? cs : sm);
+        const int np = keep ? pi : (prev_before ? cp : pm);
+        if (i < k && !keep) { ls[i] = ns; lp[i] = np; }
+        if (base == top) {
+            const int last = (k - 1) & 63;
+            tk = order_key(__shfl(ns, last, 64));
+            tp = __shfl(np, last, 64);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // the stores are seen by this wavefront's next loads
+}
+
+struct EstArgs {
+    const double* sim; int64_t n_x; const int64_t* yr_ptr; const int32_t* yr_x; const double* yr_r; int64_t n_y;
+    const int32_t* qx; const int32_t* qy; int64_t n_q; int k; int min_k;
+    double* est; int32_t* actual_k; uint8_t* impossible;
+};
+
+__global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
+    __shared__ double ls[N2V_ECCKNN_MAX_K];
+    __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
+    const int64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t x = a.qx[q], y = a.qy[q];
+    if (x < 0 || x >= a.n_x || y < 0 || y >= a.n_y) {            // 'User and/or item is unkown.'
+        if (lane == 0) { a.est[q] = 0.0; a.actual_k[q] = 0; a.impossible[q] = 1; }
+        return;
+    }
+    const int k = a.k;
+    // the list starts as k entries (NaN, POS_NONE): below any real entry, so it is always "full"
+    for (int i = lane; i < k; i += 64) { ls[i] = __builtin_nan(""); lp[i] = POS_NONE; }
+    __syncthreads();
+    const int64_t beg = a.yr_ptr[y];
+    const int64_t len64 = a.yr_ptr[y + 1] - beg;
+    const int L = (int)(len64 < POS_NONE ? len64 : POS_NONE - 1);
+    const double* srow = a.sim + x * a.n_x;
+    uint64_t tk = 0ull;
+    int tp = POS_NONE;
+    for (int base = 0; base < L; base += 64) {
+        const int p = base + lane;
+        double s = __builtin_nan("");
+        if (p < L) {
+            const int64_t x2 = a.yr_x[beg + p];
+            if (x2 >= 0 && x2 < a.n_x) s = srow[x2];
+        }
+        unsigned long long cand = __ballot(p < L && beats(order_key(s), p, tk, tp));
+        while (cand) {                                            // in list order; wave-uniform
+            const int src = __ffsll((long long)cand) - 1;
+            cand &= cand - 1;
+            const double cs = __shfl(s, src, 64);
+            const int cp = base + src;
+            const uint64_t ck = order_key(cs);
+            if (beats(ck, cp, tk, tp)) list_insert(ls, lp, k, cs, cp, ck, lane, tk, tp);
+        }
+    }
+    // rank order: `for (sim, r) in k_neighbors: if sim > 0: ...`; every lane runs the same sums
+    double sum_sim = 0.0, sum_ratings = 0.0;
+    int actual_k = 0;
+    const int n_sel = L < k ? L : k;
+    for (int base = 0; base < n_sel; base += 64) {
+        const int i = base + lane;
+        double s = 0.0, sr = 0.0;
+        if (i < n_sel) {
+            const int p = lp[i];
+            if (p < L) {                                          // always: a filler is below every real entry
+                s = ls[i];
+                sr = s * a.yr_r[beg + p];                         // sim * r, rounded before it is added
+            }
+        }
+        const int cnt = n_sel - base < 64 ? n_sel - base : 64;
+        for (int j = 0; j < cnt; ++j) {
+            const double sj = __shfl(s, j, 64), tj = __shfl(sr, j, 64);
+            if (sj > 0) { sum_sim = sum_sim + sj; sum_ratings = sum_ratings + tj; ++actual_k; }
+        }
+    }
+    if (lane == 0) {
+        const bool imp = actual_k < a.min_k;                      // 'Not enough neighbors.'
+        a.est[q] = imp ? 0.0 : sum_ratings / sum_sim;
+        a.actual_k[q] = actual_k;
+        a.impossible[q] = imp ? 1 : 0;
+    }
+}
+
+// ---- predict + rmse ---------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) predict_kernel(const double* __restrict__ est, const uint8_t* __restrict__ imp,
+                                                      const double* __restrict__ r_true, int64_t n, double global_mean,
+                                                      double lo, double hi, double* __restrict__ pred,
+                                                      double* __restrict__ rmse) {
+    __shared__ double sq[256];
+    double acc = 0.0;                                             // thread 0's; test order
+    for (int64_t base = 0; base < n; base += 256) {
+        const int64_t i = base + threadIdx.x;
+        if (i < n) {
+            double e = imp[i] ? global_mean : est[i];
+            e = (e < hi) ? e : hi;                                // min(higher_bound, est)
+            e = (e > lo) ? e : lo;                                // max(lower_bound, est)
+            pred[i] = e;
+            if (r_true) { const double d = r_true[i] - e; sq[threadIdx.x] = d * d; }
+        }
+        if (r_true) {
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                const int cnt = n - base < 256 ? (int)(n - base) : 256;
+                for (int j = 0; j < cnt; ++j) acc = acc + sq[j];
+            }
+            __syncthreads();
+        }
+    }
+    if (r_true && threadIdx.x == 0) rmse[0] = sqrt(acc / (double)n);
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t n2v_eccknn_max_k(void) { return N2V_ECCKNN_MAX_K; }
+int64_t n2v_eccknn_max_dense(void) { return MAX_DENSE; }
+
+int n2v_eccknn_densify(const int32_t* x, const int32_t* y, const double* r, int64_t n, int64_t n_x, int64_t n_y,
+                       double* dense, uint8_t* mask, void* stream) {
+    if (n < 0 || n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_densify: n=%lld n_x=%lld n_y=%lld", (long long)n, (long long)n_x, (long long)n_y);
+    if (n_x > MAX_DENSE || n_y > MAX_DENSE || n_x * n_y > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_densify: n_x * n_y = %lld x %lld exceeds the dense limit of %lld elements",
+                         (long long)n_x, (long long)n_y, (long long)MAX_DENSE);
+    if (!dense || !mask || (n > 0 && (!x || !y || !r))) return n2v::fail(N2V_ERR_INVALID, "eccknn_densify: null pointer");
+    if (n > (int64_t)0x7fffffff * 256) return n2v::fail(N2V_ERR_INVALID, "eccknn_densify: too many ratings");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(dense, 0, (size_t)(n_x * n_y) * sizeof(double), s) != hipSuccess ||
+        hipMemsetAsync(mask, 0, (size_t)(n_x * n_y), s) != hipSuccess)
+        return n2v::fail(N2V_ERR_HIP, "eccknn_densify: memset failed");
+    if (n == 0) return N2V_OK;
+    densify_kernel<<<n2v::grid_for(n, 256), 256, 0, s>>>(x, y, r, n, n_x, n_y, dense, mask);
+    return n2v::check_launch("eccknn_densify");
+}
+
+int n2v_eccknn_sim(const double* dense, const uint8_t* mask, int64_t n_x, int64_t n_y, const double* w, int32_t method,
+                   int32_t min_support, double* sim, int32_t* freq, double* prods, double* sqi, double* sqj,
+                   double* sq_diff, void* stream) {
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
+    if (n_x > MAX_DENSE || n_y > MAX_DENSE || n_x * n_y > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x * n_y = %lld x %lld exceeds the dense limit of %lld elements",
+                         (long long)n_x, (long long)n_y, (long long)MAX_DENSE);
+    if (method != N2V_ECCKNN_COSINE && method != N2V_ECCKNN_MSD) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: method %d", method);
+    if (!dense || !mask || !w || !sim) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: null pointer");
+    const int64_t T = (n_x + TB - 1) / TB;
+    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
+    SimArgs a{dense, mask, n_x, n_y, w, min_support, sim, freq, prods, sqi, sqj, sq_diff};
+    const dim3 grid((unsigned)T, (unsigned)T);
+    if (method == N2V_ECCKNN_COSINE) sim_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else sim_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("eccknn_sim");
+}
+
+int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                        int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
+                        double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
+    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
+    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: min_k %d < 1 (an empty neighbourhood has no mean)", min_k);
+    if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_q %lld outside [1, 2^31)", (long long)n_q);
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
+    if (!sim || !yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: null pointer");
+    EstArgs a{sim, n_x, yr_ptr, yr_x, yr_r, n_y, qx, qy, n_q, k, min_k, est, actual_k, impossible};
+    estimate_kernel<<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("eccknn_estimate");
+}
+
+int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,
+                       double lo, double hi, double* pred, double* rmse, void* stream) {
+    if (n_q < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_predict: n_q %lld < 1", (long long)n_q);
+    if (!est || !impossible || !pred || (r_true && !rmse)) return n2v::fail(N2V_ERR_INVALID, "eccknn_predict: null pointer");
+    predict_kernel<<<1, 256, 0, (hipStream_t)stream>>>(est, impossible, r_true, n_q, global_mean, lo, hi, pred, rmse);
+    return n2v::check_launch("eccknn_predict");
+}
+
+}  // extern "C"

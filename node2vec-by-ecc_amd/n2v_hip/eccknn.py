@@ -1,0 +1,267 @@
+"""EccenKNN: eccentricity-weighted k-NN rating prediction on the device (csrc/n2v_eccknn.hip, C-ABI include/n2v_sim.h).
+
+Reference: src/main_rec.py:63-329, a user-based or item-based k-NN collaborative filter whose similarity (cosine or
+mean squared difference over co-rated entries) weights every co-rating by a per-item statistic.  Parity is unpinned:
+the reference needs `surprise`, which is not a dependency here, and its main() raises unconditionally; the semantics are
+restated from the text (tests/eccknn_reference.py) and the kernels are held to that restatement bit for bit.
+
+x is the side similarities are formed over, y the other one: users and items when `user_based`, swapped otherwise.
+The weights are an input (an array over y, or a dict raw id -> weight); the pandas statistics that produce them in the
+reference (src/utils.py:95-153) are not part of this module.
+
+Reference quirk, not reproduced: in item-based mode the reference indexes its per-item dictionary with inner *user*
+ids (src/main_rec.py:174 and :99).  Here the weight array is indexed by y, whichever side y is.
+
+`Trainset` and `predict` restate the documented behaviour of surprise's Trainset / AlgoBase.predict: inner ids by first
+appearance, an unknown user or item or an impossible estimate falls back to the training mean, and every estimate is
+clipped to the rating scale.  The training mean is sum(r) / n in training order.
+
+There is no CPU fallback.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_K = 256                      # N2V_ECCKNN_MAX_K
+SIM_NAMES = ("cosine", "msd", "pearson", "pearson_baseline")   # the reference's construction_func keys
+_METHOD = {"cosine": 0, "msd": 1}
+
+
+class PredictionImpossible(Exception):
+    pass
+
+
+def _require_gpu():
+    if not torch.cuda.is_available():
+        raise RuntimeError("n2v_hip.eccknn: no GPU visible (torch.cuda.is_available() is False); no CPU fallback")
+
+
+def _first_appearance(raw):
+    table, inner = {}, np.empty(len(raw), dtype=np.int64)
+    for n, v in enumerate(raw):
+        i = table.get(v)
+        if i is None:
+            i = table[v] = len(table)
+        inner[n] = i
+    return inner, table
+
+
+def _csr(major, minor, r, n_major):
+    """Lists of (minor, r) per major id, each in training order (a stable sort by major id)."""
+    order = np.argsort(major, kind="stable")
+    ptr = np.zeros(n_major + 1, dtype=np.int64)
+    np.cumsum(np.bincount(major, minlength=n_major), out=ptr[1:])
+    return ptr, minor[order].astype(np.int32), r[order].astype(np.float64)
+
+
+class Trainset:
+    """Ratings with inner ids, the way surprise's Trainset holds them.  ur / ir are CSR triples (ptr, other id, rating):
+    the ratings of inner user u are ur[1][ur[0][u]:ur[0][u + 1]] (inner item ids) with ur[2] alongside."""
+
+    @classmethod
+    def from_ratings(cls, users, items, ratings, rating_scale=None):
+        users, items = list(users), list(items)
+        r = np.asarray(ratings, dtype=np.float64)
+        if not (len(users) == len(items) == len(r)) or len(r) == 0:
+            raise ValueError("from_ratings: %d users, %d items, %d ratings" % (len(users), len(items), len(r)))
+        t = cls()
+        t.u, t._raw2inner_u = _first_appearance(users)
+        t.i, t._raw2inner_i = _first_appearance(items)
+        t.r = r
+        t.n_users, t.n_items, t.n_ratings = len(t._raw2inner_u), len(t._raw2inner_i), len(r)
+        key = t.u * t.n_items + t.i
+        if len(np.unique(key)) != len(key):
+            raise ValueError("from_ratings: duplicate (user, item) pair")
+        t.ur = _csr(t.u, t.i, r, t.n_users)
+        t.ir = _csr(t.i, t.u, r, t.n_items)
+        t.global_mean = float(np.cumsum(r)[-1] / len(r))       # cumsum adds one after the other, in training order
+        t.rating_scale = (float(r.min()), float(r.max())) if rating_scale is None else tuple(map(float, rating_scale))
+        return t
+
+    def knows_user(self, uid):
+        return isinstance(uid, (int, np.integer)) and 0 <= uid < self.n_users
+
+    def knows_item(self, iid):
+        return isinstance(iid, (int, np.integer)) and 0 <= iid < self.n_items
+
+    def to_inner_uid(self, ruid):
+        try:
+            return self._raw2inner_u[ruid]
+        except KeyError:
+            raise ValueError("User %s is not part of the trainset." % str(ruid))
+
+    def to_inner_iid(self, riid):
+        try:
+            return self._raw2inner_i[riid]
+        except KeyError:
+            raise ValueError("Item %s is not part of the trainset." % str(riid))
+
+    def inner_uids(self, raw):
+        """Inner ids of raw ids, -1 for unknown ones."""
+        return np.array([self._raw2inner_u.get(v, -1) for v in raw], dtype=np.int32)
+
+    def inner_iids(self, raw):
+        return np.array([self._raw2inner_i.get(v, -1) for v in raw], dtype=np.int32)
+
+
+# ---- C-ABI wrappers (device tensors in, device tensors out) -----------------------------------------------------------
+
+def densify(x, y, r, n_x, n_y):
+    """(dense fp64 [n_y][n_x], mask uint8 [n_y][n_x]) of int32 / fp64 device triples."""
+    _require_gpu()
+    lib = _lib.load()
+    if n_x * n_y > int(lib.n2v_eccknn_max_dense()):
+        raise ValueError("eccknn: n_x * n_y = %d x %d exceeds the dense limit of %d elements"
+                         % (n_x, n_y, lib.n2v_eccknn_max_dense()))
+    dev = r.device
+    with torch.cuda.device(dev):
+        dense = torch.empty((n_y, n_x), dtype=torch.float64, device=dev)
+        mask = torch.empty((n_y, n_x), dtype=torch.uint8, device=dev)
+        _lib.check(lib.n2v_eccknn_densify(_lib.ptr(x), _lib.ptr(y), _lib.ptr(r), r.numel(), n_x, n_y, _lib.ptr(dense),
+                                          _lib.ptr(mask), _lib.stream_ptr(dev)))
+    return dense, mask
+
+
+def similarity(dense, mask, w, name, min_support=1, accumulators=False):
+    """sim fp64 [n_x][n_x]; with accumulators also a dict of the reference's arrays (freq, and prods / sqi / sqj or
+    sq_diff)."""
+    _require_gpu()
+    n_y, n_x = dense.shape
+    dev = dense.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        sim = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
+        acc = {}
+        if accumulators:
+            acc["freq"] = torch.empty((n_x, n_x), dtype=torch.int32, device=dev)
+            for nm in (("prods", "sqi", "sqj") if name == "cosine" else ("sq_diff",)):
+                acc[nm] = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
+        _lib.check(lib.n2v_eccknn_sim(_lib.ptr(dense), _lib.ptr(mask), n_x, n_y, _lib.ptr(w), _METHOD[name], int(min_support),
+                                      _lib.ptr(sim), _lib.ptr(acc.get("freq")), _lib.ptr(acc.get("prods")),
+                                      _lib.ptr(acc.get("sqi")), _lib.ptr(acc.get("sqj")), _lib.ptr(acc.get("sq_diff")),
+                                      _lib.stream_ptr(dev)))
+    return (sim, acc) if accumulators else sim
+
+
+def estimate_batch(sim, yr, qx, qy, k, min_k):
+    """(est fp64, actual_k int32, impossible uint8) device tensors.  yr: device CSR triple (ptr int64, x int32, r fp64);
+    qx / qy: int32 device tensors, -1 = unknown."""
+    _require_gpu()
+    k, min_k = int(k), int(min_k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
+    if min_k < 1:
+        raise ValueError("min_k %d < 1" % min_k)
+    n_q = qx.numel()
+    if n_q == 0 or qy.numel() != n_q:
+        raise ValueError("estimate: %d x and %d y queries: nothing to estimate" % (n_q, qy.numel()))
+    dev = sim.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        est = torch.empty(n_q, dtype=torch.float64, device=dev)
+        actual_k = torch.empty(n_q, dtype=torch.int32, device=dev)
+        imp = torch.empty(n_q, dtype=torch.uint8, device=dev)
+        _lib.check(lib.n2v_eccknn_estimate(_lib.ptr(sim), sim.shape[0], _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]),
+                                           yr[0].numel() - 1, _lib.ptr(qx), _lib.ptr(qy), n_q, k, min_k, _lib.ptr(est),
+                                           _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
+    return est, actual_k, imp
+
+
+def predict(est, impossible, global_mean, rating_scale, r_true=None):
+    """pred (device fp64), and the rmse (a Python float) when r_true is given."""
+    _require_gpu()
+    dev = est.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        pred = torch.empty_like(est)
+        out = torch.zeros(1, dtype=torch.float64, device=dev) if r_true is not None else None
+        _lib.check(lib.n2v_eccknn_predict(_lib.ptr(est), _lib.ptr(impossible), _lib.ptr(r_true), est.numel(), float(global_mean),
+                                          float(rating_scale[0]), float(rating_scale[1]), _lib.ptr(pred), _lib.ptr(out),
+                                          _lib.stream_ptr(dev)))
+    return (pred, float(out.item())) if r_true is not None else pred
+
+
+# ---- the algorithm ----------------------------------------------------------------------------------------------------
+
+class EccenKNN:
+    def __init__(self, k=40, min_k=1, sim_options=None, device="cuda:0"):
+        self.k, self.min_k = int(k), int(min_k)
+        self.sim_options = dict(sim_options or {})
+        self.sim_options.setdefault("user_based", True)
+        self.device = device
+        name = self.sim_options.get("name", "msd").lower()
+        if name not in SIM_NAMES:
+            raise NameError("Wrong sim name " + name + ". Allowed values " + "are " + ", ".join(SIM_NAMES) + ".")
+        if name not in _METHOD:
+            raise NameError("Wrong sim name " + name + ". " + name + " is surprise's own similarity, not the reference's; "
+                            "here the allowed values are " + ", ".join(_METHOD) + ".")
+        if not 1 <= self.k <= MAX_K:
+            raise ValueError("k %d outside [1, %d]" % (self.k, MAX_K))
+        if self.min_k < 1:
+            raise ValueError("min_k %d < 1" % self.min_k)
+        self.name = name
+
+    def _weights(self, trainset, weights):
+        user_based = self.sim_options["user_based"]
+        n_y = trainset.n_items if user_based else trainset.n_users
+        if isinstance(weights, dict):
+            table = trainset._raw2inner_i if user_based else trainset._raw2inner_u
+            w = np.empty(n_y, dtype=np.float64)
+            for raw, inner in table.items():
+                w[inner] = weights[raw]                     # KeyError for a missing id, as i_dict[y] raises
+            return w
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (n_y,):
+            raise ValueError("weights: shape %s, expected (%d,)" % (w.shape, n_y))
+        return w
+
+    def fit(self, trainset, weights):
+        w = self._weights(trainset, weights)
+        _require_gpu()
+        dev = torch.device(self.device)
+        ts = trainset
+        user_based = self.sim_options["user_based"]
+        x, y, yr = (ts.u, ts.i, ts.ir) if user_based else (ts.i, ts.u, ts.ur)
+        self.n_x, self.n_y = (ts.n_users, ts.n_items) if user_based else (ts.n_items, ts.n_users)
+        self.trainset = ts
+        to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+        dense, mask = densify(to(x, torch.int32), to(y, torch.int32), to(ts.r, torch.float64), self.n_x, self.n_y)
+        self.sim = similarity(dense, mask, to(w, torch.float64), self.name, self.sim_options.get("min_support", 1))
+        self.yr = (to(yr[0], torch.int64), to(yr[1], torch.int32), to(yr[2], torch.float64))
+        return self
+
+    def _queries(self, u, i):
+        u = torch.as_tensor(np.asarray(u)).to(device=self.sim.device, dtype=torch.int32).contiguous()
+        i = torch.as_tensor(np.asarray(i)).to(device=self.sim.device, dtype=torch.int32).contiguous()
+        return (u, i) if self.sim_options["user_based"] else (i, u)
+
+    def estimate(self, u, i):
+        """(est, {'actual_k': n}) for inner ids u, i; PredictionImpossible as the reference raises it."""
+        if not (self.trainset.knows_user(u) and self.trainset.knows_item(i)):
+            raise PredictionImpossible("User and/or item is unkown.")
+        qx, qy = self._queries([u], [i])
+        est, ak, imp = estimate_batch(self.sim, self.yr, qx, qy, self.k, self.min_k)
+        if int(imp.item()):
+            raise PredictionImpossible("Not enough neighbors.")
+        return float(est.item()), {"actual_k": int(ak.item())}
+
+    def _test(self, testset):
+        """testset: (raw user, raw item, true rating) triples."""
+        testset = list(testset)
+        if not testset:
+            raise ValueError("test: empty testset")
+        ts = self.trainset
+        qx, qy = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
+        est, ak, imp = estimate_batch(self.sim, self.yr, qx, qy, self.k, self.min_k)
+        r_true = torch.as_tensor(np.array([t[2] for t in testset], dtype=np.float64)).to(self.sim.device)
+        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
+        return pred, ak, imp, err
+
+    def test(self, testset):
+        """Arrays (est, actual_k, was_impossible): est after the global-mean fallback and clipping."""
+        pred, ak, imp, _ = self._test(testset)
+        return pred.cpu().numpy(), ak.cpu().numpy(), imp.cpu().numpy().astype(bool)
+
+    def rmse(self, testset):
+        return self._test(testset)[3]
