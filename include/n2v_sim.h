@@ -115,6 +115,57 @@ int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, c
 int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,
                        double lo, double hi, double* pred, double* rmse, void* stream);
 
+/* ---- Eccentricity statistics: the ir / ie / ire / ier item weights and the per-user ue (csrc/n2v_eccstats.hip) -----
+ * Replaces src/utils.py:53-153 (pandas group-bys and merges).  Rows are (user, item, feedback, timewindow) with inner
+ * ids; a group is a distinct (item, timewindow) pair, numbered in ascending (item, timewindow) order.  Everything is
+ * fp64 / int32 / int64 on the caller's stream with caller-owned buffers.  Every rounded sum has one stated order
+ * (tests/eccstats_reference.py) and the result equals that restatement bit for bit; a NaN's sign and payload are not
+ * part of the contract.  Segment sums run left to right in segment order; global sums add consecutive chunks of
+ * N2V_ECCSTATS_CHUNK elements left to right, then the chunk sums left to right.                                    */
+#define N2V_ECCSTATS_CHUNK 4096
+#define N2V_ECCSTATS_Z 0         /* out = a - (mean / std)            stats of a; the reference's precedence        */
+#define N2V_ECCSTATS_ZERO_ONE 1  /* out = (a - min) / (max - min)     stats of a                                     */
+#define N2V_ECCSTATS_MUL 2       /* out = a * b                                                                      */
+#define N2V_ECCSTATS_DIV 3       /* out = a / b                                                                      */
+#define N2V_ECCSTATS_DIV_INF0 4  /* out = a / b, +-inf replaced by 0.0                                               */
+
+/* HOST: table[c] = -log((double)c) for 1 <= c < len by the host's libm (what Python's math.log calls), table[0] NaN.
+ * The device's log is not promised to equal libm's, so irg is resolved through this table.                         */
+int n2v_eccstats_log_table(int64_t len, double* table);
+
+/* key_sorted: int64[n] ascending, key = item * n_tw + rank of the timewindow (a stable sort); perm: int64[n], the row
+ * that sorted position k holds.  Writes row_group: int32[n] BY ROW, group_begin: int64[n + 1] (entries 0 .. n_groups),
+ * unum: int64[n] (entries < n_groups), item_gptr: int64[n_items + 1] (the groups of item i are item_gptr[i] ..
+ * item_gptr[i + 1]), counts: int64[2] = {n_groups, largest unum}.  scratch: int64[n2v_eccstats_groups_scratch(n)].
+ * 1 <= n < 2^31.                                                                                                    */
+int64_t n2v_eccstats_groups_scratch(int64_t n);
+int n2v_eccstats_groups(const int64_t* key_sorted, const int64_t* perm, int64_t n, int64_t n_tw, int64_t n_items,
+                        int64_t* scratch, int32_t* row_group, int64_t* group_begin, int64_t* unum, int64_t* item_gptr,
+                        int64_t* counts, void* stream);
+/* irg[g] = log_table[unum[g]] (a DEVICE copy of the table).  A count outside [1, table_len) gives NaN and sets bit 0
+ * of *status (int32, device, cleared by the caller).                                                                */
+int n2v_eccstats_irg(const int64_t* unum, int64_t n_groups, const double* log_table, int64_t table_len, double* irg,
+                     int32_t* status, void* stream);
+
+/* Segments s = [seg_ptr[s], seg_ptr[s + 1]) of positions k; p = perm[k] (perm NULL: p = k):
+ *   out_sum[s]  = sum a[p]                  (mean != 0: divided by the segment's length)
+ *   out_wsum[s] = sum a[p] * g[idx[p]]      (idx NULL: g[p]); each product rounded before it is added
+ * both from +0.0, left to right.  A p outside [0, n_a) or an index outside [0, n_g) contributes NaN.  Segments shorter
+ * than 64 take one lane each, longer ones a wavefront each.  out_sum or out_wsum may be NULL.
+ * scratch: int32[n_seg + 1].  1 <= n_seg < 2^31.                                                                    */
+int n2v_eccstats_segsum(const int64_t* seg_ptr, int64_t n_seg, const int64_t* perm, const double* a, int64_t n_a,
+                        const int32_t* idx, const double* g, int64_t n_g, int32_t mean, int32_t* scratch, double* out_sum,
+                        double* out_wsum, void* stream);
+
+/* stats: fp64[8] = {sum, mean = sum / n, ssd = sum (x - mean) * (x - mean), var = ssd / n, std = sqrt(var), min, max,
+ * n}.  min / max: NaN if any x is NaN; -0.0 is below +0.0.  scratch: fp64[n2v_eccstats_moments_scratch(n)].        */
+int64_t n2v_eccstats_moments_scratch(int64_t n);
+int n2v_eccstats_moments(const double* x, int64_t n, double* scratch, double* stats, void* stream);
+
+/* Elementwise, op one of N2V_ECCSTATS_*; b is read by MUL / DIV / DIV_INF0, stats by Z / ZERO_ONE.                  */
+int n2v_eccstats_finish(int32_t op, const double* a, const double* b, const double* stats, int64_t n, double* out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,17 @@
 """Drop-in for the working part of the reference's src/main_rec.py: EccenKNN rating prediction on the device.
 
     python main_rec.py -input ratings.csv [-k 40] [-mink 1] [-sim cosine|msd] [-item-based] [-weights FILE]
+                       [-mode ir|ie|ire|ier] [-window-col timestamp|timewindow] [-save-weights FILE]
                        [-test-ratio 0.2] [-seed 0] [-cv N]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
-          The reference derives them with pandas (src/utils.py:95-153); here they are an input.
+-mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
+          rarity, item eccentricity, their product or their quotient, from the WHOLE input file before the split, as the
+          reference's fit does.  Needs the 4th column: a unix timestamp, cut into UTC months (-window-col timestamp, the
+          default; the reference cuts in the machine's local zone) or the time window itself (-window-col timewindow).
+          Conflicts with -weights and with -item-based (the reference keys the weights by item there while y is a user).
+-save-weights  write the `id,weight` lines that were used, in the form -weights reads.
 The split is seeded: a permutation of the ratings by numpy's RandomState(seed), the first round(n * ratio) of it are
 the test set and the rest, in file order, the training set.  -cv N runs N folds of the same permutation instead.
 Prints `RMSE: <repr>` per split (and their mean for -cv).
@@ -25,6 +31,9 @@ def parse_args(argv=None):
     p.add_argument("-item-based", dest="item_based", action="store_true")
     p.add_argument("-min-support", dest="min_support", type=int, default=1)
     p.add_argument("-weights", default=None)
+    p.add_argument("-mode", default=None, choices=["ir", "ie", "ire", "ier"])
+    p.add_argument("-window-col", dest="window_col", default="timestamp", choices=["timestamp", "timewindow"])
+    p.add_argument("-save-weights", dest="save_weights", default=None)
     p.add_argument("-test-ratio", dest="test_ratio", type=float, default=0.2)
     p.add_argument("-seed", type=int, default=0)
     p.add_argument("-cv", type=int, default=0)
@@ -34,6 +43,17 @@ def parse_args(argv=None):
         p.error("-test-ratio must be inside (0, 1)")
     if a.cv == 1 or a.cv < 0:
         p.error("-cv needs at least 2 folds")
+    if a.mode and a.weights:
+        p.error("-mode computes the weights, -weights reads them: give one of the two")
+    if a.mode and a.item_based:
+        p.error("-mode weights items, and with -item-based the weighted side is the users")
+    if a.save_weights and not (a.mode or a.weights):
+        p.error("-save-weights: there are no weights to save without -mode or -weights")
+    if a.mode:
+        try:
+            a.windows = read_windows(a.input, a.window_col)
+        except ValueError as e:
+            p.error(str(e))
     return a
 
 
@@ -55,6 +75,39 @@ def read_ratings(path):
                 raise
             users.append(parts[0]); items.append(parts[1]); ratings.append(r)
     return users, items, np.array(ratings, dtype=np.float64)
+
+
+def read_windows(path, window_col):
+    """The time window of every row that read_ratings keeps: the 4th column itself, or its UTC month."""
+    col = []
+    with open(path) as f:
+        for n, line in enumerate(f):
+            parts = line.strip().split(",")
+            if len(parts) < 3:
+                continue
+            try:
+                float(parts[2])
+            except ValueError:
+                if n == 0:
+                    continue
+                raise
+            if len(parts) < 4 or not parts[3].strip():
+                raise ValueError("%s:%d: -mode needs the 4th column (%s) and this line has none" % (path, n + 1, window_col))
+            try:
+                col.append(int(parts[3]))
+            except ValueError:
+                col.append(int(float(parts[3])))
+    col = np.array(col, dtype=np.int64)
+    if window_col == "timewindow":
+        return col
+    from n2v_hip import eccstats
+    return eccstats.timewindow_utc(col)
+
+
+def write_weights(path, weights):
+    with open(path, "w") as f:
+        for k, v in weights.items():
+            f.write("%s,%r\n" % (k, v))
 
 
 def read_weights(path):
@@ -103,6 +156,11 @@ def main(argv=None):
     args = parse_args(argv)
     users, items, ratings = read_ratings(args.input)
     weights = read_weights(args.weights) if args.weights else None
+    if args.mode:
+        from n2v_hip import eccstats
+        weights = eccstats.item_statistics(users, items, ratings, args.windows, device=args.device).weights(args.mode)
+    if args.save_weights:
+        write_weights(args.save_weights, weights)
     if args.cv:
         errs = []
         for train, test in folds(len(ratings), args.cv, args.seed):
