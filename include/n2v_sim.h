@@ -98,6 +98,26 @@ int n2v_eccknn_sim(const double* dense, const uint8_t* mask, int64_t n_x, int64_
                    int32_t min_support, double* sim, int32_t* freq, double* prods, double* sqi, double* sqj,
                    double* sq_diff, void* stream);
 
+/* The sparse form of n2v_eccknn_sim: the same outputs, byte for byte, from the x-major CSR of the ratings instead of the
+ * dense matrix, so nothing of size n_x * n_y exists and there is no bound on that product.  xr_ptr: int64[n_x + 1];
+ * xr_y: int32[n], strictly ascending inside a row; xr_r: fp64[n]; row x is [xr_ptr[x], xr_ptr[x + 1]).  An empty row is
+ * legal (freq 0, sim 0 off the diagonal); xr_y and xr_r may be NULL when n == 0.  One workgroup per 64x64 tile of the
+ * upper triangle: the tile's rows pass through LDS in rounds of up to n2v_eccknn_sparse_chunk() entries a row, and every
+ * pair merges the two staged segments in y order, so each pair still visits its co-rated y ascending.
+ * n_x >= 1, 1 <= n_y < 2^31, n >= 0, n_x <= 65535 * 64.
+ * The kernel reads nothing outside xr_y[0..n), xr_r[0..n) and w[0..n_y) whatever the arrays hold: row ranges are clamped
+ * to [0, n] and an entry whose y is outside [0, n_y) takes w = NaN.  Malformed arrays give garbage values, not a fault;
+ * n2v_eccknn_csr_check (integers only) names what is wrong by bits of *status (int32, device, cleared by the caller):    */
+#define N2V_ECCKNN_CSR_BAD_PTR 1    /* xr_ptr not monotone, or an entry of it outside [0, n]                            */
+#define N2V_ECCKNN_CSR_BAD_Y 2      /* an xr_y outside [0, n_y)                                                         */
+#define N2V_ECCKNN_CSR_UNSORTED 4   /* two neighbouring entries of one row not strictly ascending                       */
+int32_t n2v_eccknn_sparse_chunk(void);   /* entries of one row staged per round                                         */
+int n2v_eccknn_csr_check(const int64_t* xr_ptr, const int32_t* xr_y, int64_t n_x, int64_t n_y, int64_t n, int32_t* status,
+                         void* stream);
+int n2v_eccknn_sim_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_x, int64_t n_y,
+                          int64_t n, const double* w, int32_t method, int32_t min_support, double* sim, int32_t* freq,
+                          double* prods, double* sqi, double* sqj, double* sq_diff, void* stream);
+
 /* One wavefront per query (qx[q], qy[q]); -1 = unknown.  yr_ptr: int64[n_y + 1], yr_x: int32, yr_r: fp64 — the raters
  * of every y in training order.  Candidates are (sim[x, x2], r) in list order; the k largest by sim are kept, equal
  * sims in list order (heapq.nlargest with a key = a stable descending sort), -0.0 ties +0.0.  DEVIATION: a NaN sim

@@ -11,6 +11,14 @@
 //                    not a multiply by zero: ratings may be anything).  No float atomics (their order is undefined) and
 //                    no v_mfma_f64 (its four products are not added one after the other).  The mirror is written from
 //                    the same tile: prods and sq_diff are symmetric bit for bit, sqi and sqj swap.
+//   sim_sparse_kernel the same frame and the same outputs from the x-major CSR of the ratings: nothing of size n_x x n_y
+//                    exists.  The tile's 128 rows pass through LDS in rounds of up to SC entries (y, r) a row, each row
+//                    from its own cursor.  A round's bound is the smallest last-staged y among the rows that have entries
+//                    beyond their staged ones: up to it every row's staged segment is complete, so every thread merges
+//                    its 16 pairs of segments two-pointer fashion in y order, and the cursors advance by what was ready.
+//                    The row that set the bound consumes its whole chunk, so every round makes progress.  finish_tile is
+//                    shared with sim_kernel.  csr_check_kernel (integers only) names a malformed CSR; the similarity
+//                    kernel itself clamps every row range to [0, n] and never indexes w with a y outside [0, n_y).
 //   estimate_kernel  one wavefront per query: gathers sim[x, x2] over the raters of y, keeps the best k of them in a
 //                    sorted LDS list under the one order of n2v_rec.hip (higher sim first, equal sims by list position,
 //                    -0.0 ties +0.0, NaN below everything) and sums in rank order.
@@ -41,10 +49,52 @@ __global__ void __launch_bounds__(256) densify_kernel(const int32_t* __restrict_
 
 // ---- similarity -------------------------------------------------------------------------------------------------------
 
-struct SimArgs {
-    const double* dense; const uint8_t* mask; int64_t n_x; int64_t n_y; const double* w; int min_support;
+struct SimOut {
+    int64_t n_x; int min_support;
     double* sim; int32_t* freq; double* prods; double* sqi; double* sqj; double* sq_diff;
 };
+struct SimArgs {
+    const double* dense; const uint8_t* mask; int64_t n_y; const double* w; SimOut o;
+};
+
+// The finishing step of a tile, the one copy behind the dense and the sparse kernel: thread (ty, tx) holds the
+// accumulators of pairs (i0 + 4 ty + u, j0 + 4 tx + v).  i == j -> 1, freq < min_support -> 0, else the division and
+// the sqrt; the mirror is written from the same values with sqi / sqj swapped.
+template <int METHOD>
+__device__ __forceinline__ void finish_tile(const SimOut& o, int64_t i0, int64_t j0, int ty, int tx, bool diag_tile,
+                                            const int32_t (&fr)[4][4], const double (&p0)[4][4], const double (&p1)[4][4],
+                                            const double (&p2)[4][4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = i0 + 4 * ty + u;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int64_t j = j0 + 4 * tx + v;
+            if (i >= o.n_x || j >= o.n_x) continue;
+            double s;
+            if (i == j) s = 1.0;
+            else if (fr[u][v] < o.min_support) s = 0.0;
+            else if (METHOD == N2V_ECCKNN_COSINE) s = p0[u][v] / sqrt(p1[u][v] * p2[u][v]);
+            else s = 1.0 / (p0[u][v] / (double)fr[u][v] + 1.0);
+            const int64_t k = i * o.n_x + j, m = j * o.n_x + i;
+            o.sim[k] = s;
+            if (o.freq) o.freq[k] = fr[u][v];
+            if (METHOD == N2V_ECCKNN_COSINE) {
+                if (o.prods) o.prods[k] = p0[u][v];
+                if (o.sqi) o.sqi[k] = p1[u][v];
+                if (o.sqj) o.sqj[k] = p2[u][v];
+            } else if (o.sq_diff) o.sq_diff[k] = p0[u][v];
+            if (diag_tile) continue;                              // a diagonal tile computed its own lower half
+            o.sim[m] = s;
+            if (o.freq) o.freq[m] = fr[u][v];
+            if (METHOD == N2V_ECCKNN_COSINE) {
+                if (o.prods) o.prods[m] = p0[u][v];
+                if (o.sqi) o.sqi[m] = p2[u][v];
+                if (o.sqj) o.sqj[m] = p1[u][v];
+            } else if (o.sq_diff) o.sq_diff[m] = p0[u][v];
+        }
+    }
+}
 
 template <int METHOD>
 __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
@@ -74,8 +124,8 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
             double va = 0.0, vb = 0.0;
             uint8_t qa = 0, qb = 0;
             if (y < a.n_y) {
-                if (i0 + c < a.n_x) { va = a.dense[y * a.n_x + i0 + c]; qa = a.mask[y * a.n_x + i0 + c]; }
-                if (j0 + c < a.n_x) { vb = a.dense[y * a.n_x + j0 + c]; qb = a.mask[y * a.n_x + j0 + c]; }
+                if (i0 + c < a.o.n_x) { va = a.dense[y * a.o.n_x + i0 + c]; qa = a.mask[y * a.o.n_x + i0 + c]; }
+                if (j0 + c < a.o.n_x) { vb = a.dense[y * a.o.n_x + j0 + c]; qb = a.mask[y * a.o.n_x + j0 + c]; }
             }
             ra[yy][c] = va; rb[yy][c] = vb; ma[yy][c] = qa; mb[yy][c] = qb;
         }
@@ -119,37 +169,159 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
         }
     }
 
-    const bool diag_tile = ti == tj;
+    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2);
+}
+
+// ---- similarity, sparse -----------------------------------------------------------------------------------------------
+
+constexpr int SC = 16;            // entries of one row staged per round
+constexpr int SP = SC + 1;        // padded row length in LDS: the 16 column rows of a wavefront fall on distinct banks
+constexpr int Y_MAX = 0x7fffffff;
+
+struct SparseArgs {
+    const int64_t* xr_ptr; const int32_t* xr_y; const double* xr_r; int64_t n_y; int64_t n; const double* w; int64_t tiles;
+    SimOut o;
+};
+
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+template <int METHOD>
+__global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
+    __shared__ int32_t sy[2 * TB][SP];                            // rows 0..63: the tile's rows, 64..127: its columns
+    __shared__ double sr[2 * TB][SP];
+    __shared__ double sw[TB][SP];                                 // w[y] of the staged entries of the tile's rows
+    __shared__ int64_t pos[2 * TB], end[2 * TB];                  // cursor and end of every row, inside [0, n]
+    __shared__ int32_t ready[2 * TB];
+    __shared__ int32_t bound[2];
+
+    // blockIdx.x counts the tiles of the upper triangle row by row: row ti starts at ti * T - ti (ti - 1) / 2
+    const int64_t T = a.tiles, b = blockIdx.x;
+    const double td = (double)(2 * T + 1);
+    int64_t ti = clamp64((int64_t)((td - sqrt(td * td - 8.0 * (double)b)) * 0.5), 0, T - 1);
+    while (ti + 1 < T && (ti + 1) * T - (ti + 1) * ti / 2 <= b) ++ti;
+    while (ti > 0 && ti * T - ti * (ti - 1) / 2 > b) --ti;
+    const int64_t tj = ti + (b - (ti * T - ti * (ti - 1) / 2));
+
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int64_t i0 = ti * TB, j0 = tj * TB;
+
+    int32_t fr[4][4];
+    double p0[4][4], p1[4][4], p2[4][4];                          // cosine: prods, sqi, sqj; msd: sq_diff, -, -
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        const int64_t i = i0 + 4 * ty + u;
+    for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int64_t j = j0 + 4 * tx + v;
-            if (i >= a.n_x || j >= a.n_x) continue;
-            double s;
-            if (i == j) s = 1.0;
-            else if (fr[u][v] < a.min_support) s = 0.0;
-            else if (METHOD == N2V_ECCKNN_COSINE) s = p0[u][v] / sqrt(p1[u][v] * p2[u][v]);
-            else s = 1.0 / (p0[u][v] / (double)fr[u][v] + 1.0);
-            const int64_t o = i * a.n_x + j, m = j * a.n_x + i;
-            a.sim[o] = s;
-            if (a.freq) a.freq[o] = fr[u][v];
-            if (METHOD == N2V_ECCKNN_COSINE) {
-                if (a.prods) a.prods[o] = p0[u][v];
-                if (a.sqi) a.sqi[o] = p1[u][v];
-                if (a.sqj) a.sqj[o] = p2[u][v];
-            } else if (a.sq_diff) a.sq_diff[o] = p0[u][v];
-            if (diag_tile) continue;                              // a diagonal tile computed its own lower half
-            a.sim[m] = s;
-            if (a.freq) a.freq[m] = fr[u][v];
-            if (METHOD == N2V_ECCKNN_COSINE) {
-                if (a.prods) a.prods[m] = p0[u][v];
-                if (a.sqi) a.sqi[m] = p2[u][v];
-                if (a.sqj) a.sqj[m] = p1[u][v];
-            } else if (a.sq_diff) a.sq_diff[m] = p0[u][v];
+        for (int v = 0; v < 4; ++v) { fr[u][v] = 0; p0[u][v] = 0.0; p1[u][v] = 0.0; p2[u][v] = 0.0; }
+
+    int live_a = 0, live_b = 0;
+    if (t < 2 * TB) {
+        const int64_t row = t < TB ? i0 + t : j0 + (t - TB);
+        int64_t pb = 0, pe = 0;
+        if (row < a.o.n_x) {
+            pb = clamp64(a.xr_ptr[row], 0, a.n);
+            pe = clamp64(a.xr_ptr[row + 1], pb, a.n);
+        }
+        pos[t] = pb; end[t] = pe;
+        live_a = t < TB && pb < pe; live_b = t >= TB && pb < pe;
+    }
+    if (t < 2) bound[t] = Y_MAX;
+    int n_a = __syncthreads_count(live_a), n_b = __syncthreads_count(live_b);
+    int par = 0;
+    while (n_a && n_b) {                                          // a tile ends when either side is exhausted
+        for (int e = t; e < 2 * TB * SC; e += 256) {
+            const int row = e / SC, k = e % SC;
+            const int64_t p = pos[row] + k;
+            if (p < end[row]) {
+                const int32_t y = a.xr_y[p];
+                sy[row][k] = y;
+                sr[row][k] = a.xr_r[p];
+                if (row < TB) sw[row][k] = (y >= 0 && y < a.n_y) ? a.w[y] : __builtin_nan("");
+            }
+        }
+        // the bound: the smallest last-staged y among rows with entries beyond their staged ones (none: everything)
+        if (t < 2 * TB && end[t] - pos[t] > SC) atomicMin(&bound[par], a.xr_y[pos[t] + SC - 1]);
+        if (t == 2 * TB) bound[par ^ 1] = Y_MAX;
+        __syncthreads();
+        live_a = 0; live_b = 0;
+        if (t < 2 * TB) {
+            const int32_t bd = bound[par];
+            const int64_t rem = end[t] - pos[t];
+            const int cnt = rem < SC ? (int)rem : SC;
+            int rd = 0;
+            if (cnt > 0) {
+                if (sy[t][cnt - 1] <= bd) rd = cnt;               // also what makes the bound's own row advance
+                else while (rd < cnt && sy[t][rd] <= bd) ++rd;
+            }
+            ready[t] = rd;
+            pos[t] += rd;
+            live_a = t < TB && pos[t] < end[t]; live_b = t >= TB && pos[t] < end[t];
+        }
+        n_a = __syncthreads_count(live_a);
+        n_b = __syncthreads_count(live_b);
+        int na[4], nb[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { na[u] = ready[4 * ty + u]; nb[u] = ready[TB + 4 * tx + u]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int ra = 4 * ty + u;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int rb = TB + 4 * tx + v;
+                if (na[u] == 0 || nb[v] == 0) continue;
+                if (sy[ra][na[u] - 1] < sy[rb][0] || sy[rb][nb[v] - 1] < sy[ra][0]) continue;   // disjoint y ranges
+                int ka = 0, kb = 0;
+                int32_t ya = sy[ra][0], yb = sy[rb][0];
+                for (;;) {                                        // y ascending: the order of every accumulator
+                    if (ya == yb) {
+                        const double ri = sr[ra][ka], rj = sr[rb][kb], wy = sw[ra][ka];
+                        fr[u][v] += 1;
+                        if (METHOD == N2V_ECCKNN_COSINE) {
+                            p0[u][v] = p0[u][v] + (ri * rj) * wy; // `ri * rj * i_dict[y]`: left to right
+                            p1[u][v] = p1[u][v] + ri * ri;
+                            p2[u][v] = p2[u][v] + rj * rj;
+                        } else {
+                            const double d = (ri - rj) * wy;
+                            p0[u][v] = p0[u][v] + d * d;
+                        }
+                        if (++ka >= na[u] || ++kb >= nb[v]) break;
+                        ya = sy[ra][ka]; yb = sy[rb][kb];
+                    } else if (ya < yb) {
+                        if (++ka >= na[u]) break;
+                        ya = sy[ra][ka];
+                    } else {
+                        if (++kb >= nb[v]) break;
+                        yb = sy[rb][kb];
+                    }
+                }
+            }
+        }
+        par ^= 1;
+        __syncthreads();                                          // the staged segments have been consumed
+    }
+    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2);
+}
+
+// One lane per row and per entry; integers only.
+__global__ void __launch_bounds__(256) csr_check_kernel(const int64_t* __restrict__ xr_ptr, const int32_t* __restrict__ xr_y,
+                                                        int64_t n_x, int64_t n_y, int64_t n, int32_t* __restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int32_t bits = 0;
+    if (i < n_x) {
+        const int64_t pb = xr_ptr[i], pe = xr_ptr[i + 1];
+        if (pb < 0 || pb > n || pe < 0 || pe > n || pe < pb) bits |= N2V_ECCKNN_CSR_BAD_PTR;
+    }
+    if (i < n) {
+        const int32_t y = xr_y[i];
+        if (y < 0 || y >= n_y) bits |= N2V_ECCKNN_CSR_BAD_Y;
+        if (i > 0 && xr_y[i - 1] >= y) {                          // legal only where a row starts at i
+            int64_t lo = 0, hi = n_x + 1;                         // first k in [0, n_x] with xr_ptr[k] >= i
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (xr_ptr[mid] < i) lo = mid + 1; else hi = mid;
+            }
+            if (lo > n_x || xr_ptr[lo] != i) bits |= N2V_ECCKNN_CSR_UNSORTED;
         }
     }
+    if (bits) atomicOr(status, bits);
 }
 
 // ---- estimate ---------------------------------------------------------------------------------------------------------
@@ -329,11 +501,39 @@ int n2v_eccknn_sim(const double* dense, const uint8_t* mask, int64_t n_x, int64_
     if (!dense || !mask || !w || !sim) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: null pointer");
     const int64_t T = (n_x + TB - 1) / TB;
     if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SimArgs a{dense, mask, n_x, n_y, w, min_support, sim, freq, prods, sqi, sqj, sq_diff};
+    SimArgs a{dense, mask, n_y, w, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff}};
     const dim3 grid((unsigned)T, (unsigned)T);
     if (method == N2V_ECCKNN_COSINE) sim_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else sim_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     return n2v::check_launch("eccknn_sim");
+}
+
+int32_t n2v_eccknn_sparse_chunk(void) { return SC; }
+
+int n2v_eccknn_csr_check(const int64_t* xr_ptr, const int32_t* xr_y, int64_t n_x, int64_t n_y, int64_t n, int32_t* status,
+                         void* stream) {
+    if (n_x < 1 || n_y < 1 || n < 0) return n2v::fail(N2V_ERR_INVALID, "eccknn_csr_check: n_x=%lld n_y=%lld n=%lld", (long long)n_x, (long long)n_y, (long long)n);
+    if (!xr_ptr || !status || (n > 0 && !xr_y)) return n2v::fail(N2V_ERR_INVALID, "eccknn_csr_check: null pointer");
+    const int64_t lanes = n_x > n ? n_x : n;
+    if (lanes > (int64_t)0x7fffffff * 256) return n2v::fail(N2V_ERR_INVALID, "eccknn_csr_check: too many rows or entries");
+    csr_check_kernel<<<n2v::grid_for(lanes, 256), 256, 0, (hipStream_t)stream>>>(xr_ptr, xr_y, n_x, n_y, n, status);
+    return n2v::check_launch("eccknn_csr_check");
+}
+
+int n2v_eccknn_sim_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_x, int64_t n_y,
+                          int64_t n, const double* w, int32_t method, int32_t min_support, double* sim, int32_t* freq,
+                          double* prods, double* sqi, double* sqj, double* sq_diff, void* stream) {
+    if (n_x < 1 || n_y < 1 || n_y > Y_MAX || n < 0)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: n_x=%lld n_y=%lld n=%lld", (long long)n_x, (long long)n_y, (long long)n);
+    if (method != N2V_ECCKNN_COSINE && method != N2V_ECCKNN_MSD) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: method %d", method);
+    if (!xr_ptr || !w || !sim || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: null pointer");
+    const int64_t T = (n_x + TB - 1) / TB;
+    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
+    SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff}};
+    const unsigned grid = (unsigned)(T * (T + 1) / 2);            // < 2^31 for T <= 65535
+    if (method == N2V_ECCKNN_COSINE) sim_sparse_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else sim_sparse_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("eccknn_sim_sparse");
 }
 
 int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,

@@ -2,7 +2,7 @@
 
     python main_rec.py -input ratings.csv [-k 40] [-mink 1] [-sim cosine|msd] [-item-based] [-weights FILE]
                        [-mode ir|ie|ire|ier] [-window-col timestamp|timewindow] [-save-weights FILE]
-                       [-test-ratio 0.2] [-seed 0] [-cv N]
+                       [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
@@ -12,6 +12,7 @@
           default; the reference cuts in the machine's local zone) or the time window itself (-window-col timewindow).
           Conflicts with -weights and with -item-based (the reference keys the weights by item there while y is a user).
 -save-weights  write the `id,weight` lines that were used, in the form -weights reads.
+-form     the similarity kernel: dense (n_x * n_y at most 2^31), sparse (rating lists, no such limit), auto = dense inside it.
 The split is seeded: a permutation of the ratings by numpy's RandomState(seed), the first round(n * ratio) of it are
 the test set and the rest, in file order, the training set.  -cv N runs N folds of the same permutation instead.
 Prints `RMSE: <repr>` per split (and their mean for -cv).
@@ -37,6 +38,7 @@ def parse_args(argv=None):
     p.add_argument("-test-ratio", dest="test_ratio", type=float, default=0.2)
     p.add_argument("-seed", type=int, default=0)
     p.add_argument("-cv", type=int, default=0)
+    p.add_argument("-form", default="auto", choices=["auto", "dense", "sparse"])
     p.add_argument("-device", default="cuda:0")
     a = p.parse_args(argv)
     if not 0.0 < a.test_ratio < 1.0:
@@ -143,7 +145,8 @@ def run_split(args, users, items, ratings, weights, train, test):
     ts = eccknn.Trainset.from_ratings([users[i] for i in train], [items[i] for i in train], ratings[train],
                                       rating_scale=(float(ratings.min()), float(ratings.max())))
     algo = eccknn.EccenKNN(k=args.k, min_k=args.mink, device=args.device,
-                           sim_options={"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support})
+                           sim_options={"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support,
+                                        "form": args.form})
     if weights is None:
         w = np.ones(ts.n_users if args.item_based else ts.n_items)
     else:

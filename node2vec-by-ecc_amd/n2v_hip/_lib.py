@@ -102,6 +102,10 @@ SIGNATURES = {
     "n2v_eccknn_max_dense": (C.c_int64, []),
     "n2v_eccknn_densify": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]),
     "n2v_eccknn_sim": (C.c_int, [_ptr, _ptr, _i64, _i64, _ptr, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_sparse_chunk": (C.c_int32, []),
+    "n2v_eccknn_csr_check": (C.c_int, [_ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr]),
+    "n2v_eccknn_sim_sparse": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                        _ptr, _ptr]),
     "n2v_eccknn_estimate": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr,
                                       _ptr]),
     "n2v_eccknn_predict": (C.c_int, [_ptr, _ptr, _ptr, _i64, _f64, _f64, _f64, _ptr, _ptr, _ptr]),

@@ -16,6 +16,10 @@ ids (src/main_rec.py:174 and :99).  Here the weight array is indexed by y, which
 appearance, an unknown user or item or an impossible estimate falls back to the training mean, and every estimate is
 clipped to the rating scale.  The training mean is sum(r) / n in training order.
 
+The similarity has two forms with the same bytes: the dense one (a y-major fp64 matrix plus a mask, n_x * n_y at most
+n2v_eccknn_max_dense() elements) and the sparse one (the x-major CSR of the ratings, no such bound).
+sim_options["form"] = "auto" (the default: dense inside the limit, sparse past it), "dense" or "sparse".
+
 There is no CPU fallback.
 """
 import numpy as np
@@ -26,6 +30,10 @@ from . import _lib
 MAX_K = 256                      # N2V_ECCKNN_MAX_K
 SIM_NAMES = ("cosine", "msd", "pearson", "pearson_baseline")   # the reference's construction_func keys
 _METHOD = {"cosine": 0, "msd": 1}
+FORMS = ("auto", "dense", "sparse")
+MAX_DENSE = 1 << 31              # n2v_eccknn_max_dense()
+CSR_BAD = ((1, "xr_ptr is not monotone or leaves [0, n]"), (2, "a y outside [0, n_y)"),
+           (4, "a row is not strictly ascending in y (a duplicate (x, y) pair?)"))
 
 
 class PredictionImpossible(Exception):
@@ -144,6 +152,74 @@ def similarity(dense, mask, w, name, min_support=1, accumulators=False):
     return (sim, acc) if accumulators else sim
 
 
+def choose_form(n_x, n_y, form, limit=MAX_DENSE):
+    """"dense" or "sparse" for an n_x x n_y problem.  Host arithmetic only.  "auto" is dense iff n_x * n_y <= limit; an
+    explicit "dense" past the limit is the dense path's own error."""
+    if form not in FORMS:
+        raise ValueError("eccknn: form %r, allowed values are %s" % (form, ", ".join(FORMS)))
+    over = int(n_x) * int(n_y) > int(limit)
+    if form == "dense" and over:
+        raise ValueError("eccknn: n_x * n_y = %d x %d exceeds the dense limit of %d elements" % (n_x, n_y, limit))
+    if form == "auto":
+        return "sparse" if over else "dense"
+    return form
+
+
+def csr_by_x(x, y, r, n_x, n_y=None):
+    """Device triples (x, y int32 / int64, r fp64), no duplicate (x, y) -> the x-major CSR (xr_ptr int64[n_x + 1],
+    xr_y int32, xr_r fp64), every row ascending in y: a stable sort on the key x * n_y + y.  n_y None: the largest y + 1."""
+    _require_gpu()
+    x64, y64 = x.to(torch.int64), y.to(torch.int64)
+    if n_y is None:
+        n_y = int(y64.max().item()) + 1 if y64.numel() else 1
+    _, order = torch.sort(x64 * int(n_y) + y64, stable=True)
+    ptr = torch.zeros(int(n_x) + 1, dtype=torch.int64, device=x.device)
+    ptr[1:] = torch.cumsum(torch.bincount(x64, minlength=int(n_x)), 0)
+    return ptr, y64[order].to(torch.int32).contiguous(), r[order].to(torch.float64).contiguous()
+
+
+def csr_check(xr, n_y):
+    """Raises ValueError when the x-major CSR is malformed (n2v_eccknn_csr_check); one read-back of an int32."""
+    _require_gpu()
+    ptr_, ys = xr[0], xr[1]
+    dev = ptr_.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.n2v_eccknn_csr_check(_lib.ptr(ptr_), _lib.ptr(ys), ptr_.numel() - 1, int(n_y), ys.numel(),
+                                            _lib.ptr(status), _lib.stream_ptr(dev)))
+        bits = int(status.item())
+    if bits:
+        raise ValueError("eccknn: malformed CSR: " + "; ".join(msg for b, msg in CSR_BAD if bits & b))
+
+
+def similarity_sparse(xr, w, n_y, name, min_support=1, accumulators=False):
+    """similarity() from the x-major CSR xr = (xr_ptr, xr_y, xr_r) of csr_by_x: the same return value, the same bytes, and
+    no n_x * n_y limit.  The CSR is checked first; a malformed one is a ValueError."""
+    _require_gpu()
+    if len(xr) != 3 or xr[0].dtype != torch.int64 or xr[1].dtype != torch.int32 or xr[2].dtype != torch.float64:
+        raise ValueError("similarity_sparse: xr must be (int64 ptr, int32 y, fp64 r)")
+    n_x, n = xr[0].numel() - 1, xr[1].numel()
+    if n_x < 1 or xr[2].numel() != n or w.numel() != int(n_y):
+        raise ValueError("similarity_sparse: %d rows, %d y, %d r, %d weights for n_y = %d"
+                         % (n_x, n, xr[2].numel(), w.numel(), n_y))
+    csr_check(xr, n_y)
+    dev = xr[2].device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        sim = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
+        acc = {}
+        if accumulators:
+            acc["freq"] = torch.empty((n_x, n_x), dtype=torch.int32, device=dev)
+            for nm in (("prods", "sqi", "sqj") if name == "cosine" else ("sq_diff",)):
+                acc[nm] = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
+        _lib.check(lib.n2v_eccknn_sim_sparse(_lib.ptr(xr[0]), _lib.ptr(xr[1]) if n else None, _lib.ptr(xr[2]) if n else None,
+                                             n_x, int(n_y), n, _lib.ptr(w), _METHOD[name], int(min_support), _lib.ptr(sim),
+                                             _lib.ptr(acc.get("freq")), _lib.ptr(acc.get("prods")), _lib.ptr(acc.get("sqi")),
+                                             _lib.ptr(acc.get("sqj")), _lib.ptr(acc.get("sq_diff")), _lib.stream_ptr(dev)))
+    return (sim, acc) if accumulators else sim
+
+
 def estimate_batch(sim, yr, qx, qy, k, min_k):
     """(est fp64, actual_k int32, impossible uint8) device tensors.  yr: device CSR triple (ptr int64, x int32, r fp64);
     qx / qy: int32 device tensors, -1 = unknown."""
@@ -201,6 +277,9 @@ class EccenKNN:
         if self.min_k < 1:
             raise ValueError("min_k %d < 1" % self.min_k)
         self.name = name
+        self.form = self.sim_options.get("form", "auto")
+        if self.form not in FORMS:
+            raise ValueError("eccknn: form %r, allowed values are %s" % (self.form, ", ".join(FORMS)))
 
     def _weights(self, trainset, weights):
         user_based = self.sim_options["user_based"]
@@ -226,8 +305,14 @@ class EccenKNN:
         self.n_x, self.n_y = (ts.n_users, ts.n_items) if user_based else (ts.n_items, ts.n_users)
         self.trainset = ts
         to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-        dense, mask = densify(to(x, torch.int32), to(y, torch.int32), to(ts.r, torch.float64), self.n_x, self.n_y)
-        self.sim = similarity(dense, mask, to(w, torch.float64), self.name, self.sim_options.get("min_support", 1))
+        form = choose_form(self.n_x, self.n_y, self.form, int(_lib.load().n2v_eccknn_max_dense()))
+        dx, dy, dr, dw = to(x, torch.int32), to(y, torch.int32), to(ts.r, torch.float64), to(w, torch.float64)
+        if form == "dense":
+            dense, mask = densify(dx, dy, dr, self.n_x, self.n_y)
+            self.sim = similarity(dense, mask, dw, self.name, self.sim_options.get("min_support", 1))
+        else:
+            self.sim = similarity_sparse(csr_by_x(dx, dy, dr, self.n_x, self.n_y), dw, self.n_y, self.name,
+                                         self.sim_options.get("min_support", 1))
         self.yr = (to(yr[0], torch.int64), to(yr[1], torch.int32), to(yr[2], torch.float64))
         return self
 
