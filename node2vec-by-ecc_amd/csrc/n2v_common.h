@@ -30,6 +30,11 @@ inline int check_launch(const char* what) {
 
 inline unsigned grid_for(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 
+// resident 4-wave workgroups per CU of a kernel bound by its LDS (160 KiB per CU), at most 8
+constexpr int wg_per_cu(int lds_bytes_per_wg) {
+    return 160 * 1024 / lds_bytes_per_wg < 8 ? 160 * 1024 / lds_bytes_per_wg : 8;
+}
+
 // ---- device helpers shared by the walk and table kernels -----------------------------------------
 
 // Philox4x32-10 (Salmon et al., SC'11): key = seed, counter = (c0, c1, c2, c3).  The one copy behind every stream
@@ -66,21 +71,6 @@ __device__ __forceinline__ void philox_uniforms(uint64_t seed, uint64_t walk, ui
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int64_t uni64(int64_t v) {
     return ((int64_t)uni((int)(v >> 32)) << 32) | (uint32_t)uni((int)v);
-}
-
-// Fat slot {q, rec_k, rec_J} (include/n2v_hip.h, n2v_fat_slot): q[k] and the walk records of both outcomes of the draw,
-// neighbour k and neighbour J[k].  rec = {slot_lo, base, dst, deg_hi}; the row base is not needed any more.
-__device__ __forceinline__ void write_fat_slot(n2v_fat_slot* out, double q, const n2v_edge_rec* rec_k,
-                                               const n2v_edge_rec* rec_J) {
-    const uint4 ra = *reinterpret_cast<const uint4*>(rec_k);
-    const uint4 rb = *reinterpret_cast<const uint4*>(rec_J);
-    uint4 lo, hi;
-    lo.x = (uint32_t)__double2loint(q); lo.y = (uint32_t)__double2hiint(q);
-    lo.z = ra.x; lo.w = ra.w;
-    hi.x = ra.z; hi.y = rb.x; hi.z = rb.w; hi.w = rb.z;
-    uint4* o = reinterpret_cast<uint4*>(out);
-    o[0] = lo;
-    o[1] = hi;
 }
 
 // G.has_edge(u, v) on the sorted CSR (src/node2vec.py:145): binary search of v in row u.

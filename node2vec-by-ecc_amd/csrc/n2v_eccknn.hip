@@ -20,18 +20,18 @@
 //                    shared with sim_kernel.  csr_check_kernel (integers only) names a malformed CSR; the similarity
 //                    kernel itself clamps every row range to [0, n] and never indexes w with a y outside [0, n_y).
 //   estimate_kernel  one wavefront per query: gathers sim[x, x2] over the raters of y, keeps the best k of them in a
-//                    sorted LDS list under the one order of n2v_rec.hip (higher sim first, equal sims by list position,
+//                    sorted LDS list under the one order of n2v_rank.h (higher sim first, equal sims by list position,
 //                    -0.0 ties +0.0, NaN below everything) and sums in rank order.
 //   predict_kernel   one workgroup: global-mean fallback, clip to the rating scale, and the squared errors added one
 //                    after the other in query order (rmse).
 #include "n2v_common.h"
 #include "n2v_sim.h"
+#include "n2v_rank.h"
 
 namespace {
 
 constexpr int TB = 64;            // rows / columns of a tile
 constexpr int YC = 32;            // values of y staged per barrier
-constexpr int POS_NONE = 0x7fffffff;
 constexpr int64_t MAX_DENSE = (int64_t)1 << 31;   // elements of the dense matrix (16 GiB of fp64)
 
 // ---- densify ----------------------------------------------------------------------------------------------------------
@@ -326,45 +326,7 @@ __global__ void __launch_bounds__(256) csr_check_kernel(const int64_t* __restric
 
 // ---- estimate ---------------------------------------------------------------------------------------------------------
 
-// order-preserving key: larger double <=> larger key; NaN lowest; -0.0 and +0.0 share a key (order_key of n2v_rec.hip)
-__device__ __forceinline__ uint64_t order_key(double v) {
-    if (v != v) return 0ull;
-    if (v == 0.0) return 0x8000000000000000ull;
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-// (ka, pa) comes before (kb, pb) in the ranking
-__device__ __forceinline__ bool beats(uint64_t ka, int pa, uint64_t kb, int pb) {
-    return ka > kb || (ka == kb && pa < pb);
-}
-
-// Insert (cs, cp) into the sorted list ls/lp of k entries (the last one falls out), all 64 lanes together: entry i takes
-// the candidate or entry i - 1 when it does not come before the candidate.  Chunks of 64 entries from the top down, so an
-// entry is read before the chunk below it is written.  tk/tp receive the new last entry.  (list_insert of n2v_rec.hip.)
-__device__ __forceinline__ void list_insert(double* ls, int32_t* lp, int k, double cs, int cp, uint64_t ck, int lane,
-                                            uint64_t& tk, int& tp) {
-    const int top = ((k - 1) >> 6) << 6;
-    for (int base = top; base >= 0; base -= 64) {
-        const int i = base + lane;
-        double si = __builtin_nan(""), sm = si;
-        int pi = POS_NONE, pm = POS_NONE;
-        if (i < k) {
-            si = ls[i]; pi = lp[i];
-            if (i > 0) { sm = ls[i - 1]; pm = lp[i - 1]; }
-        }
-        const bool keep = beats(order_key(si), pi, ck, cp);
-        const bool prev_before = i == 0 || beats(order_key(sm), pm, ck, cp);
-        const double ns = keep ? si : (prev_before ? cs : sm);
-        const int np = keep ? pi : (prev_before ? cp : pm);
-        if (i < k && !keep) { ls[i] = ns; lp[i] = np; }
-        if (base == top) {
-            const int last = (k - 1) & 63;
-            tk = order_key(__shfl(ns, last, 64));
-            tp = __shfl(np, last, 64);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // the stores are seen by this wavefront's next loads
-}
+using n2v::POS_NONE, n2v::order_key, n2v::beats, n2v::list_insert;   // n2v_rank.h
 
 struct EstArgs {
     const double* sim; int64_t n_x; const int64_t* yr_ptr; const int32_t* yr_x; const double* yr_r; int64_t n_y;

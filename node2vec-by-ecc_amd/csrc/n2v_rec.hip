@@ -8,12 +8,11 @@
 //                     wavefront folds the 32 rows it owns into their running best-k lists before the next tile;
 //   rec_merge_kernel  one wavefront per user merges the S segment lists into the final one;
 //   rec_metrics_kernel one lane per user, the five numbers of :361-406.
-// The order is ONE total order on (score, item position): higher score first, among equal scores the lower
-// position (Python's stable sort on the caller's item list); -0.0 ties +0.0, NaN is below everything.  Every
-// comparison in this file is beats() on that order, so neither the tile size, the segment count nor the place where a
-// tie group meets a border can change the result.
+// Items are ranked by the one total order of n2v_rank.h on (score, item position in the caller's list); every
+// comparison in this file is its beats().
 #include "n2v_common.h"
 #include "n2v_bine.h"
+#include "n2v_rank.h"
 
 namespace {
 
@@ -27,19 +26,8 @@ constexpr int KC = 16;           // k-chunk staged per barrier
 constexpr int LP = KC + 1;       // LDS pitch of a staged row (doubles): the 4 k-groups of an operand read spread over the banks
 constexpr int SP = BN + 16;      // LDS pitch of a score row: the 4 rows one accumulator register writes land 32 banks apart
 constexpr int MAX_SEG = 64;      // segments per user: one lane each in the merge
-constexpr int POS_NONE = 0x7fffffff;
 
-// order-preserving key: larger double <=> larger key; NaN lowest; -0.0 and +0.0 share a key (order_key of n2v_sim.hip)
-__device__ __forceinline__ uint64_t order_key(double v) {
-    if (v != v) return 0ull;
-    if (v == 0.0) return 0x8000000000000000ull;
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-// (ka, pa) comes before (kb, pb) in the ranking
-__device__ __forceinline__ bool beats(uint64_t ka, int pa, uint64_t kb, int pb) {
-    return ka > kb || (ka == kb && pa < pb);
-}
+using n2v::POS_NONE, n2v::order_key, n2v::beats, n2v::list_insert;   // n2v_rank.h
 
 struct RecArgs {
     const double* emb; int64_t n_rows; int dim; int stride;
@@ -48,34 +36,6 @@ struct RecArgs {
     int k; int S;
     double* part_score; int32_t* part_pos;
 };
-
-// Insert (cs, cp) into the sorted list ls/lp of k entries (the last one falls out), all 64 lanes together: entry i takes
-// the candidate or entry i - 1 when it does not come before the candidate.  Chunks of 64 entries from the top down, so an
-// entry is read before the chunk below it is written.  tk/tp receive the new last entry.
-__device__ __forceinline__ void list_insert(double* ls, int32_t* lp, int k, double cs, int cp, uint64_t ck, int lane,
-                                            uint64_t& tk, int& tp) {
-    const int top = ((k - 1) >> 6) << 6;
-    for (int base = top; base >= 0; base -= 64) {
-        const int i = base + lane;
-        double si = __builtin_nan(""), sm = si;
-        int pi = POS_NONE, pm = POS_NONE;
-        if (i < k) {
-            si = ls[i]; pi = lp[i];
-            if (i > 0) { sm = ls[i - 1]; pm = lp[i - 1]; }
-        }
-        const bool keep = beats(order_key(si), pi, ck, cp);
-        const bool prev_before = i == 0 || beats(order_key(sm), pm, ck, cp);
-        const double ns = keep ? si : (prev_before ? cs : sm);
-        const int np = keep ? pi : (prev_before ? cp : pm);
-        if (i < k && !keep) { ls[i] = ns; lp[i] = np; }
-        if (base == top) {
-            const int last = (k - 1) & 63;
-            tk = order_key(__shfl(ns, last, 64));
-            tp = __shfl(np, last, 64);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // the stores are seen by this wavefront's next loads
-}
 
 __global__ void __launch_bounds__(256) rec_topn_kernel(RecArgs a) {
     __shared__ double As[BM][LP];

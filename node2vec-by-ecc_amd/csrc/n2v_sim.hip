@@ -12,6 +12,7 @@
 // with a CPU restatement); the Jensen-Shannon form is not a contraction and stays on the vector tile kernel.
 #include "n2v_common.h"
 #include "n2v_sim.h"
+#include "n2v_rank.h"
 
 #include <cstdlib>
 
@@ -286,13 +287,7 @@ rows_fill_kernel(const float* __restrict__ scores, int64_t n_cols, int64_t ld, f
     }
 }
 
-// order-preserving key: larger float <=> larger key; NaN lowest; -0.0 and +0.0 compare equal and share a key
-__device__ __forceinline__ uint32_t order_key(float v) {
-    if (v != v) return 0u;
-    if (v == 0.f) return 0x80000000u;
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+using n2v::order_key;   // n2v_rank.h
 
 __global__ void __launch_bounds__(256)
 rows_topk_kernel(const float* __restrict__ scores, int64_t n_cols, int64_t ld, int k, int32_t* __restrict__ cols,

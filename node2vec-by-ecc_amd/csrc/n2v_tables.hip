@@ -18,7 +18,7 @@
 // One lane per table (the builder this one replaced) touched every 16-B slot ~8 times with uncoalesced accesses and sat
 // on the chip's random-request rate (tools/lab: ~5e10 64-B requests/s): 0.33 s for the 1.83e9 slots of C3.
 // Compile with -ffp-contract=off (separately rounded divide / multiply / adds as in the reference).
-#include "n2v_common.h"
+#include "n2v_walk_step.h"
 #include "n2v_wave_table.h"
 
 namespace {
@@ -155,8 +155,7 @@ __global__ void __launch_bounds__(256) edge_tables_wave_kernel(TabArgs a) {
 }  // namespace
 
 namespace {
-constexpr int kLdsPerWg = 4 * (kLdsSlots * 16 + n2v::kFeed * 8 + n2v::kRowCache * 4);
-constexpr int kWgPerCu = (160 * 1024 / kLdsPerWg) < 8 ? (160 * 1024 / kLdsPerWg) : 8;
+constexpr int kWgPerCu = n2v::wg_per_cu(4 * (kLdsSlots * 16 + n2v::kFeed * 8 + n2v::kRowCache * 4));
 constexpr int64_t kMaxBlocks = 256 * kWgPerCu;     // every resident workgroup slot of the chip, once: tables are handed out
 static_assert(kLdsSlots * 16 >= 2048, "the output queue of the large tables overlays the LDS table slice");
 inline int64_t scratch_k(int64_t max_degree) { return max_degree <= kLdsSlots ? 0 : (max_degree + 15) / 16 * 16; }

@@ -13,7 +13,7 @@
 // never straddles a 64-B line, so a step is one request.  Memory: 32 B per alias slot, i.e.
 // 2x the thin tables (C3: 58.5 GB) — the reason this layout only makes sense on a 288 GB part.
 // The tables are written in this layout by n2v_build_edge_tables_wave (same bits as the thin, reference-exact tables).
-#include "n2v_common.h"
+#include "n2v_walk_step.h"
 
 namespace {
 
@@ -21,9 +21,7 @@ struct FatArgs {
     const int64_t* row_ptr;
     const n2v_fat_slot* node_fat;
     const n2v_fat_slot* fat;
-    const int32_t* starts;
-    int64_t n_starts, pos_begin, pos_count, round_begin, n_local;
-    int32_t L;
+    n2v::WalkShard sh;
     const double* uniforms;
     const int64_t* walk_uoff;
     int64_t uoff_round_stride;
@@ -56,47 +54,37 @@ __device__ __forceinline__ uint4 dpp_swap1(uint4 v) {
 template <int RNG, int BURST>
 __global__ void __launch_bounds__(256) walk_fat2_kernel(FatArgs a) {
     const int64_t lw = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool mine = lw < a.n_local;          // the last pair may have one lane without a walk: it still helps its partner
-    const int32_t L = a.L;
-    int64_t rl = 0, pl = 0;
-    if (mine) { rl = lw / a.pos_count; pl = lw - rl * a.pos_count; }
-    const uint64_t gw = (uint64_t)((a.round_begin + rl) * a.n_starts + a.pos_begin + pl);
-    const int32_t cur0 = mine ? a.starts[a.pos_begin + pl] : 0;
+    const bool mine = lw < a.sh.n_local;       // the last pair may have one lane without a walk: it still helps its partner
+    const int32_t L = a.sh.L;
+    const n2v::WalkId w = n2v::walk_id(a.sh, lw, mine);
     int64_t b0 = 0, b1 = 0;
-    if (mine) { b0 = a.row_ptr[cur0]; b1 = a.row_ptr[cur0 + 1]; }
+    if (mine) { b0 = a.row_ptr[w.start]; b1 = a.row_ptr[w.start + 1]; }
     const n2v_fat_slot* tab = a.node_fat + b0;  // first step: node table (:69-70)
     uint32_t K = (uint32_t)(b1 - b0);
     int32_t len = 1;
     uint32_t t = 0;
     constexpr bool kBuf = RNG == N2V_RNG_UNIFORMS || RNG == N2V_RNG_UNIFORMS_TILED;
-    constexpr int kStride = RNG == N2V_RNG_UNIFORMS_TILED ? 128 : 2;     // doubles between a walk's consecutive steps
     const double* up = nullptr;
     double2 unext = make_double2(0.0, 0.0);
     if (kBuf && mine && K != 0 && L > 1) {
-        const int64_t o = !a.walk_uoff ? (int64_t)2 * (L - 1) * lw
-                          : a.uoff_round_stride > 0 ? a.walk_uoff[pl] + rl * a.uoff_round_stride : a.walk_uoff[lw];
+        up = n2v::uniform_base(a.uniforms, a.sh, w, lw, a.walk_uoff, a.uoff_round_stride);
         if (RNG == N2V_RNG_UNIFORMS_TILED) {
-            const uint64_t slot = (uint64_t)o / (uint64_t)(2 * (L - 1));        // which of the active walks this one is
-            up = a.uniforms + 2 * ((slot >> 6) * (uint64_t)(L - 1) * 64 + (slot & 63));
+            up = n2v::uniform_base_tiled(a.uniforms, up - a.uniforms, L);
             unext = *reinterpret_cast<const double2*>(up);
-        } else {
-            up = a.uniforms + o;
         }
     }
     const int odd = threadIdx.x & 1;
 
-    auto step = [&]() -> int32_t {
+    // step takes its invariants by value (emit_walk)
+    auto step = [&, seed = a.seed, fat = a.fat, w, mine, odd, L]() -> int32_t {
         const bool live = mine && K != 0;       // dead end: stop, consume nothing (:76-77)
         double u1 = 0.0, u2 = 0.0;
         if (live) {
-            if (RNG == N2V_RNG_UNIFORMS_TILED) {
+            if (RNG == N2V_RNG_UNIFORMS_TILED) {   // the next step's pair is requested before this step's slot
                 u1 = unext.x; u2 = unext.y;
-                if ((int32_t)t + 2 < L) unext = *reinterpret_cast<const double2*>(up + (int64_t)kStride * (t + 1));
-            } else if (RNG == N2V_RNG_UNIFORMS) {
-                const double2 u = *reinterpret_cast<const double2*>(up + (int64_t)kStride * t);
-                u1 = u.x; u2 = u.y;
+                if ((int32_t)t + 2 < L) unext = *reinterpret_cast<const double2*>(up + (int64_t)n2v::kTiledStride * (t + 1));
             } else {
-                n2v::philox_uniforms(a.seed, gw, t, u1, u2);
+                n2v::step_uniforms(RNG, up, seed, w.gw, t, u1, u2);
             }
             ++t;
         }
@@ -108,43 +96,15 @@ __global__ void __launch_bounds__(256) walk_fat2_kernel(FatArgs a) {
         if (even_addr) x = *reinterpret_cast<const uint4*>(even_addr + (odd ? 16 : 0));   // the pair reads 32 contiguous bytes
         if (odd_addr) y = *reinterpret_cast<const uint4*>(odd_addr + (odd ? 16 : 0));
         const uint4 got = dpp_swap1(odd ? x : y);
-        const uint4 lo = odd ? got : x;   // {q.lo, q.hi, keep.slot_lo, keep.deg_hi}
-        const uint4 hi = odd ? y : got;   // {keep.dst, alias.slot_lo, alias.deg_hi, alias.dst}
         if (!live) return -1;
-        const double q = __hiloint2double((int)lo.y, (int)lo.x);
-        const bool keep = u2 < q;  // :278
-        const uint32_t slot_lo = keep ? lo.z : hi.y;
-        const uint32_t deg_hi = keep ? lo.w : hi.z;
-        const uint32_t dst = keep ? hi.x : hi.w;
-        tab = a.fat + (((uint64_t)(deg_hi >> 24) << 32) | slot_lo);
-        K = deg_hi & 0xFFFFFFu;
+        const n2v::WalkRec r = n2v::decode_fat(odd ? got : x, odd ? y : got, u2);   // the slot's lo and hi halves
+        tab = fat + r.tbl;
+        K = r.K;
         ++len;
-        return (int32_t)dst;
+        return r.dst;
     };
 
-    int32_t* out = a.walks + lw * (int64_t)L;
-    int32_t buf[BURST];
-    buf[0] = cur0;
-#pragma unroll
-    for (int i = 1; i < BURST; ++i) buf[i] = step();
-    for (int32_t g = 0;;) {
-        if (mine) {
-            if (BURST >= 4) {
-#pragma unroll
-                for (int i = 0; i + 3 < BURST; i += 4) {
-                    typedef int v4i __attribute__((ext_vector_type(4)));
-                    v4i v = {buf[i], buf[i + 1], buf[i + 2], buf[i + 3]};
-                    *reinterpret_cast<v4i*>(out + g + i) = v;
-                }
-            } else {
-                out[g] = buf[0];
-            }
-        }
-        g += BURST;
-        if (g >= L) break;
-#pragma unroll
-        for (int i = 0; i < BURST; ++i) buf[i] = step();
-    }
+    n2v::emit_walk<BURST>(a.walks + lw * (int64_t)L, L, mine, w.start, step);
     if (mine) a.lens[lw] = len;
 }
 
@@ -189,11 +149,12 @@ extern "C" int n2v_walk_fat(const int64_t* row_ptr, const n2v_fat_slot* node_fat
                             int64_t round_begin, int64_t round_count, int32_t walk_length, int32_t rng_mode,
                             const double* uniforms, const int64_t* walk_uoff, int64_t uoff_round_stride, uint64_t seed,
                             int32_t* walks, int32_t* lens, void* stream) {
-    if (pos_count < 0 || round_count < 0 || pos_begin < 0 || round_begin < 0 || walk_length < 1 ||
-        pos_begin + pos_count > n_starts || uoff_round_stride < 0)
-        return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: bad shard or length");
-    const int64_t n_local = pos_count * round_count;
-    if (n_local == 0) return N2V_OK;
+    n2v::WalkShard sh;
+    if (const int rc = n2v::check_shard("n2v_walk_fat", starts, n_starts, pos_begin, pos_count, round_begin, round_count,
+                                        walk_length, 1, &sh))
+        return rc;
+    if (uoff_round_stride < 0) return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: negative uoff_round_stride");
+    if (sh.n_local == 0) return N2V_OK;
     if (!row_ptr || !node_fat || !starts || !lens || !walks || (walk_length > 1 && !fat))
         return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: null pointer");
     if (rng_mode != N2V_RNG_UNIFORMS && rng_mode != N2V_RNG_PHILOX && rng_mode != N2V_RNG_UNIFORMS_TILED)
@@ -202,23 +163,17 @@ extern "C" int n2v_walk_fat(const int64_t* row_ptr, const n2v_fat_slot* node_fat
         return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: parity mode needs a uniform buffer");
     if (((uintptr_t)uniforms & 15) != 0 || ((uintptr_t)node_fat & 31) != 0 || ((uintptr_t)fat & 31) != 0)
         return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: misaligned buffer");
-    if (n_local > (int64_t)0x7fffffff * 256) return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: too many walks in one call");
-    FatArgs a{row_ptr, node_fat, fat, starts, n_starts, pos_begin, pos_count, round_begin, n_local, walk_length,
-              uniforms, walk_uoff, uoff_round_stride, seed, walks, lens};
-    const dim3 grid(n2v::grid_for(n_local, 256)), block(256);
+    if (sh.n_local > (int64_t)0x7fffffff * 256) return n2v::fail(N2V_ERR_INVALID, "n2v_walk_fat: too many walks in one call");
+    FatArgs a{row_ptr, node_fat, fat, sh, uniforms, walk_uoff, uoff_round_stride, seed, walks, lens};
+    const dim3 grid(n2v::grid_for(sh.n_local, 256)), block(256);
     hipStream_t st = (hipStream_t)stream;
     // whole 64-B output lines when the row length allows it, 16-B pieces or single ids otherwise
     const int burst = (walk_length % 16 == 0 && ((uintptr_t)walks & 63) == 0) ? 16
                       : (walk_length % 4 == 0 && ((uintptr_t)walks & 15) == 0) ? 4 : 1;
-#define N2V_LAUNCH_FAT(RNG)                                                                                  \
-    do {                                                                                                     \
-        if (burst == 16) hipLaunchKernelGGL((walk_fat2_kernel<RNG, 16>), grid, block, 0, st, a);             \
-        else if (burst == 4) hipLaunchKernelGGL((walk_fat2_kernel<RNG, 4>), grid, block, 0, st, a);          \
-        else hipLaunchKernelGGL((walk_fat2_kernel<RNG, 1>), grid, block, 0, st, a);                          \
-    } while (0)
-    if (rng_mode == N2V_RNG_UNIFORMS) N2V_LAUNCH_FAT(N2V_RNG_UNIFORMS);
-    else if (rng_mode == N2V_RNG_UNIFORMS_TILED) N2V_LAUNCH_FAT(N2V_RNG_UNIFORMS_TILED);
-    else N2V_LAUNCH_FAT(N2V_RNG_PHILOX);
-#undef N2V_LAUNCH_FAT
+    n2v::dispatch<N2V_RNG_UNIFORMS, N2V_RNG_UNIFORMS_TILED, N2V_RNG_PHILOX>(rng_mode, [&](auto rng) {
+        n2v::dispatch<16, 4, 1>(burst, [&](auto b) {
+            hipLaunchKernelGGL((walk_fat2_kernel<decltype(rng)::value, decltype(b)::value>), grid, block, 0, st, a);
+        });
+    });
     return n2v::check_launch("n2v_walk_fat");
 }

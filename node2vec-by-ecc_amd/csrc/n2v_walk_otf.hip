@@ -16,7 +16,7 @@
 // The table lives in the wave's slice of LDS while K <= kLdsSlots (256) and in a per-wave global
 // scratch row of max_degree slots otherwise.  Serial chains of many waves interleave on a
 // SIMD, so throughput comes from occupancy; -ffp-contract=off keeps every rounding separate.
-#include "n2v_common.h"
+#include "n2v_walk_step.h"
 #include "n2v_wave_table.h"
 
 namespace {
@@ -25,17 +25,14 @@ namespace {
 // C3 2.1 -> 2.6e8 steps/s vs 512 slots / 4 workgroups; 128: 2.5e8
 constexpr int kLdsSlots = 256;
 constexpr int kOtfRow = 256;   // two row buffers per wave: the row of `prev` (searched) and the row of `cur` (it is the next step's `prev`)
-constexpr int kLdsPerWg = 4 * (kLdsSlots * 16 + n2v::kFeed * 8 + 2 * kOtfRow * 4);
-constexpr int kWgPerCu = (160 * 1024 / kLdsPerWg) < 8 ? (160 * 1024 / kLdsPerWg) : 8;
+constexpr int kWgPerCu = n2v::wg_per_cu(4 * (kLdsSlots * 16 + n2v::kFeed * 8 + 2 * kOtfRow * 4));
 
 using n2v::uni;
 using n2v::uni64;
 
 struct OtfArgs {
     n2v::RowCtx g;      // CSR, p, q, symmetric
-    const int32_t* starts;
-    int64_t n_starts, pos_begin, pos_count, round_begin, n_local;
-    int32_t L;
+    n2v::WalkShard sh;
     int32_t rng_mode;
     const double* uniforms;
     const int64_t* walk_uoff;
@@ -154,16 +151,14 @@ struct OtfWave {
 template <bool HYBRID, int RULE>
 __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
     N2V_OTF_WAVE_STATE(W);
-    const int32_t L = a.L;
+    const int32_t L = a.sh.L;
 
-    for (int64_t lw = wave_global; lw < a.n_local; lw += n_waves) {
-        const int64_t rl = lw / a.pos_count, pl = lw - rl * a.pos_count;
-        const uint64_t gw = (uint64_t)((a.round_begin + rl) * a.n_starts + a.pos_begin + pl);
-        int32_t cur = uni(a.starts[a.pos_begin + pl]), prev = -1;
+    for (int64_t lw = wave_global; lw < a.sh.n_local; lw += n_waves) {
+        const n2v::WalkId w = n2v::walk_id(a.sh, lw);
+        int32_t cur = uni(w.start), prev = -1;
         int32_t* out = a.walks + lw * (int64_t)L;
         const double* up = nullptr;
-        if (a.rng_mode == N2V_RNG_UNIFORMS)
-            up = a.uniforms + (a.walk_uoff ? a.walk_uoff[lw] : (int64_t)2 * (L - 1) * lw);
+        if (a.rng_mode == N2V_RNG_UNIFORMS) up = n2v::uniform_base(a.uniforms, a.sh, w, lw, a.walk_uoff);
         if (lane == 0) out[0] = cur;
         if (RULE == n2v::kRulePop) W.ws.plain_row = uni((int)a.g.plain[cur]);   // read by the first step only (src < 0)
         int32_t len = 1;
@@ -180,21 +175,16 @@ __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
             }
             if (K == 0) break;  // dead end (:50-51)
             double u1, u2;
-            const uint32_t t = (uint32_t)(len - 1);
-            if (a.rng_mode == N2V_RNG_UNIFORMS) { u1 = up[2 * (int64_t)t]; u2 = up[2 * (int64_t)t + 1]; }
-            else n2v::philox_uniforms(a.seed, gw, t, u1, u2);
+            n2v::step_uniforms(a.rng_mode, up, a.seed, w.gw, (uint32_t)(len - 1), u1, u2);
             const int kk = (int)(u1 * (double)K);  // :277
             if (HYBRID && tbl != (uint64_t)N2V_NO_TABLE) {
                 // stored table: one 32-B slot (every lane reads the same address), both outcomes' records inside
                 const uint4* sp = reinterpret_cast<const uint4*>(arr + tbl + (uint64_t)kk);
-                const uint4 lo = sp[0], hi = sp[1];
-                const double qk = __hiloint2double((int)lo.y, (int)lo.x);
-                const bool keep = u2 < qk;  // :278
-                const uint32_t slot_lo = keep ? lo.z : hi.y, deg_hi = keep ? lo.w : hi.z, dst = keep ? hi.x : hi.w;
+                const n2v::WalkRec r = n2v::decode_fat(sp[0], sp[1], u2);
                 prev = cur;
-                cur = uni((int32_t)dst);
-                tbl = ((uint64_t)(uint32_t)uni((int)(deg_hi >> 24)) << 32) | (uint32_t)uni((int)slot_lo);
-                K = uni((int)(deg_hi & 0xFFFFFFu));
+                cur = uni(r.dst);
+                tbl = (uint64_t)uni64((int64_t)r.tbl);
+                K = uni((int)r.K);
                 arr = a.fat;
             } else {
                 const int pick = W.pick<!HYBRID, RULE>(a, prev, base, K, kk, u2, lane, true);
@@ -202,10 +192,10 @@ __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
                 prev = cur;
                 W.set_cached(prev);
                 if (HYBRID) {
-                    const uint4 r = *reinterpret_cast<const uint4*>(a.recs + base + pick);   // {slot_lo, base, dst, deg_hi}
-                    cur = uni((int32_t)r.z);
-                    tbl = ((uint64_t)(uint32_t)uni((int)(r.w >> 24)) << 32) | (uint32_t)uni((int)r.x);
-                    K = uni((int)(r.w & 0xFFFFFFu));
+                    const n2v::WalkRec r = n2v::decode_rec(*reinterpret_cast<const uint4*>(a.recs + base + pick));
+                    cur = uni(r.dst);
+                    tbl = (uint64_t)uni64((int64_t)r.tbl);
+                    K = uni((int)r.K);
                     arr = a.fat;
                 } else {
                     cur = W.picked_node;
@@ -229,14 +219,12 @@ __global__ void __launch_bounds__(256) walk_otf_kernel(OtfArgs a) {
 template <int RNG, int BURST>
 __global__ void __launch_bounds__(256) walk_hybrid_lanes_kernel(OtfArgs a) {
     N2V_OTF_WAVE_STATE(W);
-    const int32_t L = a.L;
-    for (int64_t lw0 = wave_global * 64; lw0 < a.n_local; lw0 += n_waves * 64) {
+    const int32_t L = a.sh.L;
+    for (int64_t lw0 = wave_global * 64; lw0 < a.sh.n_local; lw0 += n_waves * 64) {
         const int64_t lw = lw0 + lane;
-        const bool mine = lw < a.n_local;
-        int64_t rl = 0, pl = 0;
-        if (mine) { rl = lw / a.pos_count; pl = lw - rl * a.pos_count; }
-        const uint64_t gw = (uint64_t)((a.round_begin + rl) * a.n_starts + a.pos_begin + pl);
-        int32_t cur = mine ? a.starts[a.pos_begin + pl] : 0, prev = -1;
+        const bool mine = lw < a.sh.n_local;
+        const n2v::WalkId w = n2v::walk_id(a.sh, lw, mine);
+        int32_t cur = w.start, prev = -1;
         int64_t b0 = 0, b1 = 0;
         if (mine) { b0 = a.g.row_ptr[cur]; b1 = a.g.row_ptr[cur + 1]; }
         const n2v_fat_slot* arr = a.node_fat;          // first step: the node table (:69-70), always stored
@@ -246,24 +234,22 @@ __global__ void __launch_bounds__(256) walk_hybrid_lanes_kernel(OtfArgs a) {
         uint32_t t = 0;
         bool failed = false;
         const double* up = nullptr;
-        if (RNG == N2V_RNG_UNIFORMS && mine) up = a.uniforms + (a.walk_uoff ? a.walk_uoff[lw] : (int64_t)2 * (L - 1) * lw);
+        if (RNG == N2V_RNG_UNIFORMS && mine) up = n2v::uniform_base(a.uniforms, a.sh, w, lw, a.walk_uoff);
 
-        auto step = [&]() -> int32_t {
+        // step takes its invariants by value (emit_walk)
+        auto step = [&, seed = a.seed, w, mine, lane]() -> int32_t {
             const bool live = mine && K != 0 && !failed;   // dead end: stop, consume nothing (:76-77)
             double u1 = 0.0, u2 = 0.0;
             if (live) {
-                if (RNG == N2V_RNG_UNIFORMS) { u1 = up[2 * (int64_t)t]; u2 = up[2 * (int64_t)t + 1]; }
-                else n2v::philox_uniforms(a.seed, gw, t, u1, u2);
+                n2v::step_uniforms(RNG, up, seed, w.gw, t, u1, u2);
                 ++t;
             }
             const uint32_t kk = (uint32_t)(u1 * (double)K);  // :277
             const bool stored = live && tbl != (uint64_t)N2V_NO_TABLE;
-            uint32_t slot_lo = 0, deg_hi = 0, dst = 0;
+            uint4 rec = make_uint4(0, 0, 0, 0);   // the walk record of the neighbour the step moves to
             if (stored) {
                 const uint4* sp = reinterpret_cast<const uint4*>(arr + tbl + (uint64_t)kk);
-                const uint4 lo = sp[0], hi = sp[1];
-                const bool keep = u2 < __hiloint2double((int)lo.y, (int)lo.x);  // :278
-                slot_lo = keep ? lo.z : hi.y; deg_hi = keep ? lo.w : hi.z; dst = keep ? hi.x : hi.w;
+                rec = n2v::fat_pick(sp[0], sp[1], u2);
             }
             unsigned long long need = __ballot(live && !stored);
             while (need != 0ULL) {
@@ -275,42 +261,21 @@ __global__ void __launch_bounds__(256) walk_hybrid_lanes_kernel(OtfArgs a) {
                 const int64_t base = uni64(a.g.row_ptr[s_cur]);
                 const int pk = W.pick<false, n2v::kRuleNone>(a, s_prev, base, s_K, s_kk, s_u2, lane, false);
                 if (pk < 0) { if (lane == j) failed = true; continue; }
-                const uint4 r = *reinterpret_cast<const uint4*>(a.recs + base + pk);   // {slot_lo, base, dst, deg_hi}
-                if (lane == j) { slot_lo = r.x; deg_hi = r.w; dst = r.z; }
+                const uint4 r = *reinterpret_cast<const uint4*>(a.recs + base + pk);
+                if (lane == j) rec = make_uint4(r.x, 0u, r.z, r.w);   // no row base, as from a fat slot: one register less
             }
             if (!live || failed) return -1;
+            const n2v::WalkRec r = n2v::decode_rec(rec);
             prev = cur;
-            cur = (int32_t)dst;
-            tbl = ((uint64_t)(deg_hi >> 24) << 32) | slot_lo;
-            K = deg_hi & 0xFFFFFFu;
+            cur = r.dst;
+            tbl = r.tbl;
+            K = r.K;
             arr = a.fat;
             ++len;
             return cur;
         };
 
-        int32_t* out = a.walks + lw * (int64_t)L;
-        int32_t buf[BURST];
-        buf[0] = cur;
-#pragma unroll
-        for (int i = 1; i < BURST; ++i) buf[i] = step();
-        for (int32_t g = 0;;) {
-            if (mine) {
-                if (BURST >= 4) {
-#pragma unroll
-                    for (int i = 0; i + 3 < BURST; i += 4) {
-                        typedef int v4i __attribute__((ext_vector_type(4)));
-                        v4i v = {buf[i], buf[i + 1], buf[i + 2], buf[i + 3]};
-                        *reinterpret_cast<v4i*>(out + g + i) = v;
-                    }
-                } else {
-                    out[g] = buf[0];
-                }
-            }
-            g += BURST;
-            if (g >= L) break;
-#pragma unroll
-            for (int i = 0; i < BURST; ++i) buf[i] = step();
-        }
+        n2v::emit_walk<BURST>(a.walks + lw * (int64_t)L, L, mine, cur, step);
         if (mine) a.lens[lw] = len;
         if (__ballot(failed) != 0ULL && lane == 0) atomicOr(a.status, N2V_STATUS_ZERO_NORM);
     }
@@ -326,10 +291,11 @@ int launch_otf(const char* who, bool hybrid, const uint8_t* plain, const int64_t
                int32_t rng_mode, const double* uniforms, const int64_t* walk_uoff, uint64_t seed,
                n2v_alias_slot* scratch, int64_t scratch_slots, int32_t* walks, int32_t* lens,
                int32_t* status, void* stream) {
-    if (pos_count < 0 || round_count < 0 || pos_begin < 0 || round_begin < 0 || walk_length < 1 ||
-        pos_begin + pos_count > n_starts || max_degree < 0)
-        return n2v::fail(N2V_ERR_INVALID, "%s: bad shard or length", who);
-    const int64_t n_local = pos_count * round_count;
+    n2v::WalkShard sh;
+    if (const int rc = n2v::check_shard(who, starts, n_starts, pos_begin, pos_count, round_begin, round_count, walk_length, 1, &sh))
+        return rc;
+    if (max_degree < 0) return n2v::fail(N2V_ERR_INVALID, "%s: negative max_degree", who);
+    const int64_t n_local = sh.n_local;
     if (n_local == 0) return N2V_OK;
     if (!row_ptr || !col || !starts || !walks || !lens || !status)
         return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
@@ -361,7 +327,7 @@ int launch_otf(const char* who, bool hybrid, const uint8_t* plain, const int64_t
     auto dyadic = [](double x) { return x > 0.0 && x <= 1024.0 && x * 1048576.0 == (double)(int64_t)(x * 1048576.0); };
     const int32_t draw_first = (!w && symmetric && !pop) ? 2 : 1;
     const int32_t exact_sum = dyadic(wp) && dyadic(wq) && max_degree < (1 << 21);
-    OtfArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric, plain}, starts, n_starts, pos_begin, pos_count, round_begin, n_local, walk_length,
+    OtfArgs a{n2v::RowCtx{row_ptr, col, w, p, q, symmetric, plain}, sh,
               rng_mode, uniforms, walk_uoff, seed, scratch, max_degree, node_fat, fat, recs, walks, lens, status, draw_first, exact_sum, wp, wq};
     hipStream_t st = (hipStream_t)stream;
     // budgeted walk: one lane per walk once the launch is large enough to fill half the lanes of the resident waves
@@ -372,14 +338,11 @@ int launch_otf(const char* who, bool hybrid, const uint8_t* plain, const int64_t
         // 16-B output pieces: the 64-B bursts of the table-driven kernel cost 30 VGPRs here (4 instead of 6 waves per SIMD)
         // and this kernel lives on the waves it keeps in flight (C3, a third of the tables: 5.6 -> 6.3e9 steps/s)
         const int burst = (walk_length % 4 == 0 && ((uintptr_t)walks & 15) == 0) ? 4 : 1;
-#define N2V_LAUNCH_LANES(RNG)                                                                                       \
-        do {                                                                                                        \
-            if (burst == 4) hipLaunchKernelGGL((walk_hybrid_lanes_kernel<RNG, 4>), grid, block, 0, st, a);          \
-            else hipLaunchKernelGGL((walk_hybrid_lanes_kernel<RNG, 1>), grid, block, 0, st, a);                     \
-        } while (0)
-        if (rng_mode == N2V_RNG_UNIFORMS) N2V_LAUNCH_LANES(N2V_RNG_UNIFORMS);
-        else N2V_LAUNCH_LANES(N2V_RNG_PHILOX);
-#undef N2V_LAUNCH_LANES
+        n2v::dispatch<N2V_RNG_UNIFORMS, N2V_RNG_PHILOX>(rng_mode, [&](auto rng) {
+            n2v::dispatch<4, 1>(burst, [&](auto b) {
+                hipLaunchKernelGGL((walk_hybrid_lanes_kernel<decltype(rng)::value, decltype(b)::value>), grid, block, 0, st, a);
+            });
+        });
     } else if (hybrid) {
         hipLaunchKernelGGL((walk_otf_kernel<true, n2v::kRuleNone>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     } else if (pop) {
