@@ -118,6 +118,49 @@ int n2v_eccknn_sim_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const doub
                           int64_t n, const double* w, int32_t method, int32_t min_support, double* sim, int32_t* freq,
                           double* prods, double* sqi, double* sqj, double* sq_diff, void* stream);
 
+/* ---- KNNBasic's Pearson similarities and the ALS baselines (the plain k-NN that EccenKNN is compared against) -------
+ * src/main_rec.py:166-169 hands 'pearson' and 'pearson_baseline' to surprise's own functions, :181-189 feeds the second
+ * one compute_baselines(), global_mean and shrinkage, and :197 passes the per-item dictionary to all of them.  surprise
+ * (scikit-surprise 1.0.6, requirements.txt:42) is not a dependency: what follows is its arithmetic restated, parity with
+ * surprise itself is UNPINNED, and tests/eccknn_pearson_reference.py is the definition the kernels equal bit for bit.
+ * The optional w[y] is the factor the reference meant to apply (surprise would have rejected the keyword).
+ *
+ * One half-epoch per launch, 2 * n_epochs launches: bu = bi = 0, then per epoch
+ *   bi[i] = (sum over ir[i], in list order, of (r - global_mean) - bu[u]) / (reg_i + len(ir[i]))     for every item,
+ *   bu[u] = (sum over ur[u], in list order, of (r - global_mean) - bi[i]) / (reg_u + len(ur[u]))     from the new bi.
+ * ur_ptr: int64[n_users + 1], ur_i: int32, ur_r: fp64 (the ratings of every user in training order; ur_ptr[n_users] is
+ * their number), ir_* the same per item.  An id outside the other side's range is no entry: it adds nothing and does
+ * not count in len.  An empty row gives 0.0 / (reg + 0).  n_epochs >= 0 (0: zeros), reg_u, reg_i >= 0.
+ * surprise's defaults are n_epochs 10, reg_u 15, reg_i 10.  (baseline_als; the sgd method is sequential and not built.) */
+int n2v_eccknn_baselines(const int64_t* ur_ptr, const int32_t* ur_i, const double* ur_r, int64_t n_users,
+                         const int64_t* ir_ptr, const int32_t* ir_u, const double* ir_r, int64_t n_items, double global_mean,
+                         int32_t n_epochs, double reg_u, double reg_i, double* bu, double* bi, void* stream);
+
+/* The frame, the inputs and the error rules of n2v_eccknn_sim / n2v_eccknn_sim_sparse; w may be NULL (no factor, the
+ * bits of w = 1.0).  Per co-rated y ascending, freq += 1 and
+ *   PEARSON           prods += (ri*rj)*w[y]; sqi += ri*ri; sqj += rj*rj; si += ri; sj += rj;  n = (double)freq
+ *                     sim = 0 if freq < min_support, else with denum = sqrt((n*sqi - si*si) * (n*sqj - sj*sj)):
+ *                     0 if denum == 0, else (n*prods - si*sj) / denum.  A difference that cancellation makes negative
+ *                     gives sqrt of a negative number: the NaN is kept.            a1 .. a4 = sqi, sqj, si, sj
+ *   PEARSON_BASELINE  pb = global_mean + by[y]; di = ri - (pb + bx[xi]); dj = rj - (pb + bx[xj]);
+ *                     prods += (di*dj)*w[y]; sq_diff_i += di*di; sq_diff_j += dj*dj
+ *                     sim = 0 if freq < max(2, min_support), else
+ *                     (prods / sqrt(sq_diff_i*sq_diff_j)) * ((double)(freq-1) / ((double)(freq-1) + shrinkage)); no
+ *                     zero test: 0/0 and x/0 stay NaN / inf.      a1, a2 = sq_diff_i, sq_diff_j; a3, a4 are ignored
+ * The diagonal of sim is 1.  freq, prods and a1 .. a4 are [n_x][n_x], the diagonal included, each may be NULL; the
+ * mirror swaps a1 / a2 and a3 / a4.  bx: fp64[n_x], by: fp64[n_y], required for PEARSON_BASELINE, ignored for PEARSON,
+ * as are global_mean and shrinkage (surprise's default: 100).                                                        */
+#define N2V_ECCKNN_PEARSON 0
+#define N2V_ECCKNN_PEARSON_BASELINE 1
+int n2v_eccknn_pearson(const double* dense, const uint8_t* mask, int64_t n_x, int64_t n_y, const double* w, int32_t kind,
+                       int32_t min_support, double global_mean, const double* bx, const double* by, double shrinkage,
+                       double* sim, int32_t* freq, double* prods, double* a1, double* a2, double* a3, double* a4,
+                       void* stream);
+int n2v_eccknn_pearson_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_x, int64_t n_y,
+                              int64_t n, const double* w, int32_t kind, int32_t min_support, double global_mean,
+                              const double* bx, const double* by, double shrinkage, double* sim, int32_t* freq,
+                              double* prods, double* a1, double* a2, double* a3, double* a4, void* stream);
+
 /* One wavefront per query (qx[q], qy[q]); -1 = unknown.  yr_ptr: int64[n_y + 1], yr_x: int32, yr_r: fp64 — the raters
  * of every y in training order.  Candidates are (sim[x, x2], r) in list order; the k largest by sim are kept, equal
  * sims in list order (heapq.nlargest with a key = a stable descending sort), -0.0 ties +0.0.  DEVIATION: a NaN sim

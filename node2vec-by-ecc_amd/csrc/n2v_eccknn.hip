@@ -19,6 +19,13 @@
 //                    The row that set the bound consumes its whole chunk, so every round makes progress.  finish_tile is
 //                    shared with sim_kernel.  csr_check_kernel (integers only) names a malformed CSR; the similarity
 //                    kernel itself clamps every row range to [0, n] and never indexes w with a y outside [0, n_y).
+//                    The two Pearson similarities of surprise's KNNBasic (n2v_eccknn_pearson, n2v_eccknn_pearson_sparse)
+//                    are two more METHODs of the same two kernels: pearson carries prods, sqi, sqj, si, sj; the
+//                    baseline form carries prods, sq_diff_i, sq_diff_j of the ratings' deviations from
+//                    global_mean + by[y] + bx[x], with the thread's 4 + 4 bx in registers and global_mean + by[y]
+//                    staged beside w[y].  w may be absent there: the factor is 1.0, which changes no bit.
+//   baselines_kernel one half-epoch of surprise's baseline_als: one wavefront per row gathers the other side's
+//                    baselines 64 at a time and adds the terms (r - mean) - b in list order.
 //   estimate_kernel  one wavefront per query: gathers sim[x, x2] over the raters of y, keeps the best k of them in a
 //                    sorted LDS list under the one order of n2v_rank.h (higher sim first, equal sims by list position,
 //                    -0.0 ties +0.0, NaN below everything) and sums in rank order.
@@ -49,21 +56,47 @@ __global__ void __launch_bounds__(256) densify_kernel(const int32_t* __restrict_
 
 // ---- similarity -------------------------------------------------------------------------------------------------------
 
+constexpr int M_PEARSON = 2;      // METHOD values after N2V_ECCKNN_COSINE / N2V_ECCKNN_MSD; the C-ABI reaches them only
+constexpr int M_PBASE = 3;        // through n2v_eccknn_pearson[_sparse] (kind 0 / 1), never through the old method enum
+
 struct SimOut {
     int64_t n_x; int min_support;
     double* sim; int32_t* freq; double* prods; double* sqi; double* sqj; double* sq_diff;
+    double* si; double* sj; double shrinkage;                     // pearson's sums; pearson_baseline's shrinkage
 };
-struct SimArgs {
-    const double* dense; const uint8_t* mask; int64_t n_y; const double* w; SimOut o;
+// What pearson_baseline reads beside the ratings.
+struct Baselines {
+    const double* bx; const double* by; double global_mean;
+};
+struct SimArgs {                                                  // w may be NULL for the two Pearson methods
+    const double* dense; const uint8_t* mask; int64_t n_y; const double* w; SimOut o; Baselines b;
 };
 
 // The finishing step of a tile, the one copy behind the dense and the sparse kernel: thread (ty, tx) holds the
-// accumulators of pairs (i0 + 4 ty + u, j0 + 4 tx + v).  i == j -> 1, freq < min_support -> 0, else the division and
-// the sqrt; the mirror is written from the same values with sqi / sqj swapped.
+// accumulators of pairs (i0 + 4 ty + u, j0 + 4 tx + v).  i == j -> 1, freq < min_support -> 0, else the method's formula;
+// the mirror is written from the same values with the per-side accumulators (p1 / p2 and p3 / p4) swapped.
+//   cosine    p0 prods, p1 sqi, p2 sqj                  msd               p0 sq_diff
+//   pearson   p0 prods, p1 sqi, p2 sqj, p3 si, p4 sj    pearson_baseline  p0 prods, p1 sq_diff_i, p2 sq_diff_j
+template <int METHOD>
+__device__ __forceinline__ double finish_pair(const SimOut& o, int32_t fr, double p0, double p1, double p2, double p3,
+                                              double p4) {
+    if (fr < o.min_support) return 0.0;
+    if (METHOD == N2V_ECCKNN_COSINE) return p0 / sqrt(p1 * p2);
+    if (METHOD == N2V_ECCKNN_MSD) return 1.0 / (p0 / (double)fr + 1.0);
+    if (METHOD == M_PEARSON) {
+        const double n = (double)fr;
+        const double num = n * p0 - p3 * p4;
+        const double denum = sqrt((n * p1 - p3 * p3) * (n * p2 - p4 * p4));   // a negative product: NaN, and it is kept
+        return denum == 0 ? 0.0 : num / denum;
+    }
+    const double f1 = (double)(fr - 1);                           // min_support is at least 2 here
+    return (p0 / sqrt(p1 * p2)) * (f1 / (f1 + o.shrinkage));      // no zero test in the source: 0/0 and x/0 stay
+}
+
 template <int METHOD>
 __device__ __forceinline__ void finish_tile(const SimOut& o, int64_t i0, int64_t j0, int ty, int tx, bool diag_tile,
                                             const int32_t (&fr)[4][4], const double (&p0)[4][4], const double (&p1)[4][4],
-                                            const double (&p2)[4][4]) {
+                                            const double (&p2)[4][4], const double (&p3)[4][4], const double (&p4)[4][4]) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int64_t i = i0 + 4 * ty + u;
@@ -71,28 +104,47 @@ __device__ __forceinline__ void finish_tile(const SimOut& o, int64_t i0, int64_t
         for (int v = 0; v < 4; ++v) {
             const int64_t j = j0 + 4 * tx + v;
             if (i >= o.n_x || j >= o.n_x) continue;
-            double s;
-            if (i == j) s = 1.0;
-            else if (fr[u][v] < o.min_support) s = 0.0;
-            else if (METHOD == N2V_ECCKNN_COSINE) s = p0[u][v] / sqrt(p1[u][v] * p2[u][v]);
-            else s = 1.0 / (p0[u][v] / (double)fr[u][v] + 1.0);
+            const double s = i == j ? 1.0 : finish_pair<METHOD>(o, fr[u][v], p0[u][v], p1[u][v], p2[u][v], p3[u][v], p4[u][v]);
             const int64_t k = i * o.n_x + j, m = j * o.n_x + i;
             o.sim[k] = s;
             if (o.freq) o.freq[k] = fr[u][v];
-            if (METHOD == N2V_ECCKNN_COSINE) {
+            if (METHOD == N2V_ECCKNN_MSD) {
+                if (o.sq_diff) o.sq_diff[k] = p0[u][v];
+            } else {
                 if (o.prods) o.prods[k] = p0[u][v];
                 if (o.sqi) o.sqi[k] = p1[u][v];
                 if (o.sqj) o.sqj[k] = p2[u][v];
-            } else if (o.sq_diff) o.sq_diff[k] = p0[u][v];
+                if (METHOD == M_PEARSON) {
+                    if (o.si) o.si[k] = p3[u][v];
+                    if (o.sj) o.sj[k] = p4[u][v];
+                }
+            }
             if (diag_tile) continue;                              // a diagonal tile computed its own lower half
             o.sim[m] = s;
             if (o.freq) o.freq[m] = fr[u][v];
-            if (METHOD == N2V_ECCKNN_COSINE) {
+            if (METHOD == N2V_ECCKNN_MSD) {
+                if (o.sq_diff) o.sq_diff[m] = p0[u][v];
+            } else {
                 if (o.prods) o.prods[m] = p0[u][v];
                 if (o.sqi) o.sqi[m] = p2[u][v];
                 if (o.sqj) o.sqj[m] = p1[u][v];
-            } else if (o.sq_diff) o.sq_diff[m] = p0[u][v];
+                if (METHOD == M_PEARSON) {
+                    if (o.si) o.si[m] = p4[u][v];
+                    if (o.sj) o.sj[m] = p3[u][v];
+                }
+            }
         }
+    }
+}
+
+// The thread's 4 + 4 bx (rows 4 ty + u of the tile, columns 4 tx + v), read only for x < n_x.
+__device__ __forceinline__ void load_bx(const Baselines& b, int64_t n_x, int64_t i0, int64_t j0, int ty, int tx,
+                                        double (&bxi)[4], double (&bxj)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = i0 + 4 * ty + u, j = j0 + 4 * tx + u;
+        bxi[u] = i < n_x ? b.bx[i] : 0.0;
+        bxj[u] = j < n_x ? b.bx[j] : 0.0;
     }
 }
 
@@ -105,16 +157,19 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
     __shared__ __attribute__((aligned(4))) uint8_t ma[YC][TB];
     __shared__ __attribute__((aligned(4))) uint8_t mb[YC][TB];
     __shared__ double wl[YC];
+    __shared__ double pbl[METHOD == M_PBASE ? YC : 1];            // global_mean + by[y] of the staged y
 
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
     const int64_t i0 = (int64_t)ti * TB, j0 = (int64_t)tj * TB;
 
     int32_t fr[4][4];
-    double p0[4][4], p1[4][4], p2[4][4];                          // cosine: prods, sqi, sqj; msd: sq_diff, -, -
+    double p0[4][4], p1[4][4], p2[4][4], p3[4][4], p4[4][4];      // finish_tile names them per method
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { fr[u][v] = 0; p0[u][v] = 0.0; p1[u][v] = 0.0; p2[u][v] = 0.0; }
+        for (int v = 0; v < 4; ++v) { fr[u][v] = 0; p0[u][v] = 0.0; p1[u][v] = 0.0; p2[u][v] = 0.0; p3[u][v] = 0.0; p4[u][v] = 0.0; }
+    double bxi[4] = {0.0, 0.0, 0.0, 0.0}, bxj[4] = {0.0, 0.0, 0.0, 0.0};
+    if (METHOD == M_PBASE) load_bx(a.b, a.o.n_x, i0, j0, ty, tx, bxi, bxj);
 
     for (int64_t y0 = 0; y0 < a.n_y; y0 += YC) {
         __syncthreads();                                          // the previous chunk has been consumed
@@ -129,7 +184,8 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
             }
             ra[yy][c] = va; rb[yy][c] = vb; ma[yy][c] = qa; mb[yy][c] = qb;
         }
-        if (t < YC) wl[t] = (y0 + t < a.n_y) ? a.w[y0 + t] : 0.0;
+        if (t < YC) wl[t] = (y0 + t < a.n_y) ? (a.w ? a.w[y0 + t] : 1.0) : 0.0;
+        if (METHOD == M_PBASE && t < YC) pbl[t] = (y0 + t < a.n_y) ? a.b.global_mean + a.b.by[y0 + t] : 0.0;
         __syncthreads();
 #pragma unroll 2
         for (int yy = 0; yy < YC; ++yy) {                         // y ascending: the order of every accumulator
@@ -155,6 +211,42 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
                         p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
                         p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
                     }
+            } else if (METHOD == M_PEARSON) {
+                double si[4], sj[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) { si[u] = ri[u] * ri[u]; sj[u] = rj[u] * rj[u]; }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
+                        const double pr = (ri[u] * rj[v]) * wy;
+                        fr[u][v] += co ? 1 : 0;
+                        p0[u][v] = co ? p0[u][v] + pr : p0[u][v];
+                        p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
+                        p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
+                        p3[u][v] = co ? p3[u][v] + ri[u] : p3[u][v];
+                        p4[u][v] = co ? p4[u][v] + rj[v] : p4[u][v];
+                    }
+            } else if (METHOD == M_PBASE) {
+                const double pb = pbl[yy];
+                double di[4], dj[4], si[4], sj[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    di[u] = ri[u] - (pb + bxi[u]); dj[u] = rj[u] - (pb + bxj[u]);
+                    si[u] = di[u] * di[u]; sj[u] = dj[u] * dj[u];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
+                        const double pr = (di[u] * dj[v]) * wy;
+                        fr[u][v] += co ? 1 : 0;
+                        p0[u][v] = co ? p0[u][v] + pr : p0[u][v];
+                        p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
+                        p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
+                    }
             } else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -169,7 +261,7 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
         }
     }
 
-    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2);
+    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2, p3, p4);
 }
 
 // ---- similarity, sparse -----------------------------------------------------------------------------------------------
@@ -180,7 +272,7 @@ constexpr int Y_MAX = 0x7fffffff;
 
 struct SparseArgs {
     const int64_t* xr_ptr; const int32_t* xr_y; const double* xr_r; int64_t n_y; int64_t n; const double* w; int64_t tiles;
-    SimOut o;
+    SimOut o; Baselines b;
 };
 
 __device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -190,6 +282,7 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
     __shared__ int32_t sy[2 * TB][SP];                            // rows 0..63: the tile's rows, 64..127: its columns
     __shared__ double sr[2 * TB][SP];
     __shared__ double sw[TB][SP];                                 // w[y] of the staged entries of the tile's rows
+    __shared__ double sp[METHOD == M_PBASE ? TB : 1][SP];         // global_mean + by[y] of the same entries
     __shared__ int64_t pos[2 * TB], end[2 * TB];                  // cursor and end of every row, inside [0, n]
     __shared__ int32_t ready[2 * TB];
     __shared__ int32_t bound[2];
@@ -206,11 +299,13 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
     const int64_t i0 = ti * TB, j0 = tj * TB;
 
     int32_t fr[4][4];
-    double p0[4][4], p1[4][4], p2[4][4];                          // cosine: prods, sqi, sqj; msd: sq_diff, -, -
+    double p0[4][4], p1[4][4], p2[4][4], p3[4][4], p4[4][4];      // finish_tile names them per method
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int v = 0; v < 4; ++v) { fr[u][v] = 0; p0[u][v] = 0.0; p1[u][v] = 0.0; p2[u][v] = 0.0; }
+        for (int v = 0; v < 4; ++v) { fr[u][v] = 0; p0[u][v] = 0.0; p1[u][v] = 0.0; p2[u][v] = 0.0; p3[u][v] = 0.0; p4[u][v] = 0.0; }
+    double bxi[4] = {0.0, 0.0, 0.0, 0.0}, bxj[4] = {0.0, 0.0, 0.0, 0.0};
+    if (METHOD == M_PBASE) load_bx(a.b, a.o.n_x, i0, j0, ty, tx, bxi, bxj);
 
     int live_a = 0, live_b = 0;
     if (t < 2 * TB) {
@@ -234,7 +329,11 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
                 const int32_t y = a.xr_y[p];
                 sy[row][k] = y;
                 sr[row][k] = a.xr_r[p];
-                if (row < TB) sw[row][k] = (y >= 0 && y < a.n_y) ? a.w[y] : __builtin_nan("");
+                if (row < TB) {
+                    const bool in = y >= 0 && y < a.n_y;
+                    sw[row][k] = in ? (a.w ? a.w[y] : 1.0) : __builtin_nan("");
+                    if (METHOD == M_PBASE) sp[row][k] = in ? a.b.global_mean + a.b.by[y] : __builtin_nan("");
+                }
             }
         }
         // the bound: the smallest last-staged y among rows with entries beyond their staged ones (none: everything)
@@ -278,6 +377,18 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
                             p0[u][v] = p0[u][v] + (ri * rj) * wy; // `ri * rj * i_dict[y]`: left to right
                             p1[u][v] = p1[u][v] + ri * ri;
                             p2[u][v] = p2[u][v] + rj * rj;
+                        } else if (METHOD == M_PEARSON) {
+                            p0[u][v] = p0[u][v] + (ri * rj) * wy;
+                            p1[u][v] = p1[u][v] + ri * ri;
+                            p2[u][v] = p2[u][v] + rj * rj;
+                            p3[u][v] = p3[u][v] + ri;
+                            p4[u][v] = p4[u][v] + rj;
+                        } else if (METHOD == M_PBASE) {
+                            const double pb = sp[ra][ka];
+                            const double di = ri - (pb + bxi[u]), dj = rj - (pb + bxj[v]);
+                            p0[u][v] = p0[u][v] + (di * dj) * wy;
+                            p1[u][v] = p1[u][v] + di * di;
+                            p2[u][v] = p2[u][v] + dj * dj;
                         } else {
                             const double d = (ri - rj) * wy;
                             p0[u][v] = p0[u][v] + d * d;
@@ -297,7 +408,7 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
         par ^= 1;
         __syncthreads();                                          // the staged segments have been consumed
     }
-    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2);
+    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2, p3, p4);
 }
 
 // One lane per row and per entry; integers only.
@@ -322,6 +433,42 @@ __global__ void __launch_bounds__(256) csr_check_kernel(const int64_t* __restric
         }
     }
     if (bits) atomicOr(status, bits);
+}
+
+// ---- baselines --------------------------------------------------------------------------------------------------------
+
+// One half-epoch of baseline_als, one wavefront per row: b_out[row] = (sum over the row's list, in list order, of
+// (r - mean) - b_other[id]) / (reg + entries).  The lanes gather 64 terms at a time; every lane then adds them one after
+// the other.  An id outside [0, n_other) is no entry: it adds nothing and is not counted.  Row ranges are clamped to
+// [0, ptr[n_rows]].
+__global__ void __launch_bounds__(64) baselines_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ ids,
+                                                       const double* __restrict__ r, int64_t n_rows, int64_t n_other,
+                                                       double mean, double reg, const double* __restrict__ b_other,
+                                                       double* __restrict__ b_out) {
+    const int64_t row = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t n = ptr[n_rows] > 0 ? ptr[n_rows] : 0;
+    const int64_t pb = clamp64(ptr[row], 0, n), pe = clamp64(ptr[row + 1], pb, n);
+    double sum = 0.0;
+    int64_t cnt = 0;
+    for (int64_t base = pb; base < pe; base += 64) {
+        const int64_t p = base + lane;
+        double term = 0.0;
+        bool in = false;
+        if (p < pe) {
+            const int64_t id = ids[p];
+            in = id >= 0 && id < n_other;
+            if (in) term = (r[p] - mean) - b_other[id];           // `r - global_mean - bu[u]`: left to right
+        }
+        unsigned long long have = __ballot(in);
+        cnt += __popcll(have);
+        while (have) {                                            // in list order; wave-uniform
+            const int src = __ffsll((long long)have) - 1;
+            have &= have - 1;
+            sum = sum + __shfl(term, src, 64);
+        }
+    }
+    if (lane == 0) b_out[row] = sum / (reg + (double)cnt);
 }
 
 // ---- estimate ---------------------------------------------------------------------------------------------------------
@@ -463,7 +610,8 @@ int n2v_eccknn_sim(const double* dense, const uint8_t* mask, int64_t n_x, int64_
     if (!dense || !mask || !w || !sim) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: null pointer");
     const int64_t T = (n_x + TB - 1) / TB;
     if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SimArgs a{dense, mask, n_y, w, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff}};
+    SimArgs a{dense, mask, n_y, w, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff, nullptr, nullptr, 0.0},
+              Baselines{nullptr, nullptr, 0.0}};
     const dim3 grid((unsigned)T, (unsigned)T);
     if (method == N2V_ECCKNN_COSINE) sim_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else sim_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
@@ -491,11 +639,85 @@ int n2v_eccknn_sim_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const doub
     if (!xr_ptr || !w || !sim || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: null pointer");
     const int64_t T = (n_x + TB - 1) / TB;
     if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff}};
+    SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff, nullptr, nullptr, 0.0},
+                 Baselines{nullptr, nullptr, 0.0}};
     const unsigned grid = (unsigned)(T * (T + 1) / 2);            // < 2^31 for T <= 65535
     if (method == N2V_ECCKNN_COSINE) sim_sparse_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else sim_sparse_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     return n2v::check_launch("eccknn_sim_sparse");
+}
+
+// The checks n2v_eccknn_pearson and n2v_eccknn_pearson_sparse share; 0 or the error.
+static int pearson_args(const char* who, int32_t kind, const double* bx, const double* by) {
+    if (kind != N2V_ECCKNN_PEARSON && kind != N2V_ECCKNN_PEARSON_BASELINE) return n2v::fail(N2V_ERR_INVALID, "%s: kind %d", who, kind);
+    if (kind == N2V_ECCKNN_PEARSON_BASELINE && (!bx || !by)) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (bx / by, required by kind 1)", who);
+    return N2V_OK;
+}
+
+// kind 0: a1 .. a4 are sqi, sqj, si, sj; kind 1: a1, a2 are sq_diff_i, sq_diff_j and min_support is raised to 2.
+static SimOut pearson_out(int32_t kind, int64_t n_x, int32_t min_support, double shrinkage, double* sim, int32_t* freq,
+                          double* prods, double* a1, double* a2, double* a3, double* a4) {
+    const bool base = kind == N2V_ECCKNN_PEARSON_BASELINE;
+    return SimOut{n_x, base && min_support < 2 ? 2 : min_support, sim, freq, prods, a1, a2, nullptr,
+                  base ? nullptr : a3, base ? nullptr : a4, shrinkage};
+}
+
+int n2v_eccknn_pearson(const double* dense, const uint8_t* mask, int64_t n_x, int64_t n_y, const double* w, int32_t kind,
+                       int32_t min_support, double global_mean, const double* bx, const double* by, double shrinkage,
+                       double* sim, int32_t* freq, double* prods, double* a1, double* a2, double* a3, double* a4,
+                       void* stream) {
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
+    if (n_x > MAX_DENSE || n_y > MAX_DENSE || n_x * n_y > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: n_x * n_y = %lld x %lld exceeds the dense limit of %lld elements",
+                         (long long)n_x, (long long)n_y, (long long)MAX_DENSE);
+    if (const int rc = pearson_args("eccknn_pearson", kind, bx, by)) return rc;
+    if (!dense || !mask || !sim) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: null pointer");
+    const int64_t T = (n_x + TB - 1) / TB;
+    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
+    SimArgs a{dense, mask, n_y, w, pearson_out(kind, n_x, min_support, shrinkage, sim, freq, prods, a1, a2, a3, a4),
+              Baselines{bx, by, global_mean}};
+    const dim3 grid((unsigned)T, (unsigned)T);
+    if (kind == N2V_ECCKNN_PEARSON) sim_kernel<M_PEARSON><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else sim_kernel<M_PBASE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("eccknn_pearson");
+}
+
+int n2v_eccknn_pearson_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_x, int64_t n_y,
+                              int64_t n, const double* w, int32_t kind, int32_t min_support, double global_mean,
+                              const double* bx, const double* by, double shrinkage, double* sim, int32_t* freq,
+                              double* prods, double* a1, double* a2, double* a3, double* a4, void* stream) {
+    if (n_x < 1 || n_y < 1 || n_y > Y_MAX || n < 0)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson_sparse: n_x=%lld n_y=%lld n=%lld", (long long)n_x, (long long)n_y, (long long)n);
+    if (const int rc = pearson_args("eccknn_pearson_sparse", kind, bx, by)) return rc;
+    if (!xr_ptr || !sim || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson_sparse: null pointer");
+    const int64_t T = (n_x + TB - 1) / TB;
+    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson_sparse: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
+    SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T, pearson_out(kind, n_x, min_support, shrinkage, sim, freq, prods, a1, a2, a3, a4),
+                 Baselines{bx, by, global_mean}};
+    const unsigned grid = (unsigned)(T * (T + 1) / 2);            // < 2^31 for T <= 65535
+    if (kind == N2V_ECCKNN_PEARSON) sim_sparse_kernel<M_PEARSON><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    else sim_sparse_kernel<M_PBASE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("eccknn_pearson_sparse");
+}
+
+int n2v_eccknn_baselines(const int64_t* ur_ptr, const int32_t* ur_i, const double* ur_r, int64_t n_users,
+                         const int64_t* ir_ptr, const int32_t* ir_u, const double* ir_r, int64_t n_items, double global_mean,
+                         int32_t n_epochs, double reg_u, double reg_i, double* bu, double* bi, void* stream) {
+    if (n_users < 1 || n_items < 1 || n_users > 0x7fffffff || n_items > 0x7fffffff)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_baselines: n_users=%lld n_items=%lld outside [1, 2^31)", (long long)n_users, (long long)n_items);
+    if (n_epochs < 0) return n2v::fail(N2V_ERR_INVALID, "eccknn_baselines: n_epochs %d < 0", n_epochs);
+    if (!(reg_u >= 0)) return n2v::fail(N2V_ERR_INVALID, "eccknn_baselines: reg_u %g < 0", reg_u);
+    if (!(reg_i >= 0)) return n2v::fail(N2V_ERR_INVALID, "eccknn_baselines: reg_i %g < 0", reg_i);
+    if (!ur_ptr || !ur_i || !ur_r || !ir_ptr || !ir_u || !ir_r || !bu || !bi) return n2v::fail(N2V_ERR_INVALID, "eccknn_baselines: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(bu, 0, (size_t)n_users * sizeof(double), s) != hipSuccess ||
+        hipMemsetAsync(bi, 0, (size_t)n_items * sizeof(double), s) != hipSuccess)
+        return n2v::fail(N2V_ERR_HIP, "eccknn_baselines: memset failed");
+    for (int32_t e = 0; e < n_epochs; ++e) {                      // every item from bu, then every user from the new bi
+        baselines_kernel<<<(unsigned)n_items, 64, 0, s>>>(ir_ptr, ir_u, ir_r, n_items, n_users, global_mean, reg_i, bu, bi);
+        baselines_kernel<<<(unsigned)n_users, 64, 0, s>>>(ur_ptr, ur_i, ur_r, n_users, n_items, global_mean, reg_u, bi, bu);
+    }
+    return n2v::check_launch("eccknn_baselines");
 }
 
 int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,

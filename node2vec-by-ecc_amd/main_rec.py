@@ -1,10 +1,16 @@
-"""Drop-in for the working part of the reference's src/main_rec.py: EccenKNN rating prediction on the device.
+"""Drop-in for the working part of the reference's src/main_rec.py: EccenKNN rating prediction on the device, and the
+plain k-NN (surprise's KNNBasic) it is compared against.
 
-    python main_rec.py -input ratings.csv [-k 40] [-mink 1] [-sim cosine|msd] [-item-based] [-weights FILE]
+    python main_rec.py -input ratings.csv [-algo eccen|knn] [-k 40] [-mink 1] [-sim cosine|msd|pearson|pearson_baseline]
+                       [-shrinkage 100] [-item-based] [-weights FILE]
                        [-mode ir|ie|ire|ier] [-window-col timestamp|timewindow] [-save-weights FILE]
                        [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
+-algo     eccen (the default) or knn: KNNBasic, which also takes -sim pearson and pearson_baseline (surprise's functions,
+          restated; parity with surprise is unpinned) and -shrinkage for the latter.  With -algo knn, -weights / -mode
+          weight the baseline's co-ratings, as the reference meant to (src/main_rec.py:197); absent, there are no weights.
+          svd is not built.
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
 -mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
           rarity, item eccentricity, their product or their quotient, from the WHOLE input file before the split, as the
@@ -24,8 +30,10 @@ import numpy as np
 
 
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description="EccenKNN rating prediction (HIP, gfx950)")
+    p = argparse.ArgumentParser(description="EccenKNN / KNNBasic rating prediction (HIP, gfx950)")
     p.add_argument("-input", required=True)
+    p.add_argument("-algo", default="eccen")
+    p.add_argument("-shrinkage", type=float, default=100)
     p.add_argument("-k", type=int, default=40)
     p.add_argument("-mink", type=int, default=1)
     p.add_argument("-sim", default="cosine")
@@ -41,6 +49,12 @@ def parse_args(argv=None):
     p.add_argument("-form", default="auto", choices=["auto", "dense", "sparse"])
     p.add_argument("-device", default="cuda:0")
     a = p.parse_args(argv)
+    if a.algo == "svd":
+        p.error("-algo svd is not built: eccen or knn")
+    if a.algo not in ("eccen", "knn"):
+        p.error("-algo %s: eccen or knn" % a.algo)
+    if a.sim in ("pearson", "pearson_baseline") and a.algo != "knn":
+        p.error("-sim %s is surprise's own similarity: it needs -algo knn" % a.sim)
     if not 0.0 < a.test_ratio < 1.0:
         p.error("-test-ratio must be inside (0, 1)")
     if a.cv == 1 or a.cv < 0:
@@ -144,9 +158,13 @@ def run_split(args, users, items, ratings, weights, train, test):
     from n2v_hip import eccknn
     ts = eccknn.Trainset.from_ratings([users[i] for i in train], [items[i] for i in train], ratings[train],
                                       rating_scale=(float(ratings.min()), float(ratings.max())))
-    algo = eccknn.EccenKNN(k=args.k, min_k=args.mink, device=args.device,
-                           sim_options={"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support,
-                                        "form": args.form})
+    sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
+    if args.algo == "knn":
+        sim_options["shrinkage"] = args.shrinkage
+        algo = eccknn.KNNBasic(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
+        algo.fit(ts, weights)
+        return algo.rmse([(users[i], items[i], ratings[i]) for i in test])
+    algo = eccknn.EccenKNN(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
     if weights is None:
         w = np.ones(ts.n_users if args.item_based else ts.n_items)
     else:

@@ -106,6 +106,11 @@ SIGNATURES = {
     "n2v_eccknn_csr_check": (C.c_int, [_ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr]),
     "n2v_eccknn_sim_sparse": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr,
                                         _ptr, _ptr]),
+    "n2v_eccknn_baselines": (C.c_int, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i64, _f64, _i32, _f64, _f64, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_pearson": (C.c_int, [_ptr, _ptr, _i64, _i64, _ptr, _i32, _i32, _f64, _ptr, _ptr, _f64, _ptr, _ptr, _ptr, _ptr,
+                                     _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_pearson_sparse": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i32, _i32, _f64, _ptr, _ptr, _f64, _ptr,
+                                            _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_eccknn_estimate": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr,
                                       _ptr]),
     "n2v_eccknn_predict": (C.c_int, [_ptr, _ptr, _ptr, _i64, _f64, _f64, _f64, _ptr, _ptr, _ptr]),

@@ -20,6 +20,13 @@ The similarity has two forms with the same bytes: the dense one (a y-major fp64 
 n2v_eccknn_max_dense() elements) and the sparse one (the x-major CSR of the ratings, no such bound).
 sim_options["form"] = "auto" (the default: dense inside the limit, sparse past it), "dense" or "sparse".
 
+KNNBasic is the plain k-NN the reference compares EccenKNN against (src/main_rec.py:19-29, 341-348: `-algo knn`,
+surprise's KNNBasic) under the four similarities of its `-sim` flag.  cosine and msd are the kernels above with all-ones
+weights; pearson and pearson_baseline are surprise's own functions, restated (tests/eccknn_pearson_reference.py) together
+with the ALS baselines the second one needs (src/main_rec.py:181-189).  Parity with surprise itself is unpinned for the
+same reason as above: the restatement is the definition and the kernels equal it bit for bit.  Optional weights multiply
+each co-rating's product, which is what the reference meant by passing its per-item dictionary to every similarity (:197).
+
 There is no CPU fallback.
 """
 import numpy as np
@@ -30,6 +37,9 @@ from . import _lib
 MAX_K = 256                      # N2V_ECCKNN_MAX_K
 SIM_NAMES = ("cosine", "msd", "pearson", "pearson_baseline")   # the reference's construction_func keys
 _METHOD = {"cosine": 0, "msd": 1}
+_PEARSON_KIND = {"pearson": 0, "pearson_baseline": 1}          # N2V_ECCKNN_PEARSON, N2V_ECCKNN_PEARSON_BASELINE
+_PEARSON_ACC = {"pearson": ("sqi", "sqj", "si", "sj"), "pearson_baseline": ("sq_diff_i", "sq_diff_j")}   # a1 .. a4
+BSL_DEFAULTS = {"method": "als", "n_epochs": 10, "reg_u": 15, "reg_i": 10}   # surprise's baseline_als
 FORMS = ("auto", "dense", "sparse")
 MAX_DENSE = 1 << 31              # n2v_eccknn_max_dense()
 CSR_BAD = ((1, "xr_ptr is not monotone or leaves [0, n]"), (2, "a y outside [0, n_y)"),
@@ -220,6 +230,102 @@ def similarity_sparse(xr, w, n_y, name, min_support=1, accumulators=False):
     return (sim, acc) if accumulators else sim
 
 
+def bsl_check(bsl_options):
+    """bsl_options with surprise's defaults filled in; host only.  sgd is refused: its updates are sequential."""
+    opts = dict(BSL_DEFAULTS, **(bsl_options or {}))
+    unknown = sorted(set(opts) - set(BSL_DEFAULTS))
+    if unknown:
+        raise ValueError("bsl_options: unknown key %s, allowed keys are %s" % (", ".join(unknown), ", ".join(BSL_DEFAULTS)))
+    if opts["method"] == "sgd":
+        raise ValueError("bsl_options: method sgd is not built (its updates are sequential across rows); use als")
+    if opts["method"] != "als":
+        raise ValueError("Invalid method " + str(opts["method"]) + " for baseline computation. Available methods are als and sgd.")
+    if int(opts["n_epochs"]) < 0 or not float(opts["reg_u"]) >= 0 or not float(opts["reg_i"]) >= 0:
+        raise ValueError("bsl_options: n_epochs %r, reg_u %r, reg_i %r: none may be negative"
+                         % (opts["n_epochs"], opts["reg_u"], opts["reg_i"]))
+    return opts
+
+
+def baselines(trainset, bsl_options=None, device="cuda:0"):
+    """(bu, bi) device fp64 tensors: surprise's baseline_als on the trainset's ur / ir lists (n2v_eccknn_baselines)."""
+    opts = bsl_check(bsl_options)
+    _require_gpu()
+    dev = torch.device(device)
+    lib = _lib.load()
+    to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+    ts = trainset
+    with torch.cuda.device(dev):
+        ur = (to(ts.ur[0], torch.int64), to(ts.ur[1], torch.int32), to(ts.ur[2], torch.float64))
+        ir = (to(ts.ir[0], torch.int64), to(ts.ir[1], torch.int32), to(ts.ir[2], torch.float64))
+        bu = torch.empty(ts.n_users, dtype=torch.float64, device=dev)
+        bi = torch.empty(ts.n_items, dtype=torch.float64, device=dev)
+        _lib.check(lib.n2v_eccknn_baselines(_lib.ptr(ur[0]), _lib.ptr(ur[1]), _lib.ptr(ur[2]), ts.n_users, _lib.ptr(ir[0]),
+                                            _lib.ptr(ir[1]), _lib.ptr(ir[2]), ts.n_items, float(ts.global_mean),
+                                            int(opts["n_epochs"]), float(opts["reg_u"]), float(opts["reg_i"]), _lib.ptr(bu),
+                                            _lib.ptr(bi), _lib.stream_ptr(dev)))
+    return bu, bi
+
+
+def _pearson_outputs(name, n_x, dev, accumulators):
+    sim = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
+    acc = {}
+    if accumulators:
+        acc["freq"] = torch.empty((n_x, n_x), dtype=torch.int32, device=dev)
+        for nm in ("prods",) + _PEARSON_ACC[name]:
+            acc[nm] = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
+    a = [_lib.ptr(acc.get(nm)) for nm in _PEARSON_ACC[name]] + [None, None]
+    return sim, acc, [_lib.ptr(sim), _lib.ptr(acc.get("freq")), _lib.ptr(acc.get("prods"))] + a[:4]
+
+
+def _pearson_inputs(name, n_x, n_y, w, bx, by):
+    if name not in _PEARSON_KIND:
+        raise NameError("Wrong sim name " + str(name) + ". Allowed values are " + ", ".join(_PEARSON_KIND) + ".")
+    if w is not None and w.numel() != int(n_y):
+        raise ValueError("similarity_pearson: %d weights for n_y = %d" % (w.numel(), n_y))
+    if name == "pearson_baseline" and (bx is None or by is None or bx.numel() != int(n_x) or by.numel() != int(n_y)):
+        raise ValueError("similarity_pearson: pearson_baseline needs bx[%d] and by[%d]" % (n_x, n_y))
+
+
+def similarity_pearson(dense, mask, name, w=None, min_support=1, global_mean=0.0, bx=None, by=None, shrinkage=100,
+                       accumulators=False):
+    """similarity() for "pearson" and "pearson_baseline" (n2v_eccknn_pearson).  w None: no weights.  The accumulators are
+    freq, prods and sqi / sqj / si / sj, or sq_diff_i / sq_diff_j.  pearson_baseline needs global_mean, bx[n_x], by[n_y]."""
+    _require_gpu()
+    n_y, n_x = dense.shape
+    _pearson_inputs(name, n_x, n_y, w, bx, by)
+    dev = dense.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        sim, acc, outs = _pearson_outputs(name, n_x, dev, accumulators)
+        _lib.check(lib.n2v_eccknn_pearson(_lib.ptr(dense), _lib.ptr(mask), n_x, n_y, _lib.ptr(w), _PEARSON_KIND[name],
+                                          int(min_support), float(global_mean), _lib.ptr(bx), _lib.ptr(by), float(shrinkage),
+                                          *outs, _lib.stream_ptr(dev)))
+    return (sim, acc) if accumulators else sim
+
+
+def similarity_pearson_sparse(xr, n_y, name, w=None, min_support=1, global_mean=0.0, bx=None, by=None, shrinkage=100,
+                              accumulators=False):
+    """similarity_pearson() from the x-major CSR of csr_by_x: the same bytes, no n_x * n_y limit.  The CSR is checked
+    first; a malformed one is a ValueError."""
+    _require_gpu()
+    if len(xr) != 3 or xr[0].dtype != torch.int64 or xr[1].dtype != torch.int32 or xr[2].dtype != torch.float64:
+        raise ValueError("similarity_pearson_sparse: xr must be (int64 ptr, int32 y, fp64 r)")
+    n_x, n = xr[0].numel() - 1, xr[1].numel()
+    if n_x < 1 or xr[2].numel() != n:
+        raise ValueError("similarity_pearson_sparse: %d rows, %d y, %d r" % (n_x, n, xr[2].numel()))
+    _pearson_inputs(name, n_x, n_y, w, bx, by)
+    csr_check(xr, n_y)
+    dev = xr[2].device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        sim, acc, outs = _pearson_outputs(name, n_x, dev, accumulators)
+        _lib.check(lib.n2v_eccknn_pearson_sparse(_lib.ptr(xr[0]), _lib.ptr(xr[1]) if n else None,
+                                                 _lib.ptr(xr[2]) if n else None, n_x, int(n_y), n, _lib.ptr(w),
+                                                 _PEARSON_KIND[name], int(min_support), float(global_mean), _lib.ptr(bx),
+                                                 _lib.ptr(by), float(shrinkage), *outs, _lib.stream_ptr(dev)))
+    return (sim, acc) if accumulators else sim
+
+
 def estimate_batch(sim, yr, qx, qy, k, min_k):
     """(est fp64, actual_k int32, impossible uint8) device tensors.  yr: device CSR triple (ptr int64, x int32, r fp64);
     qx / qy: int32 device tensors, -1 = unknown."""
@@ -260,18 +366,17 @@ def predict(est, impossible, global_mean, rating_scale, r_true=None):
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
 
-class EccenKNN:
+class _SymmetricKNN:
+    """What EccenKNN and KNNBasic share: the options, the weights, the device fit and estimate / test / rmse.  A subclass
+    names its similarities (_check_name) and may add to them (_similarity)."""
+
     def __init__(self, k=40, min_k=1, sim_options=None, device="cuda:0"):
         self.k, self.min_k = int(k), int(min_k)
         self.sim_options = dict(sim_options or {})
         self.sim_options.setdefault("user_based", True)
         self.device = device
         name = self.sim_options.get("name", "msd").lower()
-        if name not in SIM_NAMES:
-            raise NameError("Wrong sim name " + name + ". Allowed values " + "are " + ", ".join(SIM_NAMES) + ".")
-        if name not in _METHOD:
-            raise NameError("Wrong sim name " + name + ". " + name + " is surprise's own similarity, not the reference's; "
-                            "here the allowed values are " + ", ".join(_METHOD) + ".")
+        self._check_name(name)
         if not 1 <= self.k <= MAX_K:
             raise ValueError("k %d outside [1, %d]" % (self.k, MAX_K))
         if self.min_k < 1:
@@ -295,8 +400,15 @@ class EccenKNN:
             raise ValueError("weights: shape %s, expected (%d,)" % (w.shape, n_y))
         return w
 
-    def fit(self, trainset, weights):
-        w = self._weights(trainset, weights)
+    def _similarity(self, dense_mask, xr, dw):
+        """cosine / msd from whichever form _fit prepared."""
+        ms = self.sim_options.get("min_support", 1)
+        if dense_mask is not None:
+            return similarity(dense_mask[0], dense_mask[1], dw, self.name, ms)
+        return similarity_sparse(xr, dw, self.n_y, self.name, ms)
+
+    def _fit(self, trainset, w):
+        """w: host fp64[n_y], or None where the similarity takes no weights."""
         _require_gpu()
         dev = torch.device(self.device)
         ts = trainset
@@ -306,13 +418,12 @@ class EccenKNN:
         self.trainset = ts
         to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
         form = choose_form(self.n_x, self.n_y, self.form, int(_lib.load().n2v_eccknn_max_dense()))
-        dx, dy, dr, dw = to(x, torch.int32), to(y, torch.int32), to(ts.r, torch.float64), to(w, torch.float64)
+        dx, dy, dr = to(x, torch.int32), to(y, torch.int32), to(ts.r, torch.float64)
+        dw = None if w is None else to(w, torch.float64)
         if form == "dense":
-            dense, mask = densify(dx, dy, dr, self.n_x, self.n_y)
-            self.sim = similarity(dense, mask, dw, self.name, self.sim_options.get("min_support", 1))
+            self.sim = self._similarity(densify(dx, dy, dr, self.n_x, self.n_y), None, dw)
         else:
-            self.sim = similarity_sparse(csr_by_x(dx, dy, dr, self.n_x, self.n_y), dw, self.n_y, self.name,
-                                         self.sim_options.get("min_support", 1))
+            self.sim = self._similarity(None, csr_by_x(dx, dy, dr, self.n_x, self.n_y), dw)
         self.yr = (to(yr[0], torch.int64), to(yr[1], torch.int32), to(yr[2], torch.float64))
         return self
 
@@ -350,3 +461,51 @@ class EccenKNN:
 
     def rmse(self, testset):
         return self._test(testset)[3]
+
+
+class EccenKNN(_SymmetricKNN):
+    def _check_name(self, name):
+        if name not in SIM_NAMES:
+            raise NameError("Wrong sim name " + name + ". Allowed values " + "are " + ", ".join(SIM_NAMES) + ".")
+        if name not in _METHOD:
+            raise NameError("Wrong sim name " + name + ". " + name + " is surprise's own similarity, not the reference's; "
+                            "here the allowed values are " + ", ".join(_METHOD) + ".")
+
+    def fit(self, trainset, weights):
+        return self._fit(trainset, self._weights(trainset, weights))
+
+
+class KNNBasic(_SymmetricKNN):
+    """surprise's KNNBasic under cosine, msd, pearson and pearson_baseline.  fit(trainset) is the plain baseline;
+    fit(trainset, weights) weights every co-rating's product by w[y] as EccenKNN does.  pearson_baseline computes the ALS
+    baselines first (bsl_options) and reads sim_options["shrinkage"] (default 100)."""
+
+    def __init__(self, k=40, min_k=1, sim_options=None, bsl_options=None, device="cuda:0"):
+        _SymmetricKNN.__init__(self, k, min_k, sim_options, device)
+        self.bsl_options = bsl_check(bsl_options)
+        self.shrinkage = float(self.sim_options.get("shrinkage", 100))
+
+    def _check_name(self, name):
+        if name not in SIM_NAMES:
+            raise NameError("Wrong sim name " + name + ". Allowed values " + "are " + ", ".join(SIM_NAMES) + ".")
+
+    def _similarity(self, dense_mask, xr, dw):
+        if self.name in _METHOD:
+            return _SymmetricKNN._similarity(self, dense_mask, xr, dw)
+        kw = {"w": dw, "min_support": self.sim_options.get("min_support", 1)}
+        if self.name == "pearson_baseline":
+            bu, bi = baselines(self.trainset, self.bsl_options, self.device)
+            self.bx, self.by = (bu, bi) if self.sim_options["user_based"] else (bi, bu)
+            kw.update(global_mean=self.trainset.global_mean, bx=self.bx, by=self.by, shrinkage=self.shrinkage)
+        if dense_mask is not None:
+            return similarity_pearson(dense_mask[0], dense_mask[1], self.name, **kw)
+        return similarity_pearson_sparse(xr, self.n_y, self.name, **kw)
+
+    def fit(self, trainset, weights=None):
+        if weights is not None:
+            w = self._weights(trainset, weights)
+        elif self.name in _METHOD:                              # the old kernels take their weights as given: ones
+            w = np.ones(trainset.n_items if self.sim_options["user_based"] else trainset.n_users)
+        else:
+            w = None
+        return self._fit(trainset, w)

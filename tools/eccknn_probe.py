@@ -3,6 +3,7 @@ kernels compute is the business of tests/test_gpu_eccknn.py.
 
     python tools/eccknn_probe.py [--users 6040 --items 3706 --ratings 1000000 --queries 200000 --k 20 --repeats 7]
                                  [--form dense|sparse|both] [--shape ml1m|30music-users]
+                                 [--sim cosine|msd|pearson|pearson_baseline] [--baselines]
 
 Prints one JSON line: medians over `repeats` timed runs after two warm-up runs, each run bracketed by device events;
 pair-y updates per second of the similarity kernel (every pair of the upper triangle of 64x64 tiles visits every y, the
@@ -14,6 +15,10 @@ published MI355X figure; an update is counted as the 5 flops of the cosine form)
           `check_plus_sim_ms` the CSR check and the kernel), or both: the two on the same data in one session, and an
           assertion that their `sim` matrices are equal by bytes.  Every form also prints `useful_updates` =
           sum over y of |raters(y)|^2, the updates the reference's loops make, and the rate against it.
+--sim     cosine / msd (EccenKNN's kernels) or pearson / pearson_baseline (KNNBasic's, with the same weights; the second
+          one with the trainset's ALS baselines, computed once outside the timed region).  The numpy restatement is timed
+          for cosine / msd only.  ml1m shape only for the Pearson names.
+--baselines  also time eccknn.baselines (10 ALS epochs, both sides, uploads included) as `baselines_ms`.
 --shape   ml1m (the default; --users / --items / --ratings apply) or 30music-users: 4e4 users x 5e6 items, 3e7 ratings,
           power-law items and users, de-duplicated on (user, item).  Past the dense limit, so sparse only; the estimate
           and predict timings are skipped, `fit_ms` is the sort, the check and the kernel once, and
@@ -71,6 +76,8 @@ def useful_updates(y, n_y):
 
 def numpy_subset(res, x, y, r, w, subset, sim):
     import eccknn_reference as E
+    if sim not in E.NUMPY:
+        return
     keep = x < subset
     yr_sub = E.build_yr(x[keep], y[keep], r[keep])
     t0 = time.perf_counter()
@@ -138,13 +145,16 @@ def main(argv=None):
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--numpy-subset", type=int, default=300)
-    ap.add_argument("--sim", default="cosine")
+    ap.add_argument("--sim", default="cosine", choices=["cosine", "msd", "pearson", "pearson_baseline"])
+    ap.add_argument("--baselines", action="store_true")
     ap.add_argument("--form", default="dense", choices=["dense", "sparse", "both"])
     ap.add_argument("--shape", default="ml1m", choices=["ml1m", "30music-users"])
     a = ap.parse_args(argv)
     if a.shape == "30music-users":
         if a.form != "sparse":
             ap.error("--shape 30music-users is past the dense limit: --form sparse")
+        if a.sim.startswith("pearson") or a.baselines:
+            ap.error("--shape 30music-users times cosine / msd only")
         return big_shape(a)
     import torch
     from n2v_hip import eccknn
@@ -158,25 +168,36 @@ def main(argv=None):
     res = {"metric": "eccknn_probe", "device": torch.cuda.get_device_name(0), "shape": a.shape, "form": a.form, "n_x": n_x,
            "n_y": n_y, "ratings": len(r), "queries": a.queries, "k": a.k, "sim": a.sim, "repeats": a.repeats,
            "useful_updates": useful_updates(ts.i, n_y)}
+    if a.baselines:
+        res["baselines_ms"] = timed(lambda: eccknn.baselines(ts, device=dev), a.repeats)
+    if a.sim.startswith("pearson"):
+        kw = {"w": dw}
+        if a.sim == "pearson_baseline":
+            bx, by = eccknn.baselines(ts, device=dev)
+            kw.update(global_mean=ts.global_mean, bx=bx, by=by)
+        sim_dense = lambda dense, mask: eccknn.similarity_pearson(dense, mask, a.sim, **kw)
+        sim_sparse = lambda xr: eccknn.similarity_pearson_sparse(xr, n_y, a.sim, **kw)
+    else:
+        sim_dense = lambda dense, mask: eccknn.similarity(dense, mask, dw, a.sim)
+        sim_sparse = lambda xr: eccknn.similarity_sparse(xr, dw, n_y, a.sim)
     sim = None
     if a.form in ("dense", "both"):
         dense, mask = eccknn.densify(dx, dy, dr, n_x, n_y)
-        res["sim_kernel_ms"] = timed(lambda: eccknn.similarity(dense, mask, dw, a.sim), a.repeats)
-        res["densify_plus_sim_ms"] = timed(lambda: eccknn.similarity(*eccknn.densify(dx, dy, dr, n_x, n_y), dw, a.sim),
-                                           a.repeats)
+        res["sim_kernel_ms"] = timed(lambda: sim_dense(dense, mask), a.repeats)
+        res["densify_plus_sim_ms"] = timed(lambda: sim_dense(*eccknn.densify(dx, dy, dr, n_x, n_y)), a.repeats)
         tiles = (n_x + 63) // 64
         updates = tiles * (tiles + 1) // 2 * 64 * 64 * n_y
         res["pair_y_updates_per_s"] = updates / (res["sim_kernel_ms"][0] * 1e-3)
         res["fraction_of_fp64_vector_peak"] = res["pair_y_updates_per_s"] * 5 / FP64_VECTOR_PEAK
         res["dense_useful_updates_per_s"] = res["useful_updates"] / (res["sim_kernel_ms"][0] * 1e-3)
-        sim = eccknn.similarity(dense, mask, dw, a.sim)
+        sim = sim_dense(dense, mask)
         del dense, mask
     if a.form in ("sparse", "both"):
         xr = eccknn.csr_by_x(dx, dy, dr, n_x, n_y)
         res["csr_by_x_ms"] = timed(lambda: eccknn.csr_by_x(dx, dy, dr, n_x, n_y), a.repeats)
-        res["check_plus_sim_ms"] = timed(lambda: eccknn.similarity_sparse(xr, dw, n_y, a.sim), a.repeats)
+        res["check_plus_sim_ms"] = timed(lambda: sim_sparse(xr), a.repeats)
         res["sparse_useful_updates_per_s"] = res["useful_updates"] / (res["check_plus_sim_ms"][0] * 1e-3)
-        sparse = eccknn.similarity_sparse(xr, dw, n_y, a.sim)
+        sparse = sim_sparse(xr)
         if sim is not None:
             assert torch.equal(sim.view(torch.int64), sparse.view(torch.int64)), "dense and sparse sim differ"
             res["sim_equal_by_bytes"] = True
