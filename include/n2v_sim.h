@@ -178,6 +178,55 @@ int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, c
 int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,
                        double lo, double hi, double* pred, double* rmse, void* stream);
 
+/* ---- Matrix factorisation: surprise's SVD under a deterministic stratified schedule (csrc/n2v_svd.hip) --------------
+ * The third algorithm of src/main_rec.py:341-348 (`-algo svd`, surprise 1.0.6's SVD).  surprise is not a dependency: the
+ * model and the update below are its arithmetic restated from memory, parity with surprise itself is UNPINNED, and
+ * tests/svd_reference.py is the definition the kernels equal bit for bit.  Everything is fp64 without fused
+ * multiply-add, every expression evaluated as written, left to right.  Per rating (u, i, r), with puf / qif the values
+ * before the rating:
+ *   dot = sum over f of qi[i][f] * pu[u][f]                      (the order: below)
+ *   err = r - (((mu + bu[u]) + bi[i]) + dot)                     biased;   err = r - dot   otherwise
+ *   bu[u] = bu[u] + lr_bu * (err - reg_bu * bu[u]);  bi[i] = bi[i] + lr_bi * (err - reg_bi * bi[i])      biased only
+ *   pu[u][f] = puf + lr_pu * (err * qif - reg_pu * puf);  qi[i][f] = qif + lr_qi * (err * puf - reg_qi * qif)
+ * The dot: lane l of a wavefront starts from +0.0 and adds the products of the factors l, l + 64, l + 128, l + 192 that
+ * exist, ascending; then v = v + v[lane ^ m] for m = 32, 16, 8, 4, 2, 1.  Addition commutes, so all 64 lanes end with
+ * the same value and err needs no broadcast.  (A NaN's sign and payload are not part of the contract.)
+ *
+ * The schedule, P = n_strata: user u is in block ub = (u * P) / n_users, item i in ib = (i * P) / n_items (64-bit
+ * integers), a rating in stratum s = (ib - ub) mod P and there in block ub.  One epoch applies the blocks in the order
+ * `for s: for ub:`, and inside a block the ratings in the order given (ascending u, then training order).  Two blocks
+ * of one stratum share no user and no item, so one wavefront per block and one launch per stratum — stream order is
+ * the only barrier, there are no atomics on the model — give exactly the result of that sequential loop.  P = 1 is
+ * surprise's own order.  Blocks may be empty.
+ * blk_ptr: int64[P * P + 1], block (s, ub) is [blk_ptr[s * P + ub], blk_ptr[s * P + ub + 1]); blk_u, blk_i: int32[n];
+ * blk_r: fp64[n].  n2v_svd_blocks_check (integers only; reads nothing outside blk_ptr[0 .. P * P] and the n entries)
+ * names what is wrong by bits of *status (int32, device, cleared by the caller).  n2v_svd_epoch is only defined on lists
+ * that pass it: it clamps every range to [0, n] and skips a rating whose ids are out of range, so a malformed list is no
+ * out-of-bounds access, but two blocks of a stratum that share a row would race.                                       */
+#define N2V_SVD_BAD_PTR 1       /* blk_ptr does not start at 0, is not monotone, or leaves [0, n]                     */
+#define N2V_SVD_BAD_END 2       /* blk_ptr[P * P] != n                                                                 */
+#define N2V_SVD_BAD_ID 4        /* a blk_u outside [0, n_users) or a blk_i outside [0, n_items)                        */
+#define N2V_SVD_WRONG_BLOCK 8   /* a rating outside the range of the block (s, ub) its ids put it in                   */
+#define N2V_SVD_UNSORTED 16     /* inside a block, a blk_u below its predecessor                                       */
+int32_t n2v_svd_max_factors(void);   /* 256: four factors a lane                                                       */
+int32_t n2v_svd_max_strata(void);    /* 32768                                                                          */
+int n2v_svd_blocks_check(const int64_t* blk_ptr, const int32_t* blk_u, const int32_t* blk_i, int64_t n_strata,
+                         int64_t n_users, int64_t n_items, int64_t n, int32_t* status, void* stream);
+/* One epoch: n_strata launches.  bu: fp64[n_users], bi: fp64[n_items], pu: fp64[n_users][n_factors],
+ * qi: fp64[n_items][n_factors], updated in place; bu and bi are neither read nor written when biased == 0.
+ * 1 <= n_factors <= 256, 1 <= n_strata <= 32768, n >= 1.                                                              */
+int n2v_svd_epoch(const int64_t* blk_ptr, const int32_t* blk_u, const int32_t* blk_i, const double* blk_r,
+                  int64_t n_strata, int64_t n_users, int64_t n_items, int64_t n, int32_t n_factors, double mu,
+                  int32_t biased, double lr_bu, double lr_bi, double lr_pu, double lr_qi, double reg_bu, double reg_bi,
+                  double reg_pu, double reg_qi, double* bu, double* bi, double* pu, double* qi, void* stream);
+/* One wavefront per query (q_u[q], q_i[q]); an id outside its range (-1) is unknown.  The same dot, through the same
+ * device function.  biased: est = mu, + bu[u] if the user is known, + bi[i] if the item is, + dot if both are, in that
+ * order; impossible = 0.  Otherwise est = dot if both are known, else est = 0 and impossible = 1 ('User and item are
+ * unknown.').  Before any fallback or clipping: n2v_eccknn_predict does those.  n_q >= 1.                             */
+int n2v_svd_estimate(const double* bu, const double* bi, const double* pu, const double* qi, int64_t n_users,
+                     int64_t n_items, int32_t n_factors, double mu, int32_t biased, const int32_t* q_u, const int32_t* q_i,
+                     int64_t n_q, double* est, uint8_t* impossible, void* stream);
+
 /* ---- Eccentricity statistics: the ir / ie / ire / ier item weights and the per-user ue (csrc/n2v_eccstats.hip) -----
  * Replaces src/utils.py:53-153 (pandas group-bys and merges).  Rows are (user, item, feedback, timewindow) with inner
  * ids; a group is a distinct (item, timewindow) pair, numbered in ascending (item, timewindow) order.  Everything is

@@ -1,0 +1,266 @@
+// Matrix factorisation on the device: surprise's SVD (biases + factors, plain SGD) under a deterministic stratified
+// schedule.  C-ABI and the full definition: include/n2v_sim.h ("Matrix factorisation"); the restatement the kernels
+// equal bit for bit: tests/svd_reference.py.  Parity with surprise itself is UNPINNED (it is not a dependency).
+//
+//   blocks_check_kernel  integers only: one lane per entry of blk_ptr and per rating, names a malformed block list.
+//   epoch_kernel<NS>     one launch per stratum, one wavefront per block (a 64-thread workgroup).  Lane l owns the
+//                        factors l + 64 * k, k < NS, of both rows, so a rating is two row reads, one 64-lane xor
+//                        butterfly for the dot and two row writes.  The blocks of a stratum share no user and no item:
+//                        the wavefronts of one launch touch disjoint rows, and the next stratum is the next launch.
+//                        Inside a block the ratings of one user are consecutive, so pu[u] and bu[u] stay in registers
+//                        until the user changes, and the next rating's (u, i, r), qi row and bi are fetched before the
+//                        current rating's arithmetic; where the next item is the current one, the registers just
+//                        computed are handed over instead.  Neither changes an operation or its order.
+//   estimate_kernel<NS>  one wavefront per query, the same lane_dot.
+// fp64 throughout; -ffp-contract=off (csrc/Makefile) keeps every multiply and add separately rounded.
+#include "n2v_common.h"
+#include "n2v_sim.h"
+
+namespace {
+
+constexpr int MAX_FACTORS = 256;
+constexpr int MAX_STRATA = 32768;
+
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// ---- the block list ---------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) blocks_check_kernel(const int64_t* __restrict__ blk_ptr, const int32_t* __restrict__ blk_u,
+                                                           const int32_t* __restrict__ blk_i, int64_t P, int64_t n_users,
+                                                           int64_t n_items, int64_t n, int32_t* __restrict__ status) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t n_blk = P * P;
+    int32_t bits = 0;
+    if (t < n_blk) {
+        const int64_t pb = blk_ptr[t], pe = blk_ptr[t + 1];
+        if (pb < 0 || pb > n || pe < 0 || pe > n || pe < pb || (t == 0 && pb != 0)) bits |= N2V_SVD_BAD_PTR;
+        if (t == n_blk - 1 && pe != n) bits |= N2V_SVD_BAD_END;
+    }
+    if (t < n) {
+        const int64_t u = blk_u[t], i = blk_i[t];
+        if (u < 0 || u >= n_users || i < 0 || i >= n_items) {
+            bits |= N2V_SVD_BAD_ID;
+        } else {
+            const int64_t ub = (u * P) / n_users, ib = (i * P) / n_items;
+            const int64_t k = ((ib - ub + P) % P) * P + ub;       // < P * P
+            const int64_t pb = blk_ptr[k];
+            if (t < pb || t >= blk_ptr[k + 1]) bits |= N2V_SVD_WRONG_BLOCK;
+            else if (t > pb && t > 0 && blk_u[t - 1] > u) bits |= N2V_SVD_UNSORTED;
+        }
+    }
+    if (bits) atomicOr(status, bits);
+}
+
+// ---- the rows and the dot ---------------------------------------------------------------------------------------------
+
+template <int NS>
+__device__ __forceinline__ void load_row(const double* row, int nf, int lane, double (&x)[NS]) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k) x[k] = lane + 64 * k < nf ? row[lane + 64 * k] : 0.0;
+}
+
+template <int NS>
+__device__ __forceinline__ void store_row(double* row, int nf, int lane, const double (&x)[NS]) {
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+        if (lane + 64 * k < nf) row[lane + 64 * k] = x[k];
+}
+
+// The dot of the definition; every lane returns the same value.
+template <int NS>
+__device__ __forceinline__ double lane_dot(const double (&q)[NS], const double (&p)[NS], int nf, int lane) {
+    double v = 0.0;
+#pragma unroll
+    for (int k = 0; k < NS; ++k)
+        if (lane + 64 * k < nf) v = v + q[k] * p[k];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
+    return v;
+}
+
+// ---- one stratum ------------------------------------------------------------------------------------------------------
+
+struct EpochArgs {
+    const int64_t* blk_ptr; const int32_t* blk_u; const int32_t* blk_i; const double* blk_r;
+    int64_t P, s, n_users, n_items, n;
+    int nf, biased;
+    double mu, lr_bu, lr_bi, lr_pu, lr_qi, reg_bu, reg_bi, reg_pu, reg_qi;
+    double* bu; double* bi; double* pu; double* qi;
+};
+
+template <int NS>
+__global__ void __launch_bounds__(64) epoch_kernel(EpochArgs a) {
+    const int lane = threadIdx.x;
+    const int nf = a.nf;
+    const int64_t blk = a.s * a.P + blockIdx.x;
+    const int64_t pb = clamp64(a.blk_ptr[blk], 0, a.n), pe = clamp64(a.blk_ptr[blk + 1], pb, a.n);
+    if (pb >= pe) return;
+
+    int64_t cu = -1;                                              // the user whose row is in p / b_u
+    double p[NS], b_u = 0.0;
+    // the next rating, fetched one rating ahead
+    int64_t u_n = a.blk_u[pb], i_n = a.blk_i[pb];
+    double r_n = a.blk_r[pb], q_n[NS], b_in = 0.0;
+    bool ok_n = u_n >= 0 && u_n < a.n_users && i_n >= 0 && i_n < a.n_items;
+    if (ok_n) {
+        load_row<NS>(a.qi + i_n * nf, nf, lane, q_n);
+        if (a.biased) b_in = a.bi[i_n];
+    }
+    for (int64_t pos = pb; pos < pe; ++pos) {
+        const int64_t u = u_n, i = i_n;
+        const double r = r_n;
+        const bool ok = ok_n, more = pos + 1 < pe;
+        double q[NS], b_i = b_in;
+#pragma unroll
+        for (int k = 0; k < NS; ++k) q[k] = q_n[k];
+        if (ok && u != cu) {                                      // the user changes: write the old row, read the new one
+            if (cu >= 0) {
+                store_row<NS>(a.pu + cu * nf, nf, lane, p);
+                if (a.biased && lane == 0) a.bu[cu] = b_u;
+            }
+            load_row<NS>(a.pu + u * nf, nf, lane, p);
+            if (a.biased) b_u = a.bu[u];
+            cu = u;
+        }
+        if (more) {
+            u_n = a.blk_u[pos + 1]; i_n = a.blk_i[pos + 1]; r_n = a.blk_r[pos + 1];
+            ok_n = u_n >= 0 && u_n < a.n_users && i_n >= 0 && i_n < a.n_items;
+            if (ok_n && !(ok && i_n == i)) {                      // the same item: handed over below
+                load_row<NS>(a.qi + i_n * nf, nf, lane, q_n);
+                if (a.biased) b_in = a.bi[i_n];
+            }
+        }
+        if (!ok) continue;                                        // only a list that fails blocks_check has one
+
+        const double dot = lane_dot<NS>(q, p, nf, lane);
+        const double err = a.biased ? r - (((a.mu + b_u) + b_i) + dot) : r - dot;
+        if (a.biased) {
+            b_u = b_u + a.lr_bu * (err - a.reg_bu * b_u);
+            b_i = b_i + a.lr_bi * (err - a.reg_bi * b_i);
+            if (lane == 0) a.bi[i] = b_i;
+        }
+#pragma unroll
+        for (int k = 0; k < NS; ++k) {
+            const double puf = p[k], qif = q[k];
+            p[k] = puf + a.lr_pu * (err * qif - a.reg_pu * puf);
+            q[k] = qif + a.lr_qi * (err * puf - a.reg_qi * qif);
+        }
+        store_row<NS>(a.qi + i * nf, nf, lane, q);
+        if (more && ok_n && i_n == i) {
+#pragma unroll
+            for (int k = 0; k < NS; ++k) q_n[k] = q[k];
+            b_in = b_i;
+        }
+    }
+    if (cu >= 0) {
+        store_row<NS>(a.pu + cu * nf, nf, lane, p);
+        if (a.biased && lane == 0) a.bu[cu] = b_u;
+    }
+}
+
+// ---- estimate ---------------------------------------------------------------------------------------------------------
+
+struct EstArgs {
+    const double* bu; const double* bi; const double* pu; const double* qi;
+    int64_t n_users, n_items, n_q;
+    int nf, biased;
+    double mu;
+    const int32_t* q_u; const int32_t* q_i;
+    double* est; uint8_t* impossible;
+};
+
+template <int NS>
+__global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
+    const int lane = threadIdx.x;
+    const int64_t qn = blockIdx.x;
+    const int64_t u = a.q_u[qn], i = a.q_i[qn];
+    const bool ku = u >= 0 && u < a.n_users, ki = i >= 0 && i < a.n_items;
+    double dot = 0.0;
+    if (ku && ki) {                                               // wave-uniform
+        double p[NS], q[NS];
+        load_row<NS>(a.pu + u * a.nf, a.nf, lane, p);
+        load_row<NS>(a.qi + i * a.nf, a.nf, lane, q);
+        dot = lane_dot<NS>(q, p, a.nf, lane);
+    }
+    if (lane != 0) return;
+    double est;
+    bool imp = false;
+    if (a.biased) {
+        est = a.mu;
+        if (ku) est = est + a.bu[u];
+        if (ki) est = est + a.bi[i];
+        if (ku && ki) est = est + dot;
+    } else {
+        imp = !(ku && ki);                                        // 'User and item are unknown.'
+        est = imp ? 0.0 : dot;
+    }
+    a.est[qn] = est;
+    a.impossible[qn] = imp ? 1 : 0;
+}
+
+#define N2V_SVD_DISPATCH(KERNEL, nf, ...)                                     \
+    do {                                                                      \
+        if ((nf) <= 64) KERNEL<1> __VA_ARGS__;                                \
+        else if ((nf) <= 128) KERNEL<2> __VA_ARGS__;                          \
+        else if ((nf) <= 192) KERNEL<3> __VA_ARGS__;                          \
+        else KERNEL<4> __VA_ARGS__;                                           \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int32_t n2v_svd_max_factors(void) { return MAX_FACTORS; }
+int32_t n2v_svd_max_strata(void) { return MAX_STRATA; }
+
+int n2v_svd_blocks_check(const int64_t* blk_ptr, const int32_t* blk_u, const int32_t* blk_i, int64_t n_strata,
+                         int64_t n_users, int64_t n_items, int64_t n, int32_t* status, void* stream) {
+    if (n_strata < 1 || n_strata > MAX_STRATA || n_users < 1 || n_items < 1 || n < 1 || n_users > 0x7fffffffLL ||
+        n_items > 0x7fffffffLL)
+        return n2v::fail(N2V_ERR_INVALID, "svd_blocks_check: n_strata=%lld n_users=%lld n_items=%lld n=%lld", (long long)n_strata,
+                         (long long)n_users, (long long)n_items, (long long)n);
+    if (!blk_ptr || !blk_u || !blk_i || !status) return n2v::fail(N2V_ERR_INVALID, "svd_blocks_check: null pointer");
+    const int64_t lanes = n_strata * n_strata > n ? n_strata * n_strata : n;
+    if (lanes > (int64_t)0x7fffffff * 256) return n2v::fail(N2V_ERR_INVALID, "svd_blocks_check: too many blocks or ratings");
+    blocks_check_kernel<<<n2v::grid_for(lanes, 256), 256, 0, (hipStream_t)stream>>>(blk_ptr, blk_u, blk_i, n_strata, n_users,
+                                                                                   n_items, n, status);
+    return n2v::check_launch("svd_blocks_check");
+}
+
+int n2v_svd_epoch(const int64_t* blk_ptr, const int32_t* blk_u, const int32_t* blk_i, const double* blk_r,
+                  int64_t n_strata, int64_t n_users, int64_t n_items, int64_t n, int32_t n_factors, double mu,
+                  int32_t biased, double lr_bu, double lr_bi, double lr_pu, double lr_qi, double reg_bu, double reg_bi,
+                  double reg_pu, double reg_qi, double* bu, double* bi, double* pu, double* qi, void* stream) {
+    if (n_strata < 1 || n_strata > MAX_STRATA || n_users < 1 || n_items < 1 || n < 1 || n_users > 0x7fffffffLL ||
+        n_items > 0x7fffffffLL)
+        return n2v::fail(N2V_ERR_INVALID, "svd_epoch: n_strata=%lld n_users=%lld n_items=%lld n=%lld", (long long)n_strata,
+                         (long long)n_users, (long long)n_items, (long long)n);
+    if (n_factors < 1 || n_factors > MAX_FACTORS)
+        return n2v::fail(N2V_ERR_INVALID, "svd_epoch: n_factors %d outside [1, %d]", n_factors, MAX_FACTORS);
+    if (!blk_ptr || !blk_u || !blk_i || !blk_r || !pu || !qi || (biased && (!bu || !bi)))
+        return n2v::fail(N2V_ERR_INVALID, "svd_epoch: null pointer");
+    EpochArgs a{blk_ptr, blk_u, blk_i, blk_r, n_strata, 0, n_users, n_items, n, n_factors, biased ? 1 : 0, mu,
+                lr_bu, lr_bi, lr_pu, lr_qi, reg_bu, reg_bi, reg_pu, reg_qi, bu, bi, pu, qi};
+    for (int64_t s = 0; s < n_strata; ++s) {                      // stream order is the barrier between strata
+        a.s = s;
+        N2V_SVD_DISPATCH(epoch_kernel, n_factors, <<<(unsigned)n_strata, 64, 0, (hipStream_t)stream>>>(a));
+    }
+    return n2v::check_launch("svd_epoch");
+}
+
+int n2v_svd_estimate(const double* bu, const double* bi, const double* pu, const double* qi, int64_t n_users,
+                     int64_t n_items, int32_t n_factors, double mu, int32_t biased, const int32_t* q_u, const int32_t* q_i,
+                     int64_t n_q, double* est, uint8_t* impossible, void* stream) {
+    if (n_users < 1 || n_items < 1 || n_q < 1 || n_q > 0x7fffffffLL)
+        return n2v::fail(N2V_ERR_INVALID, "svd_estimate: n_users=%lld n_items=%lld n_q=%lld", (long long)n_users,
+                         (long long)n_items, (long long)n_q);
+    if (n_factors < 1 || n_factors > MAX_FACTORS)
+        return n2v::fail(N2V_ERR_INVALID, "svd_estimate: n_factors %d outside [1, %d]", n_factors, MAX_FACTORS);
+    if (!pu || !qi || !q_u || !q_i || !est || !impossible || (biased && (!bu || !bi)))
+        return n2v::fail(N2V_ERR_INVALID, "svd_estimate: null pointer");
+    EstArgs a{bu, bi, pu, qi, n_users, n_items, n_q, n_factors, biased ? 1 : 0, mu, q_u, q_i, est, impossible};
+    N2V_SVD_DISPATCH(estimate_kernel, n_factors, <<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a));
+    return n2v::check_launch("svd_estimate");
+}
+
+}  // extern "C"

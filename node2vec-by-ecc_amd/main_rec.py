@@ -5,12 +5,19 @@ plain k-NN (surprise's KNNBasic) it is compared against.
                        [-shrinkage 100] [-item-based] [-weights FILE]
                        [-mode ir|ie|ire|ier] [-window-col timestamp|timewindow] [-save-weights FILE]
                        [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
+    python main_rec.py -input ratings.csv -algo mf [-factors 100] [-epochs 20] [-lr 0.005] [-reg 0.02] [-strata N|auto]
+                       [-unbiased] [-test-ratio 0.2] [-seed 0] [-cv N]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
 -algo     eccen (the default) or knn: KNNBasic, which also takes -sim pearson and pearson_baseline (surprise's functions,
           restated; parity with surprise is unpinned) and -shrinkage for the latter.  With -algo knn, -weights / -mode
           weight the baseline's co-ratings, as the reference meant to (src/main_rec.py:197); absent, there are no weights.
-          svd is not built.
+          mf: matrix factorisation, the model and SGD update of surprise's SVD (restated; parity with surprise is
+          unpinned) trained on the device under a deterministic stratified order of the ratings (n2v_hip.svd): -factors,
+          -epochs, -lr and -reg are surprise's n_factors, n_epochs, lr_all and reg_all, -strata the number of strata (auto:
+          chosen from the size of the training set; 1: surprise's own order), -unbiased drops the biases, and -seed also
+          seeds the factors.  It takes none of -sim, -k, -mink, -weights, -mode, -item-based and -form.
+          svd itself is not built: surprise's order of the ratings is sequential, and -algo mf follows it only with -strata 1.
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
 -mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
           rarity, item eccentricity, their product or their quotient, from the WHOLE input file before the split, as the
@@ -34,9 +41,9 @@ def parse_args(argv=None):
     p.add_argument("-input", required=True)
     p.add_argument("-algo", default="eccen")
     p.add_argument("-shrinkage", type=float, default=100)
-    p.add_argument("-k", type=int, default=40)
-    p.add_argument("-mink", type=int, default=1)
-    p.add_argument("-sim", default="cosine")
+    p.add_argument("-k", type=int, default=None)
+    p.add_argument("-mink", type=int, default=None)
+    p.add_argument("-sim", default=None)
     p.add_argument("-item-based", dest="item_based", action="store_true")
     p.add_argument("-min-support", dest="min_support", type=int, default=1)
     p.add_argument("-weights", default=None)
@@ -46,13 +53,42 @@ def parse_args(argv=None):
     p.add_argument("-test-ratio", dest="test_ratio", type=float, default=0.2)
     p.add_argument("-seed", type=int, default=0)
     p.add_argument("-cv", type=int, default=0)
-    p.add_argument("-form", default="auto", choices=["auto", "dense", "sparse"])
+    p.add_argument("-form", default=None, choices=["auto", "dense", "sparse"])
+    p.add_argument("-factors", type=int, default=None)
+    p.add_argument("-epochs", type=int, default=None)
+    p.add_argument("-lr", type=float, default=None)
+    p.add_argument("-reg", type=float, default=None)
+    p.add_argument("-strata", default=None)
+    p.add_argument("-unbiased", action="store_true")
     p.add_argument("-device", default="cuda:0")
     a = p.parse_args(argv)
     if a.algo == "svd":
-        p.error("-algo svd is not built: eccen or knn")
-    if a.algo not in ("eccen", "knn"):
-        p.error("-algo %s: eccen or knn" % a.algo)
+        p.error("-algo svd is not built: surprise's SVD applies the ratings in one sequential order.  -algo mf is the same "
+                "model and update under a deterministic stratified order (equal to surprise's only with -strata 1)")
+    if a.algo not in ("eccen", "knn", "mf"):
+        p.error("-algo %s: eccen, knn or mf" % a.algo)
+    knn_flags = (("-sim", a.sim), ("-k", a.k), ("-mink", a.mink), ("-weights", a.weights), ("-mode", a.mode),
+                 ("-item-based", a.item_based or None), ("-form", a.form))
+    mf_flags = (("-factors", a.factors), ("-epochs", a.epochs), ("-lr", a.lr), ("-reg", a.reg), ("-strata", a.strata),
+                ("-unbiased", a.unbiased or None))
+    for flag, v in (knn_flags if a.algo == "mf" else mf_flags):
+        if v is not None:
+            p.error("%s does not go with -algo %s" % (flag, a.algo))
+    for name, v in (("k", 40), ("mink", 1), ("sim", "cosine"), ("form", "auto"), ("factors", 100), ("epochs", 20),
+                    ("lr", 0.005), ("reg", 0.02), ("strata", "auto")):
+        if getattr(a, name) is None:
+            setattr(a, name, v)
+    if a.strata != "auto":
+        try:
+            a.strata = int(a.strata)
+        except ValueError:
+            p.error("-strata %s: a number or auto" % a.strata)
+    if a.algo == "mf":
+        from n2v_hip import svd
+        try:
+            svd.SVD(n_factors=a.factors, n_epochs=a.epochs, lr_all=a.lr, reg_all=a.reg, n_strata=a.strata)
+        except ValueError as e:
+            p.error(str(e))
     if a.sim in ("pearson", "pearson_baseline") and a.algo != "knn":
         p.error("-sim %s is surprise's own similarity: it needs -algo knn" % a.sim)
     if not 0.0 < a.test_ratio < 1.0:
@@ -158,6 +194,12 @@ def run_split(args, users, items, ratings, weights, train, test):
     from n2v_hip import eccknn
     ts = eccknn.Trainset.from_ratings([users[i] for i in train], [items[i] for i in train], ratings[train],
                                       rating_scale=(float(ratings.min()), float(ratings.max())))
+    if args.algo == "mf":
+        from n2v_hip import svd
+        algo = svd.SVD(n_factors=args.factors, n_epochs=args.epochs, biased=not args.unbiased, lr_all=args.lr,
+                       reg_all=args.reg, random_state=args.seed, n_strata=args.strata, device=args.device)
+        algo.fit(ts)
+        return algo.rmse([(users[i], items[i], ratings[i]) for i in test])
     sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
     if args.algo == "knn":
         sim_options["shrinkage"] = args.shrinkage
