@@ -371,7 +371,22 @@ int32_t n2v_sgns_default_blocks(int64_t n_words, int32_t update_mode);
  * pass: the last cold sum is folded in and x = xs = base on every row — identical tables on all ranks.
  * wire_bf16 != 0: the wire buffers hold bfloat16 (round to nearest even), else float.  Tables are
  * fp32[n_rows][stride]; wire buffers [n_rows][stride] (cold; hot rows' entries are written as 0) and
- * [n_hot][stride] (hot).  w: float[n_rows] weight on the SUM of the changes (1 = sum, 1/world = mean).     */
+ * [n_hot][stride] (hot).  w: float[n_rows] weight on the SUM of the changes (1 = sum, 1/world = mean).
+ * Arithmetic: IEEE float32, one rounding per operation (base + w * S is a product and a sum, never fused),
+ * subnormal changes are kept, the sign of zero is kept; the bfloat16 wire rounds to nearest even, subnormals and
+ * the overflow to inf included.  A NaN stays a NaN on either wire, but its sign and payload are not part of the
+ * contract (a bit-for-bit comparison against another implementation compares NaNs by position).
+ * Preconditions the entry points CANNOT check — each would be an out-of-range access on the device:
+ *  - a cold row (hot_pos NULL, or hot_pos[r] < 0) while cold_wire is NULL: cold_wire may be NULL only when
+ *    EVERY row is hot;
+ *  - hot_pos[r] >= 0 must be below the hot wire's row count; entries of hot_rows and of every row list must be
+ *    rows of their table (0 <= row < its height);
+ *  - a row list that is APPLIED (n2v_merge_hot_apply, n2v_tsum_apply) holds no row twice: two wavefronts would
+ *    fold into the same row.  A list that is only packed (n2v_merge_pack_rows, n2v_tsum_pack) may repeat rows,
+ *    and no list has to be sorted.
+ * Rejected arguments (negative counts, stride < 1, a NULL pointer that a non-zero count needs, n_tabs outside
+ * 0 .. N2V_TSUM_MAX_TABLES, more than 4 * (2^31 - 1) rows in one call) return N2V_ERR_INVALID before anything
+ * is launched; zero counts return N2V_OK whatever the pointers.                                              */
 int n2v_merge_snapshot(float* x, float* xs, float* base, int64_t n_rows, int32_t stride, const float* w,
                        const int32_t* hot_pos, const void* cold_sum_prev, void* cold_wire, void* hot_wire,
                        int32_t wire_bf16, void* stream);
