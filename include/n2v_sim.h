@@ -278,6 +278,63 @@ int n2v_eccstats_moments(const double* x, int64_t n, double* scratch, double* st
 int n2v_eccstats_finish(int32_t op, const double* a, const double* b, const double* stats, int64_t n, double* out,
                         void* stream);
 
+/* ---- Eccentricity split: ue -> n bins of users -> one bipartite user-item CSR graph per bin (csrc/n2v_eccsplit.hip) -----
+ * Replaces src/utils.py:305-312 (mark_n), :382-405 (split_and_save_edgelist, save_edgelist) and the read-back of each
+ * file by src/main.py:66-80.  Rows are (user, item, weight) with inner ids (int64) in file order; the graph of a set of
+ * rows is the one csr.from_edges(user name, item name, weight, directed=False) builds on the host: a repeated (user,
+ * item) row keeps its last weight, every surviving pair gives the entries u -> i and i -> u, the dense id of a node is
+ * the rank of its name among the graph's names, start_order is first appearance (user before item on a row).  Integer
+ * arithmetic only: weights are moved by their bytes (NaN payloads, inf and -0.0 included), never added.  The sorts are the
+ * caller's (stable, ascending, int64 keys).  Workgroups meet only at launch boundaries: no result depends on dispatch
+ * order.  Limits: every size (n_rows, n_users + n_items, n_bins, 2 * selected rows) is at most 2^31 - 1, so the keys
+ * dense_u * N + dense_i stay below 2^62; beyond them N2V_ERR_INVALID.  A size of 0 launches nothing.  Indices are the
+ * caller's promise (check them before the call); the kernels skip or clamp what is outside its range.             */
+#define N2V_ECCSPLIT_TILE 2048                       /* elements per workgroup of the compaction passes             */
+#define N2V_ECCSPLIT_NONE 0x7fffffffffffffffLL       /* first[] of a node that no selected row names                */
+int32_t n2v_eccsplit_tile(void);
+/* int64 words of scratch for a compaction over n elements (select: n_rows, nodes: n_users + n_items, pairs: n_sel). */
+int64_t n2v_eccsplit_scratch(int64_t n);
+
+/* key[i] orders as the split orders ue: ascending, -0.0 and +0.0 equal, every NaN (any sign or payload) after +inf. */
+int n2v_eccsplit_sort_key(const double* ue, int64_t n, int64_t* key, void* stream);
+/* order[r]: the user at rank r of the stable sort by (key, tie rank), a permutation of 0 .. n_users - 1.  Writes
+ * bin[order[r]] = n_bins if n_users / n_bins == 0, else min(r / (n_users / n_bins) + 1, n_bins): int32 in 1 .. n_bins. */
+int n2v_eccsplit_mark(const int64_t* order, int64_t n_users, int64_t n_bins, int32_t* bin, void* stream);
+
+/* rows[0 .. *count): the row numbers k with bin[user[k]] == which (which == 0: every row), ascending; rows holds n_rows
+ * words, count is one device word.  Flag and compaction are one pass over user (ballots per tile, a scan of the tile
+ * counts, a scatter).  scratch: int64[n2v_eccsplit_scratch(n_rows)].                                                 */
+int n2v_eccsplit_select(const int64_t* user, int64_t n_rows, const int32_t* bin, int64_t n_users, int32_t which, int64_t* scratch,
+                        int64_t* rows, int64_t* count, void* stream);
+/* first: int64[n_users + n_items], set to N2V_ECCSPLIT_NONE by the caller.  Over t < min(*n_sel, cap), k = rows[t]:
+ * first[user[k]] = min(.., 2 k), first[n_users + item[k]] = min(.., 2 k + 1), by 64-bit integer atomic minima (any order
+ * gives the same words).  rows NULL: k = t; n_sel NULL: cap rows.  cap <= n_rows.                                  */
+int n2v_eccsplit_first(const int64_t* rows, const int64_t* n_sel, int64_t cap, const int64_t* user, const int64_t* item,
+                       int64_t n_rows, int64_t n_users, int64_t n_items, int64_t* first, void* stream);
+/* The nodes j (users, then items) with first[j] != NONE, in that order, numbered 0 .. *count - 1 ("slots"):
+ * node_name[slot] = user_names[j] or item_names[j - n_users], node_first[slot] = first[j], slot_of[j] = slot, and
+ * slot_of[j] = -1 for the others.  node_name / node_first: int64[n_users + n_items]; slot_of: int32[n_users + n_items];
+ * scratch: int64[n2v_eccsplit_scratch(n_users + n_items)].                                                          */
+int n2v_eccsplit_nodes(const int64_t* first, int64_t n_users, int64_t n_items, const int64_t* user_names, const int64_t* item_names,
+                       int64_t* scratch, int64_t* node_name, int64_t* node_first, int32_t* slot_of, int64_t* count, void* stream);
+/* perm_name / perm_first: the slot at position r of the sort of node_name / node_first (n_nodes entries each).
+ * rank[perm_name[r]] = r (the dense id of a slot); start_order[j] = rank[perm_first[j]].  int32[n_nodes] each.       */
+int n2v_eccsplit_ranks(const int64_t* perm_name, const int64_t* perm_first, int64_t n_nodes, int32_t* rank, int32_t* start_order,
+                       void* stream);
+/* key[t] = rank[slot_of[user[k]]] * n_nodes + rank[slot_of[n_users + item[k]]], k = rows[t] (rows NULL: t), t < n_sel. */
+int n2v_eccsplit_keys(const int64_t* rows, int64_t n_sel, const int64_t* user, const int64_t* item, int64_t n_rows, int64_t n_users,
+                      int64_t n_items, const int32_t* slot_of, const int32_t* rank, int64_t n_nodes, int64_t* key, void* stream);
+/* key_sorted / perm: the stable sort of key (perm[t]: the position in key that sorted position t holds).  The last
+ * element of every run of equal keys survives, numbered p = 0 .. *count - 1 in key order, and gives two entries:
+ * ekey[2 p] = key, ekey[2 p + 1] = its mirror (i * n_nodes + u), ew[2 p] = ew[2 p + 1] = w[rows[perm[t]]] by its bytes.
+ * ekey: int64[2 n_sel]; ew: fp64[2 n_sel]; scratch: int64[n2v_eccsplit_scratch(n_sel)].  2 n_sel < 2^31.            */
+int n2v_eccsplit_pairs(const int64_t* key_sorted, const int64_t* perm, int64_t n_sel, const int64_t* rows, const double* w,
+                       int64_t n_rows, int64_t n_nodes, int64_t* scratch, int64_t* ekey, double* ew, int64_t* count, void* stream);
+/* ekey_sorted / perm: the sort of the nnz = 2 * pairs entries.  row_ptr: int64[n_nodes + 1] (rows without entries are
+ * empty), col[e] = ekey_sorted[e] % n_nodes: int32[nnz], w[e] = ew[perm[e]]: fp64[nnz] by its bytes.                */
+int n2v_eccsplit_fill(const int64_t* ekey_sorted, const int64_t* perm, int64_t nnz, const double* ew, int64_t n_nodes,
+                      int64_t* row_ptr, int32_t* col, double* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,17 @@ SIGNATURES = {
     "n2v_eccstats_moments_scratch": (C.c_int64, [_i64]),
     "n2v_eccstats_moments": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr]),
     "n2v_eccstats_finish": (C.c_int, [_i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr]),
+    "n2v_eccsplit_tile": (C.c_int32, []),
+    "n2v_eccsplit_scratch": (C.c_int64, [_i64]),
+    "n2v_eccsplit_sort_key": (C.c_int, [_ptr, _i64, _ptr, _ptr]),
+    "n2v_eccsplit_mark": (C.c_int, [_ptr, _i64, _i64, _ptr, _ptr]),
+    "n2v_eccsplit_select": (C.c_int, [_ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccsplit_first": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr]),
+    "n2v_eccsplit_nodes": (C.c_int, [_ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccsplit_ranks": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "n2v_eccsplit_keys": (C.c_int, [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr]),
+    "n2v_eccsplit_pairs": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccsplit_fill": (C.c_int, [_ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
 }
 
 _lib = None
