@@ -357,6 +357,43 @@ int n2v_sgns_train_span(const int32_t* walks, const int32_t* lens, int64_t n_loc
 /* Workgroups of the default SGNS grid (max_blocks <= 0) for a vocabulary of n_words rows and a row mode. */
 int32_t n2v_sgns_default_blocks(int64_t n_words, int32_t update_mode);
 
+/* ---- song2vec (src/extract_playlist.py:31-34 -> gensim 3.2.0 Word2Vec(sentences, min_count), i.e. sg=0: CBOW with
+ * negative sampling) over a RAGGED corpus --------------------------------------------------------------------------
+ * gensim is a third-party dependency that is not part of the reference tree: the rule of csrc/n2v_cbow.hip
+ * restates `fast_sentence_cbow_neg` from memory and is the definition; parity with gensim is unpinned.
+ * Corpus in CSR: tokens int32[n_tokens], offsets int64[n_sentences + 1]; sentence s is tokens[offsets[s] .. offsets[s+1]),
+ * at most max_len <= n2v_cbow_max_sentence() (4096) tokens: max_len sizes the LDS slot a wavefront stages its sentence in.
+ * Tokens < 0 are dropped, so a -1-padded walk matrix int32[W][L] is a corpus with offsets = {0, L, 2L, ...}.
+ * Per centre i of the effective sentence (sub-sampling and window shrink as in n2v_sgns_train, same hashes and salts):
+ * no context trains nothing and draws nothing; neu1 = sum of the context rows of syn0 in ascending position, times
+ * 1 / count when cbow_mean; targets = the centre (label 1) + `negative` draws of the sentence's LCG (a draw equal to
+ * the centre is skipped), sequential per target — a row drawn twice sees the earlier update; work is scaled by 1 / count
+ * when not cbow_mean and added to EVERY context position's row (a word twice in the window: twice).
+ * Tables, sample_int, cum_table, lut, the learning-rate schedule (sentences_base / step / total, alpha_batch), seed,
+ * sentence_id_base (= walk_id_base: keys the per-sentence streams; epoch e of S sentences uses e * S + s), max_blocks
+ * and work_counter as for n2v_sgns_train.  pair_count (may be NULL) is incremented by the number of TRAINED CENTRES.
+ * update_mode must be N2V_SGNS_ATOMIC: the context rows are held for a centre's whole target pass, so rows are only
+ * ever changed by float atomic adds; the lossy SGNS modes were never scored for CBOW and are refused.
+ * n2v_cbow_corpus_check (integers only; reads offsets[0 .. n_sentences] and tokens[0 .. n_tokens) and nothing else)
+ * names what is wrong with a corpus by bits of *status (int32, device, cleared by the caller).  n2v_cbow_train is only
+ * defined on a corpus that passes it; it clamps every range and skips out-of-range tokens, so a malformed corpus is no
+ * out-of-bounds access, but callers check first and never launch one.                                              */
+#define N2V_CBOW_BAD_START 1    /* offsets[0] != 0 */
+#define N2V_CBOW_BAD_END 2      /* offsets[n_sentences] != n_tokens */
+#define N2V_CBOW_BAD_ORDER 4    /* offsets decrease somewhere */
+#define N2V_CBOW_BAD_LENGTH 8   /* a sentence longer than max_len */
+#define N2V_CBOW_BAD_TOKEN 16   /* a token >= n_words */
+int32_t n2v_cbow_max_sentence(void);
+int n2v_cbow_corpus_check(const int32_t* tokens, const int64_t* offsets, int64_t n_sentences, int64_t n_tokens,
+                          int64_t n_words, int32_t max_len, int32_t* status, void* stream);
+int n2v_cbow_train(const int32_t* tokens, const int64_t* offsets, int64_t n_sentences, int64_t n_tokens,
+                   int32_t max_len, float* syn0, float* syn1neg, int64_t n_words, int32_t dim, int32_t row_stride,
+                   int32_t window, int32_t negative, int32_t cbow_mean, const uint32_t* sample_int,
+                   const uint32_t* cum_table, const uint32_t* lut, int32_t lut_bits, float alpha, float min_alpha,
+                   int64_t sentences_base, int64_t sentences_step, int64_t sentences_total, int64_t alpha_batch,
+                   uint64_t seed, uint64_t sentence_id_base, unsigned long long* pair_count, int32_t update_mode,
+                   int32_t max_blocks, unsigned long long* work_counter, void* stream);
+
 /* ---- replica merges of the multi-GPU trainer (no counterpart in the reference, whose gensim
  * threads share one table: src/main.py:87 `workers=`) ------------------------------------------------------
  * One process per GPU trains a replica x of a table on its shard; `base` is the copy all ranks agree on.  At

@@ -50,6 +50,8 @@ def parse_args(argv=None):
                     help="popularity-biased walks (src/main_link_multi.py:87): pop = first step by weight / degree of the "
                          "neighbour; both = half the rounds plain, then half popularity-biased")
     ap.add_argument("--seed", type=int, default=1, help="seed of the philox walk RNG and of the SGNS trainer")
+    ap.add_argument("--sg", type=int, default=1, choices=[0, 1],
+                    help="1: skip-gram (the reference's call); 0: CBOW over the same walks (n2v_hip/cbow.py, one GPU)")
     ap.add_argument("--merge", default="tsum", choices=["tsum", "hot"],
                     help="more than one GPU: how the ranks' replicas are merged (n2v_hip/merge.py: tiered pure sums, or "
                          "weighted sums — faster, but 0.005-0.006 AUC below the sequential comparator at 131k nodes: refused "
@@ -82,6 +84,8 @@ def learn_embeddings(walks, **overrides):
     epochs = overrides.get("iter", getattr(a, "iter", 1))
     seed = overrides.get("seed", getattr(a, "seed", 1))
     corpus = node2vec.as_corpus(walks)
+    if overrides.get("sg", getattr(a, "sg", 1)) == 0:
+        return _learn_embeddings_cbow(corpus, dim, window, epochs, seed, overrides)
     model = _sgns.SgnsModel(len(corpus.labels), dim=dim, window=window, negative=overrides.get("negative", 5),
                             alpha=overrides.get("alpha", 0.025), min_alpha=overrides.get("min_alpha", 1e-4),
                             sample=overrides.get("sample", 1e-3), seed=seed, device=corpus.walks.device,
@@ -104,6 +108,24 @@ def learn_embeddings(walks, **overrides):
         b, _ = _sgns.shard_bounds(overrides["n_starts"], ctx.world, ctx.rank)
         _dist.train_sharded(model, corpus.walks, corpus.lens, ctx, n_walks_global=int(tot.item()),
                             shard_offset=b * overrides["num_walks"], epochs=epochs, merge=overrides.get("merge", "tsum"))
+    wv = _sgns.KeyedVectors(corpus.labels, model.counts, model.vectors().cpu().numpy())
+    return _sgns.Word2VecResult(wv, model, model.pairs_trained())
+
+
+def _learn_embeddings_cbow(corpus, dim, window, epochs, seed, overrides):
+    """sg=0: the walks as sentences of the CBOW trainer (gensim's Word2Vec(walks, sg=0, min_count=0)); one GPU."""
+    from n2v_hip import cbow as _cbow
+    from n2v_hip.corpus import SentenceCorpus
+    ctx = overrides.get("ctx")
+    if ctx is not None and ctx.world > 1:
+        raise NotImplementedError("sg=0 trains on one GPU: the replica merges are built for the skip-gram trainer only")
+    sentences = SentenceCorpus.from_walks(corpus)
+    model = _cbow.CbowModel(len(corpus.labels), dim=dim, window=window, negative=overrides.get("negative", 5),
+                            cbow_mean=overrides.get("cbow_mean", 1), alpha=overrides.get("alpha", 0.025),
+                            min_alpha=overrides.get("min_alpha", 1e-4), sample=overrides.get("sample", 1e-3), seed=seed,
+                            device=corpus.walks.device)
+    model.build_vocab(sentences.counts)
+    _cbow.train(model, sentences, epochs=epochs)
     wv = _sgns.KeyedVectors(corpus.labels, model.counts, model.vectors().cpu().numpy())
     return _sgns.Word2VecResult(wv, model, model.pairs_trained())
 

@@ -1,0 +1,47 @@
+"""``Word2Vec(sentences, ...)`` with gensim 3.2.0's argument names and defaults, trained on the GPU: what
+src/extract_playlist.py:31-34 calls as ``gensim.models.Word2Vec(sentences, min_count=min_ct)`` (CBOW: sg=0,
+cbow_mean=1, size 100, window 5, 5 negatives, iter 5).  Returns the ``Word2VecResult`` / ``KeyedVectors`` pair of
+n2v_hip/sgns.py, keyed by the sentences' own labels.  Skip-gram over ragged sentences (sg=1) is not built: the
+skip-gram kernel reads a fixed-stride walk matrix (``main.learn_embeddings``)."""
+import numpy as np
+
+from . import cbow as _cbow
+from . import sgns as _sgns
+from .corpus import SentenceCorpus
+
+
+class LabelKeyedVectors(_sgns.KeyedVectors):
+    """KeyedVectors over arbitrary hashable labels; `labels` / `counts` / `vectors` come sorted by descending count
+    (SentenceCorpus order)."""
+
+    def __init__(self, labels, counts, vectors):
+        self.index2word = [x.item() if hasattr(x, "item") else x for x in labels]
+        self.syn0 = np.ascontiguousarray(vectors, dtype=np.float32)
+        self.vectors = self.syn0
+        self.vocab = {w: _sgns._VocabEntry(i, int(counts[i])) for i, w in enumerate(self.index2word)}
+        self.vector_size = self.syn0.shape[1] if self.syn0.ndim == 2 else 0
+
+
+def Word2Vec(sentences, size=100, window=5, min_count=5, sg=0, negative=5, cbow_mean=1, alpha=0.025, min_alpha=1e-4,
+             sample=1e-3, iter=5, seed=1, device=None, sequential=False):
+    """sentences: an iterable of lists of labels, or a SentenceCorpus (then min_count has been applied already).
+    sequential=True: one sentence at a time on one wavefront, reproducible to the bit (n2v_hip/cbow.py:train)."""
+    if sg not in (0, 1):
+        raise ValueError("sg must be 0 (CBOW) or 1 (skip-gram)")
+    if sg == 1:
+        raise NotImplementedError("sg=1 over ragged sentences is not built; main.learn_embeddings trains skip-gram "
+                                  "on a walk matrix")
+    if int(size) < 1 or int(size) > 512:
+        raise ValueError("size must be in [1, 512]")
+    if int(iter) < 1:
+        raise ValueError("iter must be >= 1")
+    corpus = sentences if isinstance(sentences, SentenceCorpus) else SentenceCorpus.from_sentences(
+        sentences, min_count=min_count, device=device)
+    if len(corpus.labels) == 0:
+        raise ValueError("no word occurs min_count=%d times: the vocabulary is empty" % int(min_count))
+    model = _cbow.CbowModel(len(corpus.labels), dim=size, window=window, negative=negative, cbow_mean=cbow_mean,
+                            alpha=alpha, min_alpha=min_alpha, sample=sample, seed=seed, device=corpus.device)
+    model.build_vocab(corpus.counts)
+    _cbow.train(model, corpus, epochs=iter, sequential=sequential)
+    wv = LabelKeyedVectors(corpus.labels, corpus.counts, model.vectors().cpu().numpy())
+    return _sgns.Word2VecResult(wv, model, model.pairs_trained())

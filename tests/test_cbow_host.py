@@ -1,0 +1,330 @@
+"""Host tests of the CBOW trainer (n2v_hip/cbow.py, corpus.py, word2vec.py, playlist.py; csrc/n2v_cbow.hip): what can
+be checked without a GPU.
+
+(a) the restatement tests/cbow_reference.py equals a literal transcription of the rule's pseudo-code;
+(b) every deliberate error the restatement can plant moves the tables of the GPU case table (tests/cbow_cases.py) by
+    at least 10 x the GPU tolerance — on the case that shows it most (the GPU test fails when ANY case leaves the
+    tolerance) and also on EVERY case it moves at all (a case an error cannot touch, such as negative=0 for a stale
+    repeated draw, shows exactly 0).  With TOL = 8.7e-6: the weakest error, the stale repeated draw, moves its best
+    case by 7.4e-2 and its least sensitive one by 1.2e-4 = 14 x TOL.
+    Two of the seven errors are no errors of the result and are pinned as such instead:
+      * reversed_sum only re-orders a float sum (the issue excludes it from the condition);
+      * draw_without_context cannot be observed at all: hi - lo <= 1 needs n_eff == 1 (for n_eff >= 2 the shrunk window
+        still reaches a neighbour: rb <= window - 1 gives lo <= i - 1 or hi >= i + 2), and a one-word sentence has no
+        later centre that could see the LCG.  Its deviation is asserted to be exactly 0 on a table that does contain
+        one-word sentences; it takes no part in the 10 x condition, which nothing could make it meet.
+(c) no sigmoid evaluation of the case table sits near a bin edge (a condition of the data, not of the kernel);
+(d) SentenceCorpus against a dict-based restatement; (e) the vocabulary tables are fed retained counts;
+(f) the C-ABI; (g) argument errors.
+"""
+import os
+import re
+from collections import Counter
+
+import numpy as np
+import pytest
+
+import cbow_cases as K
+import cbow_reference as C
+import sgns_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- (a) the pseudo-code, literally ------------------------------------------------------------------------------------
+
+def _transcription(syn0, syn1neg, sent, sid, *, window, negative, cbow_mean, alpha, seed, cum):
+    lcg, st, n_eff = R.lcg_seed(seed, sid), R.Stats(), len(sent)
+    for i in range(n_eff):
+        rb = R.hash32(seed, sid, i, R.SALT_WINDOW) % window
+        lo, hi = max(0, i - window + rb), min(n_eff, i + window + 1 - rb)
+        if hi - lo <= 1:
+            continue
+        count = hi - lo - 1
+        inv = float(np.float32(1.0) / np.float32(count))
+        neu1 = np.zeros(syn0.shape[1])
+        for m in range(lo, hi):
+            if m != i:
+                neu1 = neu1 + syn0[sent[m]]
+        if cbow_mean:
+            neu1 = neu1 * inv
+        work = np.zeros_like(neu1)
+        for d in range(negative + 1):
+            if d == 0:
+                t, label = sent[i], 1.0
+            else:
+                t, label, lcg = R.draw(lcg, cum), 0.0, R.lcg_step(lcg)
+                if t == sent[i]:
+                    continue
+            f = float(np.dot(neu1, syn1neg[t]))
+            g = R._gradient(f, 0.0, label, alpha, st)          # |f| >= 6 -> 0.0
+            if g != 0.0:
+                work = work + g * syn1neg[t]
+                syn1neg[t] = syn1neg[t] + g * neu1
+        if not cbow_mean:
+            work = work * inv
+        for m in range(lo, hi):
+            if m != i:
+                syn0[sent[m]] = syn0[sent[m]] + work
+
+
+@pytest.mark.parametrize("cbow_mean", [0, 1])
+@pytest.mark.parametrize("negative,window", [(0, 1), (3, 2), (9, 4)])
+def test_restatement_equals_the_pseudo_code(cbow_mean, negative, window):
+    rs = np.random.RandomState(5 + negative)
+    n, dim, seed, sid = 12, 6, 2**40 + 3, 17
+    counts = rs.randint(1, 50, n)
+    _, cum = K.vocab(counts, 0)
+    sent = rs.randint(0, n, 15).astype(np.int32)           # 12 words in 15 places: repeats inside every window
+    s0, s1 = rs.random_sample((n, dim)) - 0.5, rs.random_sample((n, dim)) - 0.5
+    a0, a1, b0, b1 = s0.copy(), s1.copy(), s0.copy(), s1.copy()
+    alpha = R.walk_alpha(0.05, 1e-4, 3, 1, 10, 1, 0)
+    C.train(a0, a1, sent, [0, len(sent)], window=window, negative=negative, cbow_mean=cbow_mean, alpha=0.05, min_alpha=1e-4,
+            sample_int=None, cum_table=cum, seed=seed, sentence_id_base=sid, sentences_base=3, sentences_step=1,
+            sentences_total=10, alpha_batch=1)
+    _transcription(b0, b1, [int(x) for x in sent], sid, window=window, negative=negative, cbow_mean=cbow_mean, alpha=alpha,
+                   seed=seed, cum=[int(x) for x in cum])
+    assert (a0 != s0).any() and (a1 != s1).any()
+    assert np.array_equal(a0, b0) and np.array_equal(a1, b1)
+
+
+# ---- (b), (c) the GPU case table ---------------------------------------------------------------------------------------
+
+def test_case_table_has_no_evaluation_on_a_bin_edge_and_covers_its_edges():
+    seen = Counter()
+    for c in K.CASES:
+        _, _, st = K.reference(c)
+        assert st.near_edge == 0, (K.case_id(c), st.near_edge)
+        assert st.pairs > 0, K.case_id(c)
+        seen["repeat"] += st.repeat_groups
+        seen["centre_draws"] += getattr(st, "centre_draws", 0)
+        if c["kind"] == "repeat":
+            assert st.repeat_groups > 0.3 * st.groups, (st.repeat_groups, st.groups)
+        if c["kind"] == "centre_draw":
+            assert getattr(st, "centre_draws", 0) >= 10
+    assert seen["repeat"] and seen["centre_draws"]
+    assert len({K.case_id(c) for c in K.CASES}) == len(K.CASES)
+    # the shapes the issue asks for
+    for key, want in (("dim", {1, 50, 64, 100, 128, 200, 256, 512}), ("window", {1, 5, 10, 17}),
+                      ("negative", {0, 1, 5, 7, 8, 15, 64}), ("cbow_mean", {0, 1}), ("sample", {0, 1e-3, 1e-2})):
+        assert want <= {c[key] for c in K.CASES}, key
+    assert {0, 1, 2, 3, 63, 64, 65, 130, 4096} <= {n for c in K.CASES for n in c["lens"]}
+    assert any(c["seed"] >= 2**63 for c in K.CASES) and any(2**32 <= c["seed"] < 2**63 for c in K.CASES)
+    assert any(c["sid_base"] == 2**40 for c in K.CASES)
+
+
+def test_every_planted_error_is_far_outside_the_gpu_tolerance():
+    largest, smallest = {}, {}
+    for v in C.VARIANTS:
+        devs = []
+        for c in K.CASES:
+            r0, r1, _ = K.reference(c)
+            a0, a1, _ = K.run_reference(c, variant=v)
+            devs.append(max(K.relative_deviation(a0, a1, r0, r1)))
+        largest[v] = max(devs)
+        smallest[v] = min([d for d in devs if d > 0], default=0.0)
+        print("planted %-22s largest deviation of a case %.3g, smallest non-zero %.3g, cases moved %d of %d"
+              % (v, largest[v], smallest[v], sum(d > 0 for d in devs), len(devs)))
+    assert largest["draw_without_context"] == 0.0          # unobservable by construction, see the module docstring
+    assert any(1 in c["lens"] for c in K.CASES)
+    assert 0 < largest["reversed_sum"] < K.TOL             # a re-ordered float64 sum: rounding only
+    real = [v for v in C.VARIANTS if v not in ("reversed_sum", "draw_without_context")]
+    worst = min(largest[v] for v in real)
+    print("smallest planted deviation %.3g = %.0f x TOL (%.3g)" % (worst, worst / K.TOL, K.TOL))
+    assert worst >= 10 * K.TOL, (largest, K.TOL)
+    assert min(smallest[v] for v in real) >= 10 * K.TOL, (smallest, K.TOL)
+
+
+# ---- (d) SentenceCorpus ------------------------------------------------------------------------------------------------
+
+def _rows(corpus):
+    t, o = corpus.tokens.numpy(), corpus.offsets.numpy()
+    return [t[o[s]:o[s + 1]].tolist() for s in range(len(o) - 1)]
+
+
+def _check_against_dicts(sentences, min_count):
+    from n2v_hip.corpus import SentenceCorpus
+    corpus = SentenceCorpus.from_sentences(sentences, min_count=min_count, device="cpu")
+    kept, counts, rows = K.dict_corpus(sentences, min_count)
+    assert [x.item() if hasattr(x, "item") else x for x in corpus.labels] == kept
+    assert corpus.counts.tolist() == counts
+    assert _rows(corpus) == rows
+    assert corpus.max_len == max([len(r) for r in rows] + [1])
+    assert corpus.n_tokens == sum(counts)
+    return corpus
+
+
+def test_sentence_corpus_prunes_orders_and_keeps_empty_rows():
+    # counts: a 5, b 4, c 4, d 3, e 1, f 1 — min_count 4 keeps a, b, c (count == min_count stays, min_count - 1 goes)
+    sentences = [["a", "b", "c", "d"], ["e"], ["a", "b", "c", "d", "a"], ["d", "f"], ["a", "c", "b"], [], ["a", "b", "c"]]
+    corpus = _check_against_dicts(sentences, 4)
+    assert list(corpus.labels) == ["a", "b", "c"]           # tie b / c: ascending label
+    assert _rows(corpus)[1] == [] and _rows(corpus)[3] == [] and _rows(corpus)[5] == []   # emptied rows stay
+    assert len(corpus) == len(sentences)
+    _check_against_dicts(sentences, 3)
+    _check_against_dicts(sentences, 5)
+    _check_against_dicts(sentences, 0)
+    rs = np.random.RandomState(2)
+    rnd = [rs.randint(0, 40, rs.randint(0, 30)).tolist() for _ in range(200)]
+    for mc in (1, 2, 5, 9):
+        _check_against_dicts(rnd, mc)
+    empty = _check_against_dicts([["x"], ["y"]], 2)
+    assert len(empty.labels) == 0 and empty.n_tokens == 0 and len(empty) == 2
+
+
+def test_sentence_corpus_cuts_at_4096_kept_tokens():
+    rs = np.random.RandomState(3)
+    for n in (4096, 4097, 2 * 4096 + 1):
+        s = rs.randint(0, 50, n).tolist()
+        s[10:10] = [999] * 3                                 # pruned: the cut counts KEPT tokens
+        corpus = _check_against_dicts([[1, 2], s, [], [3, 1]], 4)
+        lens = [len(r) for r in _rows(corpus)]
+        want = [4096] * (n // 4096) + ([n % 4096] if n % 4096 else [])
+        assert lens[1:1 + len(want)] == want and corpus.max_len == 4096, lens
+
+
+def test_from_walks_is_a_view():
+    import torch
+
+    import node2vec
+    from n2v_hip.corpus import SentenceCorpus
+    w = torch.tensor([[0, 2, 1, -1], [2, 2, -1, -1], [1, 0, 2, 2]], dtype=torch.int32)
+    wc = node2vec.WalkCorpus(w, torch.tensor([3, 2, 4], dtype=torch.int32), np.array([10, 11, 12]))
+    c = SentenceCorpus.from_walks(wc)
+    assert c.tokens.data_ptr() == w.data_ptr() and c.offsets.tolist() == [0, 4, 8, 12] and c.max_len == 4
+    assert c.counts.tolist() == [2, 2, 5] and c.tolist() == [[10, 12, 11], [12, 12], [11, 10, 12, 12]]
+    with pytest.raises(ValueError):
+        SentenceCorpus.from_walks(node2vec.WalkCorpus(torch.zeros((1, 4097), dtype=torch.int32), None, np.arange(1)))
+
+
+# ---- (e) retained counts -----------------------------------------------------------------------------------------------
+
+def test_vocab_tables_are_fed_retained_counts(monkeypatch):
+    import torch
+
+    from n2v_hip import cbow, sgns
+    from n2v_hip.corpus import SentenceCorpus
+    sentences = [["a", "b", "c"]] * 6 + [["a", "rare%d" % i] for i in range(50)]
+    corpus = SentenceCorpus.from_sentences(sentences, min_count=5, device="cpu")
+    assert list(corpus.labels) == ["a", "b", "c"] and corpus.counts.tolist() == [56, 6, 6]
+    got = {}
+
+    class _Stop(Exception):
+        pass
+
+    def record(counts, sample):
+        got["counts"], got["sample"] = np.asarray(counts).tolist(), sample
+        raise _Stop
+
+    monkeypatch.setattr(sgns, "vocab_tables", record)
+    m = object.__new__(cbow.CbowModel)
+    m.n_words, m.sample, m.device = 3, 1e-3, torch.device("cpu")
+    with pytest.raises(_Stop):
+        m.build_vocab(corpus.counts)
+    assert got == {"counts": [56, 6, 6], "sample": 1e-3}
+    monkeypatch.undo()
+    # the threshold is sample * (retained total): with the 50 pruned words counted it would be another table
+    a, _ = sgns.vocab_tables(np.array([56, 6, 6]), 1e-1)
+    b, _ = sgns.vocab_tables(np.array([56, 6, 6] + [1] * 50), 1e-1)
+    assert a[0] != b[0]
+    with pytest.raises(ValueError):
+        m.build_vocab(np.array([1, 2]))
+
+
+def test_alpha_batch_follows_the_mean_sentence_length():
+    from n2v_hip import cbow
+
+    class _Corpus:
+        def __init__(self, s, t):
+            self.n_sentences, self.n_tokens = s, t
+
+    assert cbow.default_alpha_batch(_Corpus(1000, 8000)) == 1250
+    assert cbow.default_alpha_batch(_Corpus(3, 3 * 4096)) == 2
+    assert cbow.default_alpha_batch(_Corpus(2, 10**6)) == 1 and cbow.default_alpha_batch(_Corpus(0, 0)) == 1
+
+
+# ---- (f) the C-ABI -----------------------------------------------------------------------------------------------------
+
+def test_symbols_are_declared_and_bound():
+    from n2v_hip import _lib, corpus
+    hdr = open(os.path.join(ROOT, "include", "n2v_hip.h")).read()
+    for (bit, _), macro in zip(corpus.CORPUS_BAD, ("START", "END", "ORDER", "LENGTH", "TOKEN")):
+        assert re.search(r"#define N2V_CBOW_BAD_%s %d\b" % (macro, bit), hdr)
+    assert "unpinned" in hdr[hdr.index("song2vec"):hdr.index("int32_t n2v_cbow_max_sentence")]
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    new = {"n2v_cbow_max_sentence", "n2v_cbow_corpus_check", "n2v_cbow_train"}
+    assert new <= set(re.findall(r"\b(n2v_[a-z0-9_]+)\s*\(", hdr)) and new <= set(_lib.SIGNATURES)
+    for name in new:
+        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr).group(1).strip()
+        assert len(_lib.SIGNATURES[name][1]) == (0 if params == "void" else params.count(",") + 1), name
+    lib = _lib.load()
+    assert all(hasattr(lib, name) for name in new)
+    assert lib.n2v_cbow_max_sentence() == 4096 == corpus.MAX_SENTENCE
+    mk = open(os.path.join(ROOT, "node2vec-by-ecc_amd", "csrc", "Makefile")).read()
+    assert "n2v_cbow.hip" in mk and "n2v_w2v_device.h" in mk
+
+
+def test_c_abi_refuses_bad_arguments_before_any_launch():
+    """Every call below returns before the first HIP call: no GPU is needed (and none is touched)."""
+    from n2v_hip import _lib
+    lib = _lib.load()
+    one = 8     # a non-NULL "pointer" that is never dereferenced: each call fails its argument checks first
+
+    def train(max_len=64, dim=100, stride=128, window=5, negative=5, mean=1, mode=2, total=10, n_words=50):
+        return lib.n2v_cbow_train(one, one, 3, 30, max_len, one, one, n_words, dim, stride, window, negative, mean, None, one,
+                                  one, 20, 0.025, 1e-4, 0, 1, total, 1, 1, 0, None, mode, 1, None, None)
+
+    for kw, msg in ((dict(max_len=4097), "max_len"), (dict(max_len=0), "max_len"), (dict(negative=65), "bad size"),
+                    (dict(negative=-1), "bad size"), (dict(window=0), "bad size"), (dict(mean=2), "bad size"),
+                    (dict(stride=96), "row_stride"), (dict(stride=64), "row_stride"), (dict(dim=600, stride=640), "row_stride"),
+                    (dict(mode=0), "update_mode"), (dict(mode=1), "update_mode"), (dict(mode=6), "update_mode"),
+                    (dict(total=0), "schedule"), (dict(n_words=0), "bad size")):
+        assert train(**kw) == -1, kw
+        assert msg in lib.n2v_last_error().decode(), (kw, lib.n2v_last_error())
+    assert lib.n2v_cbow_train(None, None, 3, 30, 64, None, None, 50, 100, 128, 5, 5, 1, None, None, None, 20, 0.025, 1e-4, 0,
+                              1, 10, 1, 1, 0, None, 2, 1, None, None) == -1
+    assert "null pointer" in lib.n2v_last_error().decode()
+    assert lib.n2v_cbow_corpus_check(one, one, 3, 30, 50, 4097, one, None) == -1
+    assert lib.n2v_cbow_corpus_check(one, None, 3, 30, 50, 64, one, None) == -1
+
+
+# ---- (g) argument errors -----------------------------------------------------------------------------------------------
+
+def test_word2vec_argument_errors():
+    from n2v_hip.corpus import SentenceCorpus
+    from n2v_hip.word2vec import Word2Vec
+    with pytest.raises(NotImplementedError, match="main.learn_embeddings"):
+        Word2Vec([["a", "b"]], sg=1)
+    with pytest.raises(ValueError):
+        Word2Vec([["a", "b"]], sg=2)
+    with pytest.raises(ValueError):
+        Word2Vec([["a", "b"]], size=0)
+    with pytest.raises(ValueError):
+        Word2Vec([["a", "b"]], size=513)
+    with pytest.raises(ValueError):
+        Word2Vec([["a", "b"]], iter=0)
+    with pytest.raises(ValueError):
+        SentenceCorpus.from_sentences([["a", "b"]], min_count=-1, device="cpu")
+    with pytest.raises(ValueError, match="vocabulary is empty"):
+        Word2Vec(SentenceCorpus.from_sentences([["a", "b"]], min_count=2, device="cpu"))
+
+
+def test_main_has_the_sg_flag_and_defaults_to_skip_gram():
+    import main
+    assert main.parse_args([]).sg == 1 and main.parse_args(["--sg", "0"]).sg == 0
+    with pytest.raises(SystemExit):
+        main.parse_args(["--sg", "2"])
+
+
+def test_playlists_on_the_host_follow_the_loop():
+    """The torch ops of n2v_hip/playlist.py are device-agnostic: the rule itself is checked here, its GPU run in
+    tests/test_gpu_cbow.py."""
+    import playlist_reference as P
+    from n2v_hip.playlist import extract_playlists
+    uid = ["u1"] * 5 + ["u2"] * 3
+    ts = [0, 100, 700, 710, 1000, 2010, 2020, 2030]
+    pt = [100, 300, 9, 10, 5, 50, 50, 50]       # row 1 -> 2: 700 < 100 + 300 + 300 is false: a new session at row 2
+    tid = ["a", "b", "c", "d", "e", "f", "g", "h"]
+    got = extract_playlists(uid, ts, pt, tid, device="cpu")
+    assert got == P.extract_playlist(uid, ts, pt, tid) == [["a", "b"], ["d", "e"], ["f", "g", "h"]]
+    assert extract_playlists([], [], [], [], device="cpu") == []
