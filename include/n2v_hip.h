@@ -394,6 +394,35 @@ int n2v_cbow_train(const int32_t* tokens, const int64_t* offsets, int64_t n_sent
                    uint64_t seed, uint64_t sentence_id_base, unsigned long long* pair_count, int32_t update_mode,
                    int32_t max_blocks, unsigned long long* work_counter, void* stream);
 
+/* ---- skip-gram (sg=1) over the same RAGGED corpus (csrc/n2v_sgns_csr.hip) ------------------------------------------
+ * The update rule per (centre, context) pair is n2v_sgns_train's (csrc/n2v_sgns.hip is its definition: same hashes and
+ * salts, per-sentence LCG, draws, late-slot rule for a row drawn twice, centre row's change added once per centre,
+ * predraw under the same condition and N2V_SGNS_PREDRAW switch); gensim is not part of the reference tree and parity
+ * with gensim is unpinned.  Token position = offset inside the sentence, so a -1-padded walk matrix seen as CSR trains
+ * exactly the streams n2v_sgns_train sees.  Corpus, tables, schedule and the corpus contract as for n2v_cbow_train: only
+ * launched on a corpus n2v_cbow_corpus_check passed (the kernel clamps every range and skips out-of-range tokens all the
+ * same).  The learning rate of sentence s (index in `offsets`) steps with floor(s / alpha_batch); its id, which keys its
+ * random streams, is sentence_id_base + s.
+ * Work items: chunk == 0: item = sentence, one wavefront each, LDS slot max_len (the sequential algorithm per sentence);
+ * item_off is ignored.  chunk >= 1: sentence s of n_s raw tokens has S_s = ceil(n_s / chunk) items (none when empty);
+ * item sp trains the effective centres [sp * n_eff / S_s, (sp + 1) * n_eff / S_s) — at most `chunk` — with the
+ * sentence's LCG advanced to its first centre in closed form, and stages only those plus `window` tokens on each side:
+ * the slot is chunk + 2 * window rounded up to 64 and may not exceed 4096 tokens.  item_off: device int64[n_sentences + 1],
+ * item_off[s] = sum of S_t over t < s (exclusive prefix sum; the last entry is the item count).  The launch trains the
+ * items [first_item, first_item + n_items); the entry point can only bound that range by n_tokens (n_sentences when
+ * chunk == 0) — item_off is device memory — and the kernel skips any item item_off does not cover.
+ * pair_count (may be NULL) is incremented by the number of (centre, context) pairs trained.  update_mode must be
+ * N2V_SGNS_ATOMIC: nothing scores lossy rows on a ragged corpus.  Every argument error (sizes, null pointers, stride,
+ * mode, schedule, chunk < 0, slot too long, item range, item_off missing with chunk > 0) returns before the first HIP call. */
+int n2v_sgns_csr_train(const int32_t* tokens, const int64_t* offsets, int64_t n_sentences, int64_t n_tokens,
+                       int32_t max_len, const int64_t* item_off, int32_t chunk, int64_t first_item, int64_t n_items,
+                       float* syn0, float* syn1neg, int64_t n_words, int32_t dim, int32_t row_stride, int32_t window,
+                       int32_t negative, const uint32_t* sample_int, const uint32_t* cum_table, const uint32_t* lut,
+                       int32_t lut_bits, float alpha, float min_alpha, int64_t sentences_base, int64_t sentences_step,
+                       int64_t sentences_total, int64_t alpha_batch, uint64_t seed, uint64_t sentence_id_base,
+                       unsigned long long* pair_count, int32_t update_mode, int32_t max_blocks,
+                       unsigned long long* work_counter, void* stream);
+
 /* ---- replica merges of the multi-GPU trainer (no counterpart in the reference, whose gensim
  * threads share one table: src/main.py:87 `workers=`) ------------------------------------------------------
  * One process per GPU trains a replica x of a table on its shard; `base` is the copy all ranks agree on.  At

@@ -69,6 +69,9 @@ SIGNATURES = {
     "n2v_cbow_train": (C.c_int, [_ptr, _ptr, _i64, _i64, _i32, _ptr, _ptr, _i64, _i32, _i32, _i32, _i32, _i32, _ptr, _ptr,
                                  _ptr, _i32, C.c_float, C.c_float, _i64, _i64, _i64, _i64, _u64, _u64, _ptr, _i32, _i32,
                                  _ptr, _ptr]),
+    "n2v_sgns_csr_train": (C.c_int, [_ptr, _ptr, _i64, _i64, _i32, _ptr, _i32, _i64, _i64, _ptr, _ptr, _i64, _i32, _i32,
+                                     _i32, _i32, _ptr, _ptr, _ptr, _i32, C.c_float, C.c_float, _i64, _i64, _i64, _i64,
+                                     _u64, _u64, _ptr, _i32, _i32, _ptr, _ptr]),
     "n2v_merge_snapshot": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
     "n2v_merge_hot_apply": (C.c_int, [_ptr, _ptr, _ptr, _i32, _ptr, _ptr, _i64, _ptr, _i32, _ptr]),
     "n2v_merge_flush": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _i32, _ptr]),

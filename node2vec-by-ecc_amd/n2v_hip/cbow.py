@@ -19,27 +19,24 @@ from .corpus import SentenceCorpus
 UPDATE_MODE = _sgns.UPDATE_MODES["atomic"]   # the only mode n2v_cbow_train accepts
 
 
-class CbowModel:
-    """Embedding tables + vocabulary statistics of one CBOW training run, on one device."""
+class RaggedModel:
+    """Embedding tables + vocabulary statistics of one training run over a SentenceCorpus, on one device: what the CBOW
+    trainer and the skip-gram trainer (n2v_hip/skipgram.py) share."""
 
-    def __init__(self, n_words, dim=100, window=5, negative=5, cbow_mean=1, alpha=0.025, min_alpha=1e-4, sample=1e-3,
-                 seed=1, device=None):
-        if int(n_words) < 1:
-            raise ValueError("empty vocabulary")
-        if int(window) < 1 or not 0 <= int(negative) <= 64 or cbow_mean not in (0, 1, False, True):
-            raise ValueError("window must be >= 1, negative in [0, 64], cbow_mean 0 or 1")
+    def __init__(self, n_words, dim=100, window=5, negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3, seed=1,
+                 device=None, what="CBOW"):
         if not torch.cuda.is_available():
-            raise RuntimeError("n2v_hip: no GPU visible; the CBOW trainer has no CPU fallback")
+            raise RuntimeError("n2v_hip: no GPU visible; the %s trainer has no CPU fallback" % what)
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.n_words, self.dim = int(n_words), int(dim)
         self.stride = _sgns._row_stride(self.dim)
-        self.window, self.negative, self.cbow_mean = int(window), int(negative), int(bool(cbow_mean))
+        self.window, self.negative = int(window), int(negative)
         self.alpha, self.min_alpha, self.sample, self.seed = float(alpha), float(min_alpha), sample, int(seed)
         d = self.device
         self.syn0 = torch.empty((self.n_words, self.stride), dtype=torch.float32, device=d)
         self.syn1neg = torch.empty((self.n_words, self.stride), dtype=torch.float32, device=d)
-        self.pair_count = torch.zeros(1, dtype=torch.int64, device=d)     # trained centres
+        self.pair_count = torch.zeros(1, dtype=torch.int64, device=d)     # trained centres (CBOW) / pairs (skip-gram)
         self.work_counter = torch.zeros(1, dtype=torch.int64, device=d)   # in-order hand-out; None: static grid stride
         self.counts = None
         self.sample_int = self.cum_table = self.lut = None
@@ -68,10 +65,7 @@ class CbowModel:
             _lib.check(self.lib.n2v_build_neg_lut(_lib.ptr(self.cum_table), self.n_words, _sgns.LUT_BITS,
                                                   _lib.ptr(self.lut), self._stream()))
 
-    def train_pass(self, corpus, sentences_base, sentences_total, sentence_id_base, sentences_step=1, alpha_batch=None,
-                   max_blocks=0, first=0, count=None):
-        """One kernel launch over the corpus (or its sentences [first, first + count): the launch then numbers them
-        from 0); asynchronous.  The corpus is checked (once, as a whole) before anything is launched."""
+    def _check_corpus(self, corpus):
         if not isinstance(corpus, SentenceCorpus):
             raise TypeError("train_pass takes a SentenceCorpus")
         if self.cum_table is None:
@@ -79,6 +73,34 @@ class CbowModel:
         if corpus.device != self.device:
             raise ValueError("corpus on %s, model on %s" % (corpus.device, self.device))
         corpus.check(self.n_words)
+
+    def pairs_trained(self):
+        """Centres trained so far (a centre without context trains nothing and is not counted)."""
+        return int(self.pair_count.item())
+
+    def vectors(self):
+        """syn0 without the padding columns (device view)."""
+        return self.syn0[:, :self.dim]
+
+
+class CbowModel(RaggedModel):
+    """Embedding tables + vocabulary statistics of one CBOW training run, on one device."""
+
+    def __init__(self, n_words, dim=100, window=5, negative=5, cbow_mean=1, alpha=0.025, min_alpha=1e-4, sample=1e-3,
+                 seed=1, device=None):
+        if int(n_words) < 1:
+            raise ValueError("empty vocabulary")
+        if int(window) < 1 or not 0 <= int(negative) <= 64 or cbow_mean not in (0, 1, False, True):
+            raise ValueError("window must be >= 1, negative in [0, 64], cbow_mean 0 or 1")
+        self.cbow_mean = int(bool(cbow_mean))
+        RaggedModel.__init__(self, n_words, dim=dim, window=window, negative=negative, alpha=alpha, min_alpha=min_alpha,
+                             sample=sample, seed=seed, device=device, what="CBOW")
+
+    def train_pass(self, corpus, sentences_base, sentences_total, sentence_id_base, sentences_step=1, alpha_batch=None,
+                   max_blocks=0, first=0, count=None):
+        """One kernel launch over the corpus (or its sentences [first, first + count): the launch then numbers them
+        from 0); asynchronous.  The corpus is checked (once, as a whole) before anything is launched."""
+        self._check_corpus(corpus)
         first = int(first)
         count = corpus.n_sentences - first if count is None else int(count)
         if first < 0 or count < 0 or first + count > corpus.n_sentences:
@@ -95,14 +117,6 @@ class CbowModel:
                 _sgns.LUT_BITS, self.alpha, self.min_alpha, int(sentences_base), int(sentences_step),
                 int(sentences_total), int(alpha_batch), self.seed & (2**64 - 1), int(sentence_id_base) & (2**64 - 1),
                 _lib.ptr(self.pair_count), UPDATE_MODE, int(max_blocks), _lib.ptr(self.work_counter), self._stream()))
-
-    def pairs_trained(self):
-        """Centres trained so far (a centre without context trains nothing and is not counted)."""
-        return int(self.pair_count.item())
-
-    def vectors(self):
-        """syn0 without the padding columns (device view)."""
-        return self.syn0[:, :self.dim]
 
 
 def default_alpha_batch(corpus):

@@ -1,12 +1,14 @@
 """``Word2Vec(sentences, ...)`` with gensim 3.2.0's argument names and defaults, trained on the GPU: what
 src/extract_playlist.py:31-34 calls as ``gensim.models.Word2Vec(sentences, min_count=min_ct)`` (CBOW: sg=0,
 cbow_mean=1, size 100, window 5, 5 negatives, iter 5).  Returns the ``Word2VecResult`` / ``KeyedVectors`` pair of
-n2v_hip/sgns.py, keyed by the sentences' own labels.  Skip-gram over ragged sentences (sg=1) is not built: the
-skip-gram kernel reads a fixed-stride walk matrix (``main.learn_embeddings``)."""
+n2v_hip/sgns.py, keyed by the sentences' own labels.  ``Word2Vec(..., sg=1)`` still refuses (its callers rely on the
+refusal); skip-gram over ragged sentences is ``SkipGram(sentences, ...)`` below (n2v_hip/skipgram.py,
+csrc/n2v_sgns_csr.hip)."""
 import numpy as np
 
 from . import cbow as _cbow
 from . import sgns as _sgns
+from . import skipgram as _skipgram
 from .corpus import SentenceCorpus
 
 
@@ -25,7 +27,8 @@ class LabelKeyedVectors(_sgns.KeyedVectors):
 def Word2Vec(sentences, size=100, window=5, min_count=5, sg=0, negative=5, cbow_mean=1, alpha=0.025, min_alpha=1e-4,
              sample=1e-3, iter=5, seed=1, device=None, sequential=False):
     """sentences: an iterable of lists of labels, or a SentenceCorpus (then min_count has been applied already).
-    sequential=True: one sentence at a time on one wavefront, reproducible to the bit (n2v_hip/cbow.py:train)."""
+    sequential=True: one sentence at a time on one wavefront, reproducible to the bit (n2v_hip/cbow.py:train).
+    sg=1 is refused here: skip-gram over ragged sentences is SkipGram(sentences, ...)."""
     if sg not in (0, 1):
         raise ValueError("sg must be 0 (CBOW) or 1 (skip-gram)")
     if sg == 1:
@@ -43,5 +46,32 @@ def Word2Vec(sentences, size=100, window=5, min_count=5, sg=0, negative=5, cbow_
                             alpha=alpha, min_alpha=min_alpha, sample=sample, seed=seed, device=corpus.device)
     model.build_vocab(corpus.counts)
     _cbow.train(model, corpus, epochs=iter, sequential=sequential)
+    wv = LabelKeyedVectors(corpus.labels, corpus.counts, model.vectors().cpu().numpy())
+    return _sgns.Word2VecResult(wv, model, model.pairs_trained())
+
+
+def SkipGram(sentences, size=100, window=5, min_count=5, negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3, iter=5,
+             seed=1, device=None, sequential=False, chunk="auto"):
+    """gensim's Word2Vec(sentences, sg=1, ...) over ragged sentences: same arguments, corpus and result as Word2Vec
+    above.  chunk: centres per work item ("auto": whole sentences up to 256 tokens, else 256; 0: whole sentences);
+    sequential=True: one item at a time on one wavefront, reproducible to the bit (n2v_hip/skipgram.py:train)."""
+    if int(size) < 1 or int(size) > 512:
+        raise ValueError("size must be in [1, 512]")
+    if int(iter) < 1:
+        raise ValueError("iter must be >= 1")
+    if int(window) < 1 or not 0 <= int(negative) <= 64:
+        raise ValueError("window must be >= 1, negative in [0, 64]")
+    if not (chunk == "auto" or (isinstance(chunk, (int, np.integer)) and not isinstance(chunk, bool) and chunk >= 0)):
+        raise ValueError("chunk must be 'auto' or an int >= 0")
+    if chunk != "auto" and ((int(chunk) + 2 * int(window) + 63) // 64) * 64 > _skipgram.MAX_SLOT:
+        raise ValueError("chunk %d + 2 x window %d exceeds the %d tokens a wavefront stages" % (chunk, window, _skipgram.MAX_SLOT))
+    corpus = sentences if isinstance(sentences, SentenceCorpus) else SentenceCorpus.from_sentences(
+        sentences, min_count=min_count, device=device)
+    if len(corpus.labels) == 0:
+        raise ValueError("no word occurs min_count=%d times: the vocabulary is empty" % int(min_count))
+    model = _skipgram.SkipGramModel(len(corpus.labels), dim=size, window=window, negative=negative, alpha=alpha,
+                                    min_alpha=min_alpha, sample=sample, seed=seed, device=corpus.device)
+    model.build_vocab(corpus.counts)
+    _skipgram.train(model, corpus, epochs=iter, chunk=chunk, sequential=sequential)
     wv = LabelKeyedVectors(corpus.labels, corpus.counts, model.vectors().cpu().numpy())
     return _sgns.Word2VecResult(wv, model, model.pairs_trained())
