@@ -77,7 +77,8 @@ int n2v_bine_walk(const int64_t* row_ptr, const int32_t* col, const int64_t* cum
  * [side_lo, side_hi), drawn uniformly, redrawn (up to 16 times) while it is v itself or its
  * Jaccard similarity with v (over their rows) exceeds max_jaccard — the stand-in for "not
  * returned by the LSH forest query" (DESIGN.md 4.7).  Rows v in [v_begin, v_end) are filled;
- * pool is int32[(v_end-v_begin)][pool_size] (row 0 = v_begin).                              */
+ * pool is int32[(v_end-v_begin)][pool_size] (row 0 = v_begin).  A side of one vertex has no
+ * other vertex to offer: its row is -1, the "no negative" value training skips.            */
 int n2v_bine_neg_pools(const int64_t* row_ptr, const int32_t* col, int64_t side_lo, int64_t side_hi,
                        int64_t v_begin, int64_t v_end, int32_t pool_size, double max_jaccard,
                        uint64_t seed, int32_t* pool, void* stream);

@@ -296,7 +296,10 @@ __global__ void __launch_bounds__(256) neg_pool_kernel(const int64_t* __restrict
             const int mult = lane_intersect(col, vb, vn, cb, cn);
             if (!((double)mult > max_jaccard * (double)(vn + cn - mult))) break;
         }
-        if (c == v) c = (v + 1 < side_hi) ? v + 1 : side_lo;  // all draws hit v itself: next vertex of the side
+        if (c == v) {
+            c = (v + 1 < side_hi) ? v + 1 : side_lo;  // all draws hit v itself: next vertex of the side
+            if (c == v) c = -1;  // a side of one vertex: no negative, the value the LSH pools use and training skips
+        }
         pool[(v - v_begin) * pool_size + s] = (int32_t)c;
     }
 }

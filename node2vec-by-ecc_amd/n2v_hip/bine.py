@@ -122,6 +122,27 @@ class BipartiteGraph:
         return self.user_labels[v] if v < self.n_u else self.item_labels[v - self.n_u]
 
 
+def user_edges_csr(g, src_user, dst_user, weight):
+    """The CSR (row_ptr int64, col int32, w fp64) of graph g with weighted user-user edges added, and the number of
+    distinct unordered pairs: the host half of BineEngine.add_user_edges."""
+    a = np.asarray(src_user, dtype=np.int64)
+    b = np.asarray(dst_user, dtype=np.int64)
+    w = np.asarray(weight, dtype=np.float64)
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    key = lo * g.n + hi
+    _, last_rev = np.unique(key[::-1], return_index=True)
+    win = len(key) - 1 - last_rev
+    lo, hi, w = lo[win], hi[win], w[win]
+    loop = lo == hi
+    src = np.concatenate([np.repeat(np.arange(g.n), np.diff(g.row_ptr)), lo, hi[~loop]])
+    dst = np.concatenate([g.col.astype(np.int64), hi, lo[~loop]])
+    ww = np.concatenate([g.w, w, w[~loop]])
+    o = np.lexsort((dst, src))
+    rp = np.zeros(g.n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=g.n), out=rp[1:])
+    return rp, dst[o].astype(np.int32), ww[o], int(len(lo))
+
+
 def _require_gpu(device):
     if not torch.cuda.is_available():
         raise RuntimeError("n2v_hip.bine: no GPU visible (torch.cuda.is_available() is False); "
@@ -171,27 +192,11 @@ class BineEngine:
         (the projections come from the biadjacency of node_u x node_v, :114; edge_list / edge_dict_u are not
         rebuilt), so only the HITS matrix changes.  Edges are applied in order; a repeated unordered pair keeps
         its last weight (networkx semantics).  src_user / dst_user: user indices (0..n_u-1)."""
-        g = self.g
-        a = np.asarray(src_user, dtype=np.int64)
-        b = np.asarray(dst_user, dtype=np.int64)
-        w = np.asarray(weight, dtype=np.float64)
-        lo, hi = np.minimum(a, b), np.maximum(a, b)
-        key = lo * g.n + hi
-        _, last_rev = np.unique(key[::-1], return_index=True)
-        win = len(key) - 1 - last_rev
-        lo, hi, w = lo[win], hi[win], w[win]
-        loop = lo == hi
-        src = np.concatenate([np.repeat(np.arange(g.n), np.diff(g.row_ptr)), lo, hi[~loop]])
-        dst = np.concatenate([g.col.astype(np.int64), hi, lo[~loop]])
-        ww = np.concatenate([g.w, w, w[~loop]])
-        o = np.lexsort((dst, src))
-        rp = np.zeros(g.n + 1, dtype=np.int64)
-        np.cumsum(np.bincount(src, minlength=g.n), out=rp[1:])
+        rp, col, ww, n_pairs = user_edges_csr(self.g, src_user, dst_user, weight)
         d = self.device
-        self.hits_csr = (torch.from_numpy(rp).to(d), torch.from_numpy(dst[o].astype(np.int32)).to(d),
-                         torch.from_numpy(ww[o]).to(d))
+        self.hits_csr = (torch.from_numpy(rp).to(d), torch.from_numpy(col).to(d), torch.from_numpy(ww).to(d))
         self.authority = None
-        return int(len(lo))
+        return n_pairs
 
     hits_csr = None  # (row_ptr, col, w) of the graph handed to hits() when user-user edges were added
 
@@ -199,6 +204,8 @@ class BineEngine:
     def calculate_centrality(self, max_iter=100, tol=1.0e-8):
         """nx.hits(G) of networkx 1.11 (src/bine_graph_utils.py:61): authority scores by power iteration from
         h = 1/n, max-normalised every iteration, stop at sum|h - h_last| < tol, error after max_iter."""
+        if self.g.n == 0:
+            raise ValueError("calculate_centrality: the graph has no ratings, so no vertex to score")
         n, d, lib = self.g.n, self.device, self.lib
         with torch.cuda.device(d):
             h = torch.full((n,), 1.0 / n, dtype=torch.float64, device=d)

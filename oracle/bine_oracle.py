@@ -138,7 +138,35 @@ def _intersect(col, a_lo, a_n, b_lo, b_n):
     return len(set(col[a_lo:a_lo + a_n].tolist()) & set(col[b_lo:b_lo + b_n].tolist()))
 
 
-def device_walk(row_ptr, col, cum2, node, gw, length, seed, stats=None):
+def _count(stats, key, n=1):
+    if stats is not None:
+        stats[key] = stats.get(key, 0) + n
+
+
+def _common_search_stats(col, a_lo, a_n, b_lo, b_n, stats):
+    """The branches wave_any_common takes for these two sorted ranges (swap to the shorter range, 64 of its
+    elements per round, exit at the first round with a hit)."""
+    if a_n > b_n:
+        a_lo, a_n, b_lo, b_n = b_lo, b_n, a_lo, a_n
+        _count(stats, "swap")
+    else:
+        _count(stats, "no_swap")
+    longer = set(col[b_lo:b_lo + b_n].tolist())
+    for i0 in range(0, a_n, 64):
+        if i0 == 64:
+            _count(stats, "second_round")
+        if longer & set(col[a_lo + i0:a_lo + min(i0 + 64, a_n)].tolist()):
+            if i0 + 64 < a_n:
+                _count(stats, "early_exit")
+            return
+
+
+def device_walk(row_ptr, col, cum2, node, gw, length, seed, stats=None, variant=None):
+    """`stats` (optional dict) counts the branches taken: "trials", "retry_self" (the proposal is the current
+    vertex), "rejected" (its middle vertex is not the first common neighbour), "steps", "clamp", and the branches of
+    the wave-wide search ("swap", "no_swap", "second_round", "early_exit").  `variant` plants an error for
+    tests/test_bine_prep_host.py: "keep_all" drops the first-common-neighbour test, "entry_left" searches the CSR
+    entry with side="left"."""
     cur = int(node)
     out = [cur]
     for t in range(length - 1):
@@ -146,29 +174,49 @@ def device_walk(row_ptr, col, cum2, node, gw, length, seed, stats=None):
         base = int(cum2[rb])
         paths = int(cum2[re]) - base
         nxt = cur
+        _count(stats, "steps")
         for trial in range(MAX_TRIALS):
             r = _philox(seed, gw, gw >> 32, t, 1 + trial)
-            pick = min(int(math.floor(_u53(r[0], r[1]) * float(paths))), paths - 1)
-            e = rb + int(np.searchsorted(cum2[rb + 1:re + 1] - base, pick, side="right"))
+            pick = int(math.floor(_u53(r[0], r[1]) * float(paths)))
+            if pick >= paths:
+                pick = paths - 1
+                _count(stats, "clamp")
+            e = rb + int(np.searchsorted(cum2[rb + 1:re + 1] - base, pick,
+                                         side="left" if variant == "entry_left" else "right"))
             mid = int(col[e])
-            w = int(col[int(row_ptr[mid]) + pick - (int(cum2[e]) - base)])
-            if stats is not None:
-                stats["trials"] = stats.get("trials", 0) + 1
+            k = pick - (int(cum2[e]) - base)
+            if variant == "entry_left":                   # the planted search can point one past mid's row
+                k = min(k, int(row_ptr[mid + 1] - row_ptr[mid]) - 1)
+            w = int(col[int(row_ptr[mid]) + k])
+            _count(stats, "trials")
             if w == cur:
+                _count(stats, "retry_self")
                 continue
             nxt = w
             wb = int(row_ptr[w])
+            if variant == "keep_all":
+                break
+            if stats is not None:
+                below = int(np.searchsorted(col[wb:int(row_ptr[w + 1])], mid, side="left"))
+                _common_search_stats(col, rb, e - rb, wb, below, stats)
             before = set(col[rb:e].tolist())              # cur's neighbours below mid
             if not (before & set(col[wb:int(row_ptr[w + 1])].tolist())):
                 break                                     # mid is the first common neighbour: keep the path
+            _count(stats, "rejected")
         cur = nxt
         out.append(cur)
     return out
 
 
-def neg_pool(row_ptr, col, side_lo, side_hi, v, pool_size, max_jaccard, seed):
+def neg_pool(row_ptr, col, side_lo, side_hi, v, pool_size, max_jaccard, seed, stats=None, variant=None):
+    """One vertex's pool row.  A side of one vertex has nobody to offer: its row is -1, the "no negative" value
+    (pool_valid).  `stats` (optional dict) counts "self_draw", "give_up" (the 17th draw kept without the similarity
+    test), "fallback" (every draw was v itself), "fallback_wrap", "no_negative", "swap" (v's row longer than the
+    candidate's) and "thinned".  `variant`: "no_wrap" takes v + 1 without wrapping to the side's start, "early_give_up"
+    gives up one trial early."""
     vb, vn = int(row_ptr[v]), int(row_ptr[v + 1] - row_ptr[v])
     side_n = side_hi - side_lo
+    last = POOL_TRIALS - 1 if variant == "early_give_up" else POOL_TRIALS
     out = []
     for s in range(pool_size):
         c = v
@@ -177,15 +225,28 @@ def neg_pool(row_ptr, col, side_lo, side_hi, v, pool_size, max_jaccard, seed):
             k = min(int(math.floor(_u53(r[0], r[1]) * float(side_n))), side_n - 1)
             c = side_lo + k
             if c == v:
+                _count(stats, "self_draw")
                 continue
-            if trial == POOL_TRIALS:
+            if trial >= last:
+                _count(stats, "give_up")
                 break
             cb, cn = int(row_ptr[c]), int(row_ptr[c + 1] - row_ptr[c])
+            _count(stats, "swap" if vn > cn else "no_swap")
             mult = _intersect(col, vb, vn, cb, cn)
             if not (float(mult) > max_jaccard * float(vn + cn - mult)):
                 break
+            _count(stats, "thinned")
         if c == v:
-            c = v + 1 if v + 1 < side_hi else side_lo
+            _count(stats, "fallback")
+            if variant == "no_wrap":
+                c = v + 1
+            else:
+                if not v + 1 < side_hi:
+                    _count(stats, "fallback_wrap")
+                c = v + 1 if v + 1 < side_hi else side_lo
+                if c == v:
+                    _count(stats, "no_negative")
+                    c = -1
         out.append(c)
     return out
 
