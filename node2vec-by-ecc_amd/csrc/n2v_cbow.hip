@@ -19,6 +19,7 @@
 // with memory-side float atomics only: the context rows are held (as neu1) for the whole target pass, so a whole-row
 // store would erase what other wavefronts added meanwhile.  No lossy mode is offered.
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <mutex>
 
@@ -30,26 +31,12 @@
 
 namespace {
 
-constexpr int kMaxSentence = 4096;  // tokens of one sentence: 4 waves x 4096 x 4 B = the 64 KB of LDS a workgroup may ask for
-
 struct CbowArgs {
+    W2vArgs w;                   // count: centres trained; lpad >= max_len
     const int32_t* tokens;
     const int64_t* offsets;
-    int64_t n_sent, n_tokens, n_words;
-    float* syn0;
-    float* syn1neg;
-    int32_t row_stride;
-    int32_t window, negative, cbow_mean;
-    const uint32_t* sample_int;
-    const uint32_t* cum_table;
-    const uint32_t* lut;
-    int32_t lut_shift;  // 31 - lut_bits
-    float alpha0, min_alpha;
-    int64_t sent_base, sent_step, sent_total, alpha_batch;
-    uint64_t seed, sent_id_base;
-    unsigned long long* centre_count;
-    unsigned long long* work;    // NULL: static grid stride; else the in-order item counter (reset by the launch)
-    int32_t lpad;                // LDS slot of a wave, >= max_len
+    int64_t n_sent, n_tokens;
+    int32_t cbow_mean;
 };
 
 // G = target slots in use per group of 8 (6 when negative <= 5: the centre + 5 draws)
@@ -58,49 +45,28 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
     extern __shared__ int32_t smem[];
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int32_t* sent = smem + wv * a.lpad;
+    int32_t* sent = smem + wv * a.w.lpad;
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     const int my_k = bitrev3(lane & 7);  // which of the 8 reduced values this lane ends up holding
     unsigned long long centres_done = 0;
 
-    for (int64_t si = a.work ? next_item(a.work, lane) : (int64_t)blockIdx.x * 4 + wv; si < a.n_sent;
-         si = a.work ? next_item(a.work, lane) : si + n_waves) {
+    for (int64_t si = a.w.work ? next_item(a.w.work, lane) : (int64_t)blockIdx.x * 4 + wv; si < a.n_sent;
+         si = a.w.work ? next_item(a.w.work, lane) : si + n_waves) {
         // a corpus that passed n2v_cbow_corpus_check needs none of these clamps; they keep a malformed one inside
         // tokens[0, T), the LDS slot and the tables
         int64_t tb = n2v::uni64(a.offsets[si]), te = n2v::uni64(a.offsets[si + 1]);
         tb = tb < 0 ? 0 : (tb > a.n_tokens ? a.n_tokens : tb);
         te = te < tb ? tb : (te > a.n_tokens ? a.n_tokens : te);
-        const int len = (int)(te - tb > (int64_t)a.lpad ? (int64_t)a.lpad : te - tb);
-        const uint64_t sid = a.sent_id_base + (uint64_t)si;
-        // ---- effective sentence: drop tokens < 0 and sub-sampled words, keep order
-        int n_eff = 0;
-        for (int base = 0; base < len; base += 64) {
-            const int pos = base + lane;
-            bool keep = false;
-            int32_t tok = -1;
-            if (pos < len) {
-                tok = a.tokens[tb + pos];
-                keep = tok >= 0 && (int64_t)tok < a.n_words;
-                if (keep && a.sample_int) keep = !(a.sample_int[tok] < hash32(a.seed, sid, (uint32_t)pos, 0x5AB));
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) sent[n_eff + __popcll(m & ((1ULL << lane) - 1ULL))] = tok;
-            n_eff += __popcll(m);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        // ---- learning rate of this sentence (gensim: linear decay, stepped per job)
-        const int64_t pushed = a.sent_base + (si / a.alpha_batch) * a.alpha_batch * a.sent_step;
-        float alpha = a.alpha0 - (a.alpha0 - a.min_alpha) * (float)((double)pushed / (double)a.sent_total);
-        alpha = fmaxf(alpha, a.min_alpha);
-
-        uint64_t lcg = mix64(a.seed ^ mix64(sid + 0x632BE59BD9B4E019ULL)) & kLcgMask;
+        const int len = (int)(te - tb > (int64_t)a.w.lpad ? (int64_t)a.w.lpad : te - tb);
+        const uint64_t sid = a.w.id_base + (uint64_t)si;
+        const int n_eff = stage_sentence<true>(a.w, a.tokens + tb, len, sid, lane, sent, 0, a.w.lpad, false);
+        slot_staged();
+        const float alpha = sentence_alpha(a.w, si);
+        uint64_t lcg = sentence_lcg(a.w.seed, sid);
 
         for (int i = 0; i < n_eff; ++i) {
-            const int rb = (int)(hash32(a.seed, sid, (uint32_t)i, 0xB17) % (uint32_t)a.window);
-            const int lo = max(0, i - a.window + rb), hi = min(n_eff, i + a.window + 1 - rb);
+            const Window w = shrunk_window(a.w, sid, i, n_eff);
+            const int lo = w.lo, hi = w.hi;
             if (hi - lo <= 1) continue;
             const int32_t ci = __builtin_amdgcn_readfirstlane(sent[i]);
             const float inv = 1.0f / (float)(hi - lo - 1);
@@ -111,7 +77,7 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
             for (int m = lo; m < hi; ++m) {
                 if (m == i) continue;
                 const int32_t xm = __builtin_amdgcn_readfirstlane(sent[m]);
-                const Row<VPL> r = load_row<VPL, kAtomic>(a.syn0, xm, a.row_stride, lane);
+                const Row<VPL> r = load_row<VPL, kAtomic>(a.w.syn0, xm, a.w.row_stride, lane);
 #pragma unroll
                 for (int v = 0; v < VPL; ++v) neu1.v[v] += r.v[v];
             }
@@ -120,16 +86,8 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
                 for (int v = 0; v < VPL; ++v) neu1.v[v] *= inv;
             }
             // ---- targets, 8 at a time: slot 0 of the first group is the centre word
-            for (int t0 = 0; t0 < a.negative + 1; t0 += 8) {
-                // lane k (k < 8) draws the target of slot k of this group
-                int32_t my_t = -1;
-                const int tk = t0 + lane;  // target number: 0 = positive, d >= 1 = d-th negative
-                if (lane < 8 && tk >= 1 && tk <= a.negative) {
-                    uint64_t s = lcg;  // state of the first draw of this group
-                    for (int d = max(t0, 1); d < tk; ++d) s = (s * kLcgA + kLcgC) & kLcgMask;
-                    my_t = draw_target(a.cum_table, a.lut, a.lut_shift, (uint32_t)((s >> 16) % 2147483647ULL));
-                    if (my_t == ci) my_t = -1;  // `if target_index == word_index: continue`
-                }
+            for (int t0 = 0; t0 < a.w.negative + 1; t0 += 8) {
+                const int32_t my_t = draw_group_target(a.w, lcg, t0, ci, lane);
                 int32_t tgt[G];
                 Row<VPL> n[G];
                 float p[8];
@@ -138,17 +96,11 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
                     tgt[k] = __builtin_amdgcn_readlane(my_t, k);
                     if (k == 0 && t0 == 0) tgt[k] = ci;
                 }
-                // a row drawn by two slots of the group: the later slot sits out the parallel pass (see sgns_kernel)
-                uint32_t late = 0;
-#pragma unroll
-                for (int k = 1; k < G; ++k)
-#pragma unroll
-                    for (int k1 = 0; k1 < k; ++k1)
-                        if (tgt[k] >= 0 && tgt[k] == tgt[k1]) late |= 1u << k;
+                const uint32_t late = late_slots<G>(tgt);
 #pragma unroll
                 for (int k = 0; k < G; ++k) {
                     if (tgt[k] >= 0 && !(late >> k & 1)) {
-                        n[k] = load_row<VPL, kAtomic>(a.syn1neg, tgt[k], a.row_stride, lane);
+                        n[k] = load_row<VPL, kAtomic>(a.w.syn1neg, tgt[k], a.w.row_stride, lane);
                     } else {
 #pragma unroll
                         for (int v = 0; v < VPL; ++v) n[k].v[v] = 0.f;
@@ -165,12 +117,7 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
                 }
                 const float f = reduce8(p, lane);
                 // this lane's own target: sigmoid table, gradient
-                float g = 0.f;
-                if (f > -kMaxExp && f < kMaxExp) {
-                    const float sig = c_exp_table[(int)((f + kMaxExp) * (float)(kExpTableSize / (int)kMaxExp / 2))];
-                    const float label = (my_k == 0 && t0 == 0) ? 1.f : 0.f;
-                    g = (label - sig) * alpha;
-                }
+                const float g = target_gradient(f, (my_k == 0 && t0 == 0) ? 1.f : 0.f, alpha);
 #pragma unroll
                 for (int k = 0; k < G; ++k) {
                     if (tgt[k] < 0 || (late >> k & 1)) continue;
@@ -183,14 +130,14 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
                         work.v[v] = fmaf(gk, n[k].v[v], work.v[v]);
                         dn.v[v] = gk * neu1.v[v];
                     }
-                    add_row<VPL>(a.syn1neg, tgt[k], a.row_stride, lane, dn);
+                    add_row<VPL>(a.w.syn1neg, tgt[k], a.w.row_stride, lane, dn);
                 }
                 if (late) {
                     // the repeated slots, in slot order: a negative each, from the row as memory holds it by now
 #pragma unroll
                     for (int k = 1; k < G; ++k) {
                         if (!(late >> k & 1)) continue;
-                        const Row<VPL> r = load_row<VPL, kAtomic>(a.syn1neg, tgt[k], a.row_stride, lane);
+                        const Row<VPL> r = load_row<VPL, kAtomic>(a.w.syn1neg, tgt[k], a.w.row_stride, lane);
                         const float gk = negative_gradient<VPL>(neu1, r, alpha);
                         if (gk == 0.f) continue;
                         Row<VPL> dn;
@@ -199,12 +146,10 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
                             work.v[v] = fmaf(gk, r.v[v], work.v[v]);
                             dn.v[v] = gk * neu1.v[v];
                         }
-                        add_row<VPL>(a.syn1neg, tgt[k], a.row_stride, lane, dn);
+                        add_row<VPL>(a.w.syn1neg, tgt[k], a.w.row_stride, lane, dn);
                     }
                 }
-                // advance the sentence's LCG past this group's negatives
-                const int used = min(a.negative, t0 + 7) - max(t0, 1) + 1;
-                for (int d = 0; d < used; ++d) lcg = (lcg * kLcgA + kLcgC) & kLcgMask;
+                lcg = lcg_past_group(lcg, a.w.negative, t0);
             }
             if (!a.cbow_mean) {
 #pragma unroll
@@ -214,13 +159,13 @@ __global__ void __launch_bounds__(256) cbow_kernel(CbowArgs a) {
             for (int m = lo; m < hi; ++m) {
                 if (m == i) continue;
                 const int32_t xm = __builtin_amdgcn_readfirstlane(sent[m]);
-                add_row<VPL>(a.syn0, xm, a.row_stride, lane, work);
+                add_row<VPL>(a.w.syn0, xm, a.w.row_stride, lane, work);
             }
             ++centres_done;
         }
         __builtin_amdgcn_wave_barrier();  // LDS sentence is reused by the next one
     }
-    if (a.centre_count && lane == 0 && centres_done) atomicAdd(a.centre_count, centres_done);
+    if (a.w.count && lane == 0 && centres_done) atomicAdd(a.w.count, centres_done);
 }
 
 // integers only: one lane per sentence and per token; reads offsets[0 .. S] and tokens[0 .. T) of the CLAIMED sizes
@@ -244,11 +189,11 @@ cbow_corpus_check_kernel(const int32_t* __restrict__ tokens, const int64_t* __re
 
 }  // namespace
 
-extern "C" int32_t n2v_cbow_max_sentence(void) { return kMaxSentence; }
+extern "C" int32_t n2v_cbow_max_sentence(void) { return kSlotTokens; }
 
 extern "C" int n2v_cbow_corpus_check(const int32_t* tokens, const int64_t* offsets, int64_t n_sentences, int64_t n_tokens,
                                      int64_t n_words, int32_t max_len, int32_t* status, void* stream) {
-    if (n_sentences < 0 || n_tokens < 0 || n_words < 1 || n_words > 0x7fffffffLL || max_len < 1 || max_len > kMaxSentence)
+    if (n_sentences < 0 || n_tokens < 0 || n_words < 1 || n_words > 0x7fffffffLL || max_len < 1 || max_len > kSlotTokens)
         return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_corpus_check: bad size (sentences %lld, tokens %lld, words %lld, max_len %d)",
                          (long long)n_sentences, (long long)n_tokens, (long long)n_words, (int)max_len);
     if (!offsets || !status || (n_tokens > 0 && !tokens)) return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_corpus_check: null pointer");
@@ -266,50 +211,32 @@ extern "C" int n2v_cbow_train(const int32_t* tokens, const int64_t* offsets, int
                               int64_t sentences_base, int64_t sentences_step, int64_t sentences_total, int64_t alpha_batch,
                               uint64_t seed, uint64_t sentence_id_base, unsigned long long* pair_count, int32_t update_mode,
                               int32_t max_blocks, unsigned long long* work_counter, void* stream) {
-    if (n_sentences < 0 || n_tokens < 0 || n_words < 1 || n_words > 0x7fffffffLL || dim < 1 || window < 1 || negative < 0 ||
-        negative > 64 || (cbow_mean != 0 && cbow_mean != 1))
-        return n2v::fail(N2V_ERR_INVALID,
-                         "n2v_cbow_train: bad size (sentences %lld, tokens %lld, words %lld, dim %d, window %d, negative %d, "
-                         "cbow_mean %d)", (long long)n_sentences, (long long)n_tokens, (long long)n_words, (int)dim, (int)window,
-                         (int)negative, (int)cbow_mean);
-    if (max_len < 1 || max_len > kMaxSentence)
-        return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_train: max_len %d outside [1, %d]", (int)max_len, kMaxSentence);
-    if (update_mode != N2V_SGNS_ATOMIC)
-        return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_train: update_mode %d: only N2V_SGNS_ATOMIC (lossless rows) is offered",
-                         (int)update_mode);
-    if (row_stride < dim || (row_stride != 64 && row_stride != 128 && row_stride != 256 && row_stride != 512))
-        return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_train: row_stride %d must be 64, 128, 256 or 512 and >= dim %d",
-                         (int)row_stride, (int)dim);
-    if (lut_bits < 1 || lut_bits > 24) return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_train: lut_bits %d", (int)lut_bits);
-    if (sentences_total < 1 || alpha_batch < 1 || sentences_step < 1 || sentences_base < 0)
-        return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_train: bad schedule");
+    const char* who = "n2v_cbow_train";
+    char size_tail[32];
+    snprintf(size_tail, sizeof(size_tail), ", cbow_mean %d", (int)cbow_mean);
+    int32_t slot = 0;
+    if (int rc = refuse_ragged(who, cbow_mean == 0 || cbow_mean == 1, size_tail, n_sentences, n_tokens, n_words, dim, window,
+                               negative, max_len, 0, update_mode, row_stride, lut_bits, sentences_base, sentences_step,
+                               sentences_total, alpha_batch, &slot))
+        return rc;
     if (n_sentences == 0 || n_tokens == 0) return N2V_OK;
-    if (!tokens || !offsets || !syn0 || !syn1neg || (negative > 0 && (!cum_table || !lut)))
-        return n2v::fail(N2V_ERR_INVALID, "n2v_cbow_train: null pointer");
+    if (int rc = refuse_ragged_null(who, tokens, offsets, syn0, syn1neg, negative, cum_table, lut)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_exp_table()) return rc;
+    if (int rc = upload_exp_table(who)) return rc;
 
     CbowArgs a;
-    a.tokens = tokens; a.offsets = offsets; a.n_sent = n_sentences; a.n_tokens = n_tokens; a.n_words = n_words;
-    a.syn0 = syn0; a.syn1neg = syn1neg; a.row_stride = row_stride;
-    a.window = window; a.negative = negative; a.cbow_mean = cbow_mean; a.sample_int = sample_int;
-    a.cum_table = cum_table; a.lut = lut; a.lut_shift = 31 - lut_bits;
-    a.alpha0 = alpha; a.min_alpha = min_alpha;
-    a.sent_base = sentences_base; a.sent_step = sentences_step; a.sent_total = sentences_total;
-    a.alpha_batch = alpha_batch;
-    a.seed = seed; a.sent_id_base = sentence_id_base; a.centre_count = pair_count;
-    a.work = work_counter;
-    a.lpad = (max_len + 63) & ~63;
-    const size_t shmem = (size_t)4 * a.lpad * sizeof(int32_t);   // <= 64 KB by max_len <= kMaxSentence
-    int64_t blocks = (n_sentences + 3) / 4;
+    a.w = w2v_args(syn0, syn1neg, n_words, row_stride, window, negative, sample_int, cum_table, lut, lut_bits, alpha, min_alpha,
+                   sentences_base, sentences_step, sentences_total, alpha_batch, seed, sentence_id_base, pair_count,
+                   work_counter, slot);
+    a.tokens = tokens; a.offsets = offsets; a.n_sent = n_sentences; a.n_tokens = n_tokens; a.cbow_mean = cbow_mean;
+    const size_t shmem = (size_t)4 * slot * sizeof(int32_t);   // <= 64 KB by max_len <= kSlotTokens
     // the SGNS grid for lossless rows (n2v_sgns_default_blocks: at most one wavefront per 64 vocabulary rows, whole
     // workgroups per CU); nothing about CBOW was scored against a comparator at any grid
-    const int64_t cap = max_blocks > 0 ? max_blocks : n2v_sgns_default_blocks(n_words, N2V_SGNS_ATOMIC);
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
-    if (n_sentences <= blocks * 4) a.work = nullptr;   // no wave gets a second sentence: no hand-out needed
-    if (a.work && hipMemsetAsync(a.work, 0, sizeof(unsigned long long), st) != hipSuccess)
-        return n2v::fail(N2V_ERR_HIP, "n2v_cbow_train: resetting the work counter failed");
+    dim3 grid;
+    const dim3 block(256);
+    if (int rc = w2v_grid(who, n_sentences, max_blocks > 0 ? max_blocks : n2v_sgns_default_blocks(n_words, N2V_SGNS_ATOMIC),
+                          a.w, st, &grid))
+        return rc;
 #define N2V_CBOW_LAUNCH(V)                                                                       \
     if (negative <= 5) hipLaunchKernelGGL((cbow_kernel<V, 6>), grid, block, shmem, st, a);       \
     else hipLaunchKernelGGL((cbow_kernel<V, 8>), grid, block, shmem, st, a)

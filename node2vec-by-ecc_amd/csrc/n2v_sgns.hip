@@ -38,26 +38,12 @@
 namespace {
 
 struct SgnsArgs {
+    W2vArgs w;        // id_base: id of walk 0
     const int32_t* walks;
     const int32_t* lens;
     int64_t n_walks;
     int32_t walk_stride;
-    float* syn0;
-    float* syn1neg;
-    int32_t row_stride;
-    int32_t window, negative;
-    const uint32_t* sample_int;
-    const uint32_t* cum_table;
-    const uint32_t* lut;
-    int32_t lut_shift;  // 31 - lut_bits
-    float alpha0, min_alpha;
-    int64_t sent_base, sent_step, sent_total, alpha_batch;
-    uint64_t seed, walk_id_base;
-    unsigned long long* pair_count;
-    unsigned long long* work;    // NULL: static grid stride; else the in-order item counter (reset by the launch)
-    int32_t lpad;
     int32_t splits;   // wavefronts per walk (>= 1): split s trains the centres [s*n/S, (s+1)*n/S) of the sentence
-    int32_t predraw;  // 1: all negatives of a centre are drawn by the lanes in parallel before its pairs (short launches)
     // span mode (n2v_sgns_train_span): which walks this launch trains is read from device memory, so that a captured
     // launch can be replayed for every merge interval of a pass
     const int64_t* dyn;          // NULL, or {base interval index, sentences of earlier epochs}
@@ -75,8 +61,8 @@ __device__ __forceinline__ void resolve_span(SgnsArgs& a) {
     a.n_walks = e - b;
     a.walks += b * a.walk_stride;
     if (a.lens) a.lens += b;
-    a.sent_base = epoch_base + b * a.sent_step;
-    a.walk_id_base = (uint64_t)(epoch_base + a.dyn_shard_offset + b);
+    a.w.sent_base = epoch_base + b * a.w.sent_step;
+    a.w.id_base = (uint64_t)(epoch_base + a.dyn_shard_offset + b);
 }
 
 template <int VPL, int G, int MODE>
@@ -91,7 +77,7 @@ __global__ void __launch_bounds__(256) sgns_kernel(SgnsArgs a_in) {
     // the wave index is the same in all 64 lanes: tell the compiler, so that everything derived from
     // it (walk id, loop bounds, table sizes) is scalar and loops branch on SCC instead of EXEC
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int32_t* sent = smem + wv * a.lpad;
+    int32_t* sent = smem + wv * a.w.lpad;
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     const int my_k = bitrev3(lane & 7);  // which of the 8 reduced values this lane ends up holding
     unsigned long long pairs_done = 0;
@@ -104,232 +90,27 @@ __global__ void __launch_bounds__(256) sgns_kernel(SgnsArgs a_in) {
     const int64_t n_items = a.n_walks * S;
     // (every item comes off the counter, the first one too: a workgroup that only becomes resident late in the pass must not
     // start with the early sentence its index names — measured: -0.0037 at 3072 workgroups on the 400k fixture)
-    for (int64_t item = a.work ? next_item(a.work, lane) : (int64_t)blockIdx.x * 4 + wv; item < n_items;
-         item = a.work ? next_item(a.work, lane) : item + n_waves) {
+    for (int64_t item = a.w.work ? next_item(a.w.work, lane) : (int64_t)blockIdx.x * 4 + wv; item < n_items;
+         item = a.w.work ? next_item(a.w.work, lane) : item + n_waves) {
         const int64_t wi = S == 1 ? item : item / S;
         const int sp = S == 1 ? 0 : (int)(item - wi * S);
         const int len = a.lens ? a.lens[wi] : a.walk_stride;
-        const uint64_t wid = a.walk_id_base + (uint64_t)wi;
-        // ---- effective sentence: drop padding and sub-sampled words, keep order
-        int n_eff = 0;
-        for (int base = 0; base < len; base += 64) {
-            const int pos = base + lane;
-            bool keep = false;
-            int32_t tok = -1;
-            if (pos < len) {
-                tok = a.walks[wi * a.walk_stride + pos];
-                keep = tok >= 0;
-                if (keep && a.sample_int) keep = !(a.sample_int[tok] < hash32(a.seed, wid, (uint32_t)pos, 0x5AB));
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) sent[n_eff + __popcll(m & ((1ULL << lane) - 1ULL))] = tok;
-            n_eff += __popcll(m);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-        // ---- learning rate of this walk (gensim: linear decay, stepped per job)
-        const int64_t pushed = a.sent_base + (wi / a.alpha_batch) * a.alpha_batch * a.sent_step;
-        float alpha = a.alpha0 - (a.alpha0 - a.min_alpha) * (float)((double)pushed / (double)a.sent_total);
-        alpha = fmaxf(alpha, a.min_alpha);
-
-        uint64_t lcg = mix64(a.seed ^ mix64(wid + 0x632BE59BD9B4E019ULL)) & kLcgMask;
+        const uint64_t wid = a.w.id_base + (uint64_t)wi;
+        const int n_eff = stage_sentence<false>(a.w, a.walks + wi * a.walk_stride, len, wid, lane, sent, 0, a.w.lpad, false);
+        slot_staged();
+        const float alpha = sentence_alpha(a.w, wi);
+        uint64_t lcg = sentence_lcg(a.w.seed, wid);
         int i_begin = 0, i_end = n_eff;
         if (S > 1) {
             i_begin = (int)((int64_t)sp * n_eff / S);
             i_end = (int)((int64_t)(sp + 1) * n_eff / S);
-            // draws of the centres before i_begin: `negative` per (centre, context) pair
-            int pairs_before = 0;
-            for (int base = 0; base < i_begin; base += 64) {
-                const int i = base + lane;
-                int np = 0;
-                if (i < i_begin) {
-                    const int rb = (int)(hash32(a.seed, wid, (uint32_t)i, 0xB17) % (uint32_t)a.window);
-                    const int lo = max(0, i - a.window + rb), hi = min(n_eff, i + a.window + 1 - rb);
-                    np = hi - lo > 1 ? hi - lo - 1 : 0;
-                }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) np += __shfl_xor(np, o, 64);
-                pairs_before += np;
-            }
-            lcg = lcg_skip(lcg, (uint64_t)pairs_before * (uint64_t)a.negative);
+            lcg = lcg_skip_to_centre(a.w, wid, n_eff, i_begin, lcg, lane);
         }
-
-        for (int i = i_begin; i < i_end; ++i) {
-            const int32_t ci = __builtin_amdgcn_readfirstlane(sent[i]);
-            const int rb = (int)(hash32(a.seed, wid, (uint32_t)i, 0xB17) % (uint32_t)a.window);
-            const int lo = max(0, i - a.window + rb), hi = min(n_eff, i + a.window + 1 - rb);
-            if (hi - lo <= 1) continue;
-            Row<VPL> c = load_row<VPL, MODE>(a.syn1neg, ci, a.row_stride, lane);
-            Row<VPL> cd;  // kAtomic: this wave's accumulated change of the centre row
-#pragma unroll
-            for (int v = 0; v < VPL; ++v) cd.v[v] = 0.f;
-            // A wave's pairs are a chain of dependent loads, and the look-up of the negatives (bucket index, then a
-            // bisect of the cumulative table) is two to three links of it per pair — visible even in full-size launches
-            // at 7 waves per SIMD.  With predraw the lanes make ALL draws of the centre at once — draw number d
-            // of the centre uses the walk's LCG advanced d times, exactly the state the pair-by-pair path reaches —
-            // and a pair fetches its targets from the lanes that hold them.
-            const int nd = (hi - lo - 1) * a.negative;
-            const bool pre = a.predraw && nd <= 128;
-            int32_t drawn0 = -1, drawn1 = -1;   // draws 0..63 and 64..127 of this centre, one per lane
-            if (pre) {
-#pragma unroll
-                for (int half = 0; half < 2; ++half) {
-                    const int d = half * 64 + lane;
-                    int32_t t = -1;
-                    if (d < nd) {
-                        const uint64_t s = lcg_skip(lcg, (uint64_t)d);
-                        t = draw_target(a.cum_table, a.lut, a.lut_shift, (uint32_t)((s >> 16) % 2147483647ULL));
-                        if (t == ci) t = -1;  // `if target_index == word_index: continue`
-                    }
-                    if (half == 0) drawn0 = t;
-                    else drawn1 = t;
-                }
-            }
-            int pidx = 0;  // number of this pair among the centre's pairs
-            for (int j = lo; j < hi; ++j) {
-                if (j == i) continue;
-                const int32_t xj = __builtin_amdgcn_readfirstlane(sent[j]);
-                Row<VPL> h = load_row<VPL, MODE>(a.syn0, xj, a.row_stride, lane);
-                Row<VPL> work;
-#pragma unroll
-                for (int v = 0; v < VPL; ++v) work.v[v] = 0.f;
-                // targets are processed 8 at a time: slot 0 of the first group is the centre word
-                for (int t0 = 0; t0 < a.negative + 1; t0 += 8) {
-                    // lane k (k < 8) draws the target of slot k of this group
-                    int32_t my_t = -1;
-                    if (pre) {   // negative <= 7: one group, lane k in [1, negative] holds target k
-                        const int d = min(max(pidx * a.negative + lane - 1, 0), 127);
-                        const int v0 = __builtin_amdgcn_ds_bpermute((d & 63) << 2, drawn0);
-                        const int v1 = __builtin_amdgcn_ds_bpermute((d & 63) << 2, drawn1);
-                        if (lane >= 1 && lane <= a.negative) my_t = d < 64 ? v0 : v1;
-                    } else {
-                        const int tk = t0 + lane;  // target number: 0 = positive, d >= 1 = d-th negative
-                        if (lane < 8 && tk >= 1 && tk <= a.negative) {
-                            uint64_t s = lcg;  // state of the first draw of this group
-                            for (int d = max(t0, 1); d < tk; ++d) s = (s * kLcgA + kLcgC) & kLcgMask;
-                            const uint32_t r = (uint32_t)((s >> 16) % 2147483647ULL);
-                            my_t = draw_target(a.cum_table, a.lut, a.lut_shift, r);
-                            if (my_t == ci) my_t = -1;  // `if target_index == word_index: continue`
-                        }
-                    }
-                    int32_t tgt[G];
-                    Row<VPL> n[G];
-                    float p[8];
-#pragma unroll
-                    for (int k = 0; k < G; ++k) {
-                        tgt[k] = __builtin_amdgcn_readlane(my_t, k);
-                        if (k == 0 && t0 == 0) tgt[k] = ci;
-                    }
-                    // A row drawn by two slots of the group (common where a few hubs hold most of the unigram^0.75
-                    // mass): the sequential rule lets the later slot see the row the earlier one updated.  The targets
-                    // are scalar, so a few scalar compares find such a slot; it sits out the group's parallel pass and
-                    // is trained after it, from the row as this wave has updated it (in memory by then).  Only the
-                    // order among slots of ONE row matters (another row's update changes neither h nor this row), and
-                    // the late slot's registers are free again by then: carrying the updated row over in registers
-                    // keeps all rows of the group live and spills at d = 128.
-                    uint32_t late = 0;
-#pragma unroll
-                    for (int k = 1; k < G; ++k)
-#pragma unroll
-                        for (int k1 = 0; k1 < k; ++k1)
-                            if (tgt[k] >= 0 && tgt[k] == tgt[k1]) late |= 1u << k;
-#pragma unroll
-                    for (int k = 0; k < G; ++k) {
-                        if (k == 0 && t0 == 0) {
-                            n[k] = c;
-                        } else if (tgt[k] >= 0 && !(late >> k & 1)) {
-                            n[k] = load_row<VPL, MODE>(a.syn1neg, tgt[k], a.row_stride, lane);
-                        } else {
-#pragma unroll
-                            for (int v = 0; v < VPL; ++v) n[k].v[v] = 0.f;
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        float acc = 0.f;
-                        if (k < G) {
-#pragma unroll
-                            for (int v = 0; v < VPL; ++v) acc = fmaf(h.v[v], n[k].v[v], acc);
-                        }
-                        p[k] = acc;
-                    }
-                    const float f = reduce8(p, lane);
-                    // this lane's own target: sigmoid table, gradient
-                    float g = 0.f;
-                    if (f > -kMaxExp && f < kMaxExp) {
-                        const float sig = c_exp_table[(int)((f + kMaxExp) * (float)(kExpTableSize / (int)kMaxExp / 2))];
-                        const float label = (my_k == 0 && t0 == 0) ? 1.f : 0.f;
-                        g = (label - sig) * alpha;
-                    }
-#pragma unroll
-                    for (int k = 0; k < G; ++k) {
-                        if (tgt[k] < 0 || (late >> k & 1)) continue;
-                        const float gk = __builtin_bit_cast(
-                            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, g), bitrev3(k)));
-                        if (gk == 0.f) continue;  // |f| >= MAX_EXP: no update at all
-                        Row<VPL> dn;
-#pragma unroll
-                        for (int v = 0; v < VPL; ++v) {
-                            work.v[v] = fmaf(gk, n[k].v[v], work.v[v]);
-                            dn.v[v] = gk * h.v[v];
-                            n[k].v[v] += dn.v[v];
-                        }
-                        if (k == 0 && t0 == 0) {
-                            c = n[k];
-#pragma unroll
-                            for (int v = 0; v < VPL; ++v) cd.v[v] += dn.v[v];
-                        } else if constexpr (MODE == kAtomic) {
-                            add_row<VPL>(a.syn1neg, tgt[k], a.row_stride, lane, dn);
-                        } else {
-                            store_row<VPL, MODE>(a.syn1neg, tgt[k], a.row_stride, lane, n[k]);
-                        }
-                    }
-                    if (late) {
-                        // the repeated slots, in slot order: a negative each (a draw equal to the centre is skipped)
-#pragma unroll
-                        for (int k = 1; k < G; ++k) {
-                            if (!(late >> k & 1)) continue;
-                            Row<VPL> r = load_row<VPL, MODE>(a.syn1neg, tgt[k], a.row_stride, lane);
-                            const float gk = negative_gradient<VPL>(h, r, alpha);
-                            if (gk == 0.f) continue;
-                            Row<VPL> dn;
-#pragma unroll
-                            for (int v = 0; v < VPL; ++v) {
-                                work.v[v] = fmaf(gk, r.v[v], work.v[v]);
-                                dn.v[v] = gk * h.v[v];
-                                r.v[v] += dn.v[v];
-                            }
-                            if constexpr (MODE == kAtomic) add_row<VPL>(a.syn1neg, tgt[k], a.row_stride, lane, dn);
-                            else store_row<VPL, MODE>(a.syn1neg, tgt[k], a.row_stride, lane, r);
-                        }
-                    }
-                    // advance the walk's LCG past this group's negatives
-                    const int used = min(a.negative, t0 + 7) - max(t0, 1) + 1;
-                    for (int d = 0; d < used; ++d) lcg = (lcg * kLcgA + kLcgC) & kLcgMask;
-                }
-                if constexpr (MODE == kAtomic) {
-                    add_row<VPL>(a.syn0, xj, a.row_stride, lane, work);
-                } else {
-#pragma unroll
-                    for (int v = 0; v < VPL; ++v) h.v[v] += work.v[v];
-                    store_row<VPL, MODE>(a.syn0, xj, a.row_stride, lane, h);
-                }
-                ++pidx;
-                ++pairs_done;
-            }
-            // The centre row sits in registers for the whole window (~20 pairs, tens of microseconds): written back whole it
-            // would erase every update other waves made to it meanwhile — by far the longest exposure of any row.  kAgent
-            // therefore ADDS this wave's accumulated change, like kAtomic (one atomic row per centre: < 1 % of the row
-            // updates); the context and negative rows, held for one pair, keep their whole-row stores.
-            if constexpr (MODE == kAtomic) add_row<VPL>(a.syn1neg, ci, a.row_stride, lane, cd);
-            else if constexpr (MODE == kAgent) add_row_packed<VPL>(a.syn1neg, ci, a.row_stride, lane, cd);
-            else store_row<VPL, MODE>(a.syn1neg, ci, a.row_stride, lane, c);
-        }
+        for (int i = i_begin; i < i_end; ++i)
+            sg_centre_step<VPL, G, MODE>(a.w, sent, n_eff, i, wid, alpha, lane, my_k, lcg, pairs_done);
         __builtin_amdgcn_wave_barrier();  // LDS sentence is reused by the next walk
     }
-    if (a.pair_count && lane == 0 && pairs_done) atomicAdd(a.pair_count, pairs_done);
+    if (a.w.count && lane == 0 && pairs_done) atomicAdd(a.w.count, pairs_done);
 }
 
 // Opt-in variant (N2V_SGNS_SHARE_NEGATIVES): the `negative` draws are made once per CENTRE word
@@ -347,50 +128,27 @@ __global__ void __launch_bounds__(256) sgns_shared_kernel(SgnsArgs a_in) {
     // the wave index is the same in all 64 lanes: tell the compiler, so that everything derived from
     // it (walk id, loop bounds, table sizes) is scalar and loops branch on SCC instead of EXEC
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int32_t* sent = smem + wv * a.lpad;
+    int32_t* sent = smem + wv * a.w.lpad;
     const int64_t n_waves = (int64_t)gridDim.x * 4;
     const int my_k = bitrev3(lane & 7);
     unsigned long long pairs_done = 0;
 
     for (int64_t wi = (int64_t)blockIdx.x * 4 + wv; wi < a.n_walks; wi += n_waves) {
         const int len = a.lens ? a.lens[wi] : a.walk_stride;
-        const uint64_t wid = a.walk_id_base + (uint64_t)wi;
-        int n_eff = 0;
-        for (int base = 0; base < len; base += 64) {
-            const int pos = base + lane;
-            bool keep = false;
-            int32_t tok = -1;
-            if (pos < len) {
-                tok = a.walks[wi * a.walk_stride + pos];
-                keep = tok >= 0;
-                if (keep && a.sample_int) keep = !(a.sample_int[tok] < hash32(a.seed, wid, (uint32_t)pos, 0x5AB));
-            }
-            const unsigned long long m = __ballot(keep);
-            if (keep) sent[n_eff + __popcll(m & ((1ULL << lane) - 1ULL))] = tok;
-            n_eff += __popcll(m);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int64_t pushed = a.sent_base + (wi / a.alpha_batch) * a.alpha_batch * a.sent_step;
-        float alpha = a.alpha0 - (a.alpha0 - a.min_alpha) * (float)((double)pushed / (double)a.sent_total);
-        alpha = fmaxf(alpha, a.min_alpha);
-        uint64_t lcg = mix64(a.seed ^ mix64(wid + 0x632BE59BD9B4E019ULL)) & kLcgMask;
+        const uint64_t wid = a.w.id_base + (uint64_t)wi;
+        const int n_eff = stage_sentence<false>(a.w, a.walks + wi * a.walk_stride, len, wid, lane, sent, 0, a.w.lpad, false);
+        slot_staged();
+        const float alpha = sentence_alpha(a.w, wi);
+        uint64_t lcg = sentence_lcg(a.w.seed, wid);
 
         for (int i = 0; i < n_eff; ++i) {
             const int32_t ci = __builtin_amdgcn_readfirstlane(sent[i]);
-            const int rb = (int)(hash32(a.seed, wid, (uint32_t)i, 0xB17) % (uint32_t)a.window);
-            const int lo = max(0, i - a.window + rb), hi = min(n_eff, i + a.window + 1 - rb);
+            const Window w = shrunk_window(a.w, wid, i, n_eff);
+            const int lo = w.lo, hi = w.hi;
             if (hi - lo <= 1) continue;
             // targets of this centre: slot 0 = the centre itself, slots 1..negative = one draw each
-            int32_t my_t = -1;
-            if (lane >= 1 && lane <= a.negative) {
-                uint64_t s = lcg;
-                for (int d = 1; d < lane; ++d) s = (s * kLcgA + kLcgC) & kLcgMask;
-                my_t = draw_target(a.cum_table, a.lut, a.lut_shift, (uint32_t)((s >> 16) % 2147483647ULL));
-                if (my_t == ci) my_t = -1;
-            }
-            for (int d = 0; d < a.negative; ++d) lcg = (lcg * kLcgA + kLcgC) & kLcgMask;
+            const int32_t my_t = draw_group_target(a.w, lcg, 0, ci, lane);
+            lcg = lcg_past_group(lcg, a.w.negative, 0);
             int32_t tgt[8];
             Row<VPL> n[8], dn[8];
 #pragma unroll
@@ -400,7 +158,7 @@ __global__ void __launch_bounds__(256) sgns_shared_kernel(SgnsArgs a_in) {
 #pragma unroll
                 for (int k2 = 1; k2 < k; ++k2)
                     if (tgt[k] >= 0 && tgt[k] == tgt[k2]) tgt[k] = -1;
-                if (tgt[k] >= 0) n[k] = load_row<VPL, MODE>(a.syn1neg, tgt[k], a.row_stride, lane);
+                if (tgt[k] >= 0) n[k] = load_row<VPL, MODE>(a.w.syn1neg, tgt[k], a.w.row_stride, lane);
 #pragma unroll
                 for (int v = 0; v < VPL; ++v) {
                     if (tgt[k] < 0) n[k].v[v] = 0.f;
@@ -410,7 +168,7 @@ __global__ void __launch_bounds__(256) sgns_shared_kernel(SgnsArgs a_in) {
             for (int j = lo; j < hi; ++j) {
                 if (j == i) continue;
                 const int32_t xj = __builtin_amdgcn_readfirstlane(sent[j]);
-                Row<VPL> h = load_row<VPL, MODE>(a.syn0, xj, a.row_stride, lane);
+                Row<VPL> h = load_row<VPL, MODE>(a.w.syn0, xj, a.w.row_stride, lane);
                 float p[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -420,11 +178,7 @@ __global__ void __launch_bounds__(256) sgns_shared_kernel(SgnsArgs a_in) {
                     p[k] = acc;
                 }
                 const float f = reduce8(p, lane);
-                float g = 0.f;
-                if (f > -kMaxExp && f < kMaxExp) {
-                    const float sig = c_exp_table[(int)((f + kMaxExp) * (float)(kExpTableSize / (int)kMaxExp / 2))];
-                    g = ((my_k == 0 ? 1.f : 0.f) - sig) * alpha;
-                }
+                const float g = target_gradient(f, my_k == 0 ? 1.f : 0.f, alpha);
                 Row<VPL> work;
 #pragma unroll
                 for (int v = 0; v < VPL; ++v) work.v[v] = 0.f;
@@ -443,24 +197,24 @@ __global__ void __launch_bounds__(256) sgns_shared_kernel(SgnsArgs a_in) {
                     }
                 }
                 if constexpr (MODE == kAtomic) {
-                    add_row<VPL>(a.syn0, xj, a.row_stride, lane, work);
+                    add_row<VPL>(a.w.syn0, xj, a.w.row_stride, lane, work);
                 } else {
 #pragma unroll
                     for (int v = 0; v < VPL; ++v) h.v[v] += work.v[v];
-                    store_row<VPL, MODE>(a.syn0, xj, a.row_stride, lane, h);
+                    store_row<VPL, MODE>(a.w.syn0, xj, a.w.row_stride, lane, h);
                 }
                 ++pairs_done;
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 if (tgt[k] < 0) continue;
-                if constexpr (MODE == kAtomic) add_row<VPL>(a.syn1neg, tgt[k], a.row_stride, lane, dn[k]);
-                else store_row<VPL, MODE>(a.syn1neg, tgt[k], a.row_stride, lane, n[k]);
+                if constexpr (MODE == kAtomic) add_row<VPL>(a.w.syn1neg, tgt[k], a.w.row_stride, lane, dn[k]);
+                else store_row<VPL, MODE>(a.w.syn1neg, tgt[k], a.w.row_stride, lane, n[k]);
             }
         }
         __builtin_amdgcn_wave_barrier();
     }
-    if (a.pair_count && lane == 0 && pairs_done) atomicAdd(a.pair_count, pairs_done);
+    if (a.w.count && lane == 0 && pairs_done) atomicAdd(a.w.count, pairs_done);
 }
 
 // syn0 ~ U(-0.5/d, 0.5/d), syn1neg = 0 (gensim reset_weights); one Philox call per 4 floats,
@@ -524,19 +278,6 @@ extern "C" int n2v_sgns_init(float* syn0, float* syn1neg, int64_t n_words, int32
                        syn1neg, n_words, dim, row_stride, seed);
     return n2v::check_launch("n2v_sgns_init");
 }
-
-namespace {
-// predraw (parallel draws of a centre's negatives): on whenever negative <= 7 (one target group).  Measured on C3's
-// walks: full-size launches 7.98e8 -> 8.85e8 pairs/s, one wavefront per walk (latency-bound) 3.49 -> 2.67 us per pair,
-// the 83-walk launches of the tiered merges 145 -> 128 us.  N2V_SGNS_PREDRAW=0 switches it off (A/B timing, and the
-// test that both paths train the same bits).
-int predraw_mode(int walk_splits, int negative) {
-    (void)walk_splits;
-    if (negative < 1 || negative > 7) return 0;
-    const char* e = getenv("N2V_SGNS_PREDRAW");
-    return (e && e[0] == '0') ? 0 : 1;
-}
-}  // namespace
 
 namespace {
 struct SpanSpec {                // n2v_sgns_train_span; dyn == NULL: an ordinary launch
@@ -603,26 +344,20 @@ int sgns_launch(const char* who, const int32_t* walks, const int32_t* lens, int6
         return n2v::fail(N2V_ERR_INVALID, "n2v_sgns_train: walk_splits > 1 needs N2V_SGNS_ATOMIC (or N2V_SGNS_UNCHECKED)");
     if (sentences_total < 1 || alpha_batch < 1 || sentences_step < 1) return n2v::fail(N2V_ERR_INVALID, "n2v_sgns_train: bad schedule");
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = upload_exp_table()) return rc;
+    if (int rc = upload_exp_table(who)) return rc;
 
     SgnsArgs a;
+    // (the shared-negatives kernel keeps the static stride)
+    a.w = w2v_args(syn0, syn1neg, n_words, row_stride, window, negative, sample_int, cum_table, lut, lut_bits, alpha,
+                   min_alpha, sentences_base, sentences_step, sentences_total, alpha_batch, seed, walk_id_base, pair_count,
+                   share ? nullptr : work_counter, (walk_stride + 63) & ~63);
     a.walks = walks; a.lens = lens; a.n_walks = n_walks; a.walk_stride = walk_stride;
-    a.syn0 = syn0; a.syn1neg = syn1neg; a.row_stride = row_stride;
-    a.window = window; a.negative = negative; a.sample_int = sample_int;
-    a.cum_table = cum_table; a.lut = lut; a.lut_shift = 31 - lut_bits;
-    a.alpha0 = alpha; a.min_alpha = min_alpha;
-    a.work = share ? nullptr : work_counter;   // (the shared-negatives kernel keeps the static stride)
-    a.sent_base = sentences_base; a.sent_step = sentences_step; a.sent_total = sentences_total;
-    a.alpha_batch = alpha_batch;
-    a.seed = seed; a.walk_id_base = walk_id_base; a.pair_count = pair_count;
-    a.lpad = (walk_stride + 63) & ~63;
     a.splits = walk_splits;
-    a.predraw = predraw_mode(walk_splits, negative);
     a.dyn = span.dyn; a.dyn_sub = span.sub; a.dyn_subs = span.subs;
     a.dyn_n_sub_total = span.n_sub_total; a.dyn_n_local = span.n_local; a.dyn_shard_offset = span.shard_offset;
-    const size_t shmem = (size_t)4 * a.lpad * sizeof(int32_t);
-    if (shmem > 64 * 1024) return n2v::fail(N2V_ERR_INVALID, "n2v_sgns_train: walk_stride %d too long", (int)walk_stride);
-    int64_t blocks = (n_walks * walk_splits + 3) / 4;
+    const size_t shmem = (size_t)4 * a.w.lpad * sizeof(int32_t);
+    if (a.w.lpad > kSlotTokens)
+        return n2v::fail(N2V_ERR_INVALID, "n2v_sgns_train: walk_stride %d too long", (int)walk_stride);
     // default grid: 256 CUs x 12 workgroups of 4 waves (measured on C3: 2048 blocks 6.9e8 pairs/s, 3072 8.2e8, 4096
     // 8.0e8, 6144 8.3e8; at 8 waves per SIMD 8 of the 12 are resident at a time and the others follow as slots free up —
     // harmless with the in-order hand-out, and the reason the static stride lost the band at large grids: a workgroup
@@ -639,14 +374,11 @@ int sgns_launch(const char* who, const int32_t* walks, const int32_t* lens, int6
     // Both were measured with the static grid stride; with the in-order hand-out (next_item) the AUC no longer depends on
     // the grid (lossless rows: within 3e-5 of the comparator from 768 to 3072 workgroups).  The rules stay: they are what
     // the test suite validated, and they cost no speed.
-    const int64_t cap = max_blocks > 0 ? max_blocks : default_grid(n_words, update_mode);
-    if (blocks > cap) blocks = cap;
-    const dim3 grid((unsigned)blocks), block(256);
-    // a launch in which no wave gets a second item needs no hand-out (the replicas' short launches: thousands per pass,
-    // and 6 640 waves asking one address for "nothing left" cost 90 us each time)
-    if (n_walks * walk_splits <= blocks * 4) a.work = nullptr;
-    if (a.work && hipMemsetAsync(a.work, 0, sizeof(unsigned long long), st) != hipSuccess)
-        return n2v::fail(N2V_ERR_HIP, "%s: resetting the work counter failed", who);
+    dim3 grid;
+    const dim3 block(256);
+    if (int rc = w2v_grid(who, n_walks * walk_splits, max_blocks > 0 ? max_blocks : default_grid(n_words, update_mode), a.w,
+                          st, &grid))
+        return rc;
 #define N2V_SGNS_LAUNCH_M(V, M)                                                            \
     if (share) hipLaunchKernelGGL((sgns_shared_kernel<V, M>), grid, block, shmem, st, a);     \
     else if (negative <= 5) hipLaunchKernelGGL((sgns_kernel<V, 6, M>), grid, block, shmem, st, a); \

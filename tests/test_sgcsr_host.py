@@ -254,8 +254,15 @@ def test_symbol_is_declared_bound_and_exported():
     assert hasattr(lib, name) and lib.n2v_abi_version() == 5
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert "n2v_sgns_csr.hip" in mk
-    # n2v_sgns.hip is what bench.py times: the new file restates its pair step instead of editing it
-    assert "n2v_sgns.hip:159-329" in open(os.path.join(CSRC, "n2v_sgns_csr.hip")).read()
+    # one pair step: the centre step is defined once, in the shared header; both skip-gram kernels call it, and the
+    # ragged one loads, reduces and adds no row of its own
+    src = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".h"))}
+    defined = {f: len(re.findall(r"\bvoid\s+sg_centre_step\s*\(", txt)) for f, txt in src.items()}
+    assert {f: n for f, n in defined.items() if n} == {"n2v_w2v_device.h": 1}, defined
+    for f in ("n2v_sgns.hip", "n2v_sgns_csr.hip"):
+        assert len(re.findall(r"\bsg_centre_step<", src[f])) == 1, f
+    for own in ("load_row<", "add_row<", "reduce8("):
+        assert own not in src["n2v_sgns_csr.hip"], own
 
 
 def test_c_abi_refuses_bad_arguments_before_any_launch():
