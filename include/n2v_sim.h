@@ -74,6 +74,28 @@ int n2v_sim_rows_fill(const float* scores, int64_t n_rows, int64_t n_cols, int64
 int n2v_sim_rows_topk(const float* scores, int64_t n_rows, int64_t n_cols, int64_t ld, int32_t k,
                       int32_t* cols, float* vals, void* stream);
 
+/* ---- Fused k nearest neighbours (csrc/n2v_knn.hip): gensim's most_similar, src/utils.py:428-442 find_similar_users ----
+ * Q: fp32[n_q][dpad], B: fp32[n_cols][dpad], both as n2v_sim_prepare writes them (16-byte aligned, dpad a multiple of 32).
+ * method: N2V_SIM_COS or N2V_SIM_PEARSON (one kernel, the preparation differs); N2V_SIM_JSD is N2V_ERR_INVALID.  The scores
+ * are always formed on the matrix cores, by the device function n2v_sim_block's MFMA kernel runs (N2V_SIM_VECTOR is
+ * ignored): the score of (q, c) is bit for bit what n2v_sim_block writes for that pair.
+ * The candidates of query q are the columns c < n_cols except c == exclude[q] (exclude: int32[n_q] or NULL; an entry < 0
+ * or >= n_cols excludes nothing), ranked by csrc/n2v_rank.h: higher score first, equal scores by lower column, NaN below
+ * everything, -0.0 ties +0.0.  cols[q][i] / vals[q][i], i < k, are the first k IN RANK ORDER; where fewer than k candidates
+ * exist the rest is (-1, NaN).  n_seg splits the 128-column tiles into segments that run as separate workgroups (0: chosen
+ * from the CU count of the device current at the call, the same for n2v_sim_knn_scratch and n2v_sim_knn; segments beyond
+ * the number of tiles are empty and legal); a merge pass joins their partial lists.  THE
+ * RESULT DOES NOT DEPEND ON n_seg.  Nothing of size n_q * n_cols is written: scratch holds 2 * n_seg lists of k entries a
+ * query, n2v_sim_knn_scratch bytes for the n_seg the call will use, 4-byte aligned, and need not be initialised.
+ * 1 <= k <= N2V_SIM_KNN_MAX_K, 0 <= n_seg <= n2v_sim_knn_max_seg(), n_q >= 0, 0 <= n_cols < 2^31 (n_cols == 0: every
+ * entry is empty).  Bad arguments return N2V_ERR_INVALID before any launch (n2v_sim_knn_scratch: -1).                   */
+#define N2V_SIM_KNN_MAX_K 256
+int32_t n2v_sim_knn_max_k(void);
+int32_t n2v_sim_knn_max_seg(void);
+int64_t n2v_sim_knn_scratch(int64_t n_q, int32_t k, int32_t n_seg);
+int n2v_sim_knn(const float* Q, int64_t n_q, const float* B, int64_t n_cols, int32_t dpad, int32_t method,
+                const int32_t* exclude, int32_t k, int32_t n_seg, void* scratch, int32_t* cols, float* vals, void* stream);
+
 /* ---- EccenKNN: eccentricity-weighted k-NN rating prediction (csrc/n2v_eccknn.hip) --------------------------------
  * Replaces src/main_rec.py:73-151 (cosine_eccen / msd_eccen, a triple Python loop over five dense n_x x n_x arrays)
  * and :305-329 (estimate).  x is the side similarities are formed over, y the other one; ids are inner ids (first

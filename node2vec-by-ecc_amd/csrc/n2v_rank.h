@@ -32,12 +32,13 @@ __device__ __forceinline__ bool beats(uint64_t ka, int pa, uint64_t kb, int pb) 
 // Insert (cs, cp) into the sorted list ls/lp of k entries (the last one falls out), all 64 lanes together: entry i takes
 // the candidate or entry i - 1 when it does not come before the candidate.  Chunks of 64 entries from the top down, so an
 // entry is read before the chunk below it is written.  tk/tp receive the new last entry.
-__device__ __forceinline__ void list_insert(double* ls, int32_t* lp, int k, double cs, int cp, uint64_t ck, int lane,
-                                            uint64_t& tk, int& tp) {
+// S / K: double scores with uint64_t keys (n2v_rec.hip, n2v_eccknn.hip) or float scores with uint32_t keys (n2v_knn.hip).
+template <typename S, typename K>
+__device__ __forceinline__ void list_insert(S* ls, int32_t* lp, int k, S cs, int cp, K ck, int lane, K& tk, int& tp) {
     const int top = ((k - 1) >> 6) << 6;
     for (int base = top; base >= 0; base -= 64) {
         const int i = base + lane;
-        double si = __builtin_nan(""), sm = si;
+        S si = (S)__builtin_nan(""), sm = si;
         int pi = POS_NONE, pm = POS_NONE;
         if (i < k) {
             si = ls[i]; pi = lp[i];
@@ -45,7 +46,7 @@ __device__ __forceinline__ void list_insert(double* ls, int32_t* lp, int k, doub
         }
         const bool keep = beats(order_key(si), pi, ck, cp);
         const bool prev_before = i == 0 || beats(order_key(sm), pm, ck, cp);
-        const double ns = keep ? si : (prev_before ? cs : sm);
+        const S ns = keep ? si : (prev_before ? cs : sm);
         const int np = keep ? pi : (prev_before ? cp : pm);
         if (i < k && !keep) { ls[i] = ns; lp[i] = np; }
         if (base == top) {

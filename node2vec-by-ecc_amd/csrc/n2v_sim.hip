@@ -13,6 +13,7 @@
 #include "n2v_common.h"
 #include "n2v_sim.h"
 #include "n2v_rank.h"
+#include "n2v_sim_tile.h"
 
 #include <cstdlib>
 
@@ -159,63 +160,23 @@ __global__ void __launch_bounds__(256) sim_tile_kernel(TileArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------- MFMA tile (dot)
-// 128x128 scores per workgroup, 64x64 per wavefront as 2x2 blocks of v_mfma_f32_32x32x2_f32 (fp32 in, fp32
-// accumulate: the reference's float32 dot, no reduced precision).  Operands staged k-major through LDS like the
-// vector kernel; per k-pair a wave issues 4 LDS reads for 4 MFMAs (8 192 FMAs), against 8 LDS floats per 16 FMAs
-// in the vector form — the matrix pipe is what a dense fp32 contraction is for on this chip.  Operand layout of
-// the instruction: lane l supplies A[m = l % 32][k = l / 32] and B[k = l / 32][n = l % 32]; accumulator register v
-// of lane l holds D[8 * (v / 4) + 4 * (l / 32) + (v % 4)][l % 32].
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-constexpr int MT = 128;    // tile edge
-constexpr int MKC = 16;    // k-chunk per barrier
-constexpr int MLD = 132;   // LDS pitch: the two k-halves of a wave's store land 32 banks apart
+// 128x128 scores per workgroup on the matrix cores: the staging, the k-loop and the accumulator map are n2v_sim_tile.h's
+// (shared with the fused k-NN kernel of n2v_knn.hip, which must give every pair these bits).
+using n2v::floatx16;
+constexpr int MT = n2v::SIM_MT;      // tile edge
 
 template <bool SCAN>
 __global__ void __launch_bounds__(256) sim_mfma_kernel(TileArgs a) {
-    __shared__ __attribute__((aligned(16))) float As[MKC][MLD];
-    __shared__ __attribute__((aligned(16))) float Bs[MKC][MLD];
+    __shared__ __attribute__((aligned(16))) float As[n2v::SIM_MKC][n2v::SIM_MLD];
+    __shared__ __attribute__((aligned(16))) float Bs[n2v::SIM_MKC][n2v::SIM_MLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
     const int64_t r0 = a.row_begin + (int64_t)blockIdx.y * MT, c0 = (int64_t)blockIdx.x * MT;
     if (SCAN && a.upper && c0 + MT - 1 <= r0) return;
     const int lrow = tid >> 1, kq = (tid & 1) * 8;
     const int64_t ar = r0 + lrow, br = c0 + lrow;
-    const float* ap = a.A + ar * a.dpad + kq;
-    const float* bp = a.B + br * a.dpad + kq;
-    const bool a_ok = ar < a.row_end, b_ok = br < a.n_cols;
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-    const float4 z4 = {0, 0, 0, 0};
-    float4 a0 = z4, a1 = z4, b0 = z4, b1 = z4;
-    if (a_ok) { a0 = *reinterpret_cast<const float4*>(ap); a1 = *reinterpret_cast<const float4*>(ap + 4); }
-    if (b_ok) { b0 = *reinterpret_cast<const float4*>(bp); b1 = *reinterpret_cast<const float4*>(bp + 4); }
     const int kh = lane >> 5, m = lane & 31;
-    for (int k0 = 0; k0 < a.dpad; k0 += MKC) {
-        __syncthreads();
-        As[kq + 0][lrow] = a0.x; As[kq + 1][lrow] = a0.y; As[kq + 2][lrow] = a0.z; As[kq + 3][lrow] = a0.w;
-        As[kq + 4][lrow] = a1.x; As[kq + 5][lrow] = a1.y; As[kq + 6][lrow] = a1.z; As[kq + 7][lrow] = a1.w;
-        Bs[kq + 0][lrow] = b0.x; Bs[kq + 1][lrow] = b0.y; Bs[kq + 2][lrow] = b0.z; Bs[kq + 3][lrow] = b0.w;
-        Bs[kq + 4][lrow] = b1.x; Bs[kq + 5][lrow] = b1.y; Bs[kq + 6][lrow] = b1.z; Bs[kq + 7][lrow] = b1.w;
-        __syncthreads();
-        if (k0 + MKC < a.dpad) {      // next chunk's rows travel while this one is multiplied
-            a0 = a1 = b0 = b1 = z4;
-            if (a_ok) { a0 = *reinterpret_cast<const float4*>(ap + k0 + MKC); a1 = *reinterpret_cast<const float4*>(ap + k0 + MKC + 4); }
-            if (b_ok) { b0 = *reinterpret_cast<const float4*>(bp + k0 + MKC); b1 = *reinterpret_cast<const float4*>(bp + k0 + MKC + 4); }
-        }
-#pragma unroll
-        for (int kk = 0; kk < MKC; kk += 2) {
-            const float av0 = As[kk + kh][wr * 64 + m], av1 = As[kk + kh][wr * 64 + 32 + m];
-            const float bv0 = Bs[kk + kh][wc * 64 + m], bv1 = Bs[kk + kh][wc * 64 + 32 + m];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0, bv0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0, bv1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1, bv0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1, bv1, acc[1][1], 0, 0, 0);
-        }
-    }
+    floatx16 acc[2][2];
+    n2v::sim_mfma_tile(a.A + ar * a.dpad + kq, a.B + br * a.dpad + kq, ar < a.row_end, br < a.n_cols, a.dpad, As, Bs, acc, wr, wc, lrow, kq, kh, m);
     const float tau = SCAN ? *a.tau : 0.f;
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi)

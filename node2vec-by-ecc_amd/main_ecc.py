@@ -3,6 +3,7 @@
     python main_ecc.py -input ratings.csv [-split-n 10] [-out DIR] [-prefix P] [-window-col timestamp|timewindow]
                        [-save-bins FILE] [-embed DIR --num-walks 3 --walk-length 40 --dimensions 128 --window-size 10
                         --iter 1 --p 1 --q 1 --rng numpy|philox --seed 1] [-device cuda:0]
+                       [-similar-emb EMB -similar-ratio R [-similar-target UID] [-similar-name cosine_onetenth]]
 
 The reference (src/main_ecc.py:32-38, :65-74, :112-117) reads ./data/ratings.csv, computes every user's eccentricity
 ue, marks the users with `split_n` equal bins by ue and writes ./graph/ml/ue.edgelist and ue_1.edgelist .. ue_n.edgelist,
@@ -17,6 +18,9 @@ n + 1 graphs (n2v_hip.eccsplit) are computed on the device.
 -save-bins   write `uid,ue,bin` lines
 -embed       embed every non-empty graph as split_embedding.sh does, straight from the in-memory graph (no file is
              read back), and write DIR/<prefix>ue.emb, DIR/<prefix>ue_<k>.emb in word2vec text format
+-similar-emb the similar-users subgraph (src/main_ecc.py:102-104, src/utils.py:428-456): the int(R * n_users) users of the
+             word2vec text file EMB nearest to one user by cosine (n2v_hip.neighbors.find_similar_users; -similar-target,
+             default a choice seeded by --seed) and, with -out, <prefix><name>.edgelist of their rows
 Prints one line per graph: its name, nodes and adjacency entries.
 """
 import argparse
@@ -33,6 +37,10 @@ def parse_args(argv=None):
     p.add_argument("-save-bins", dest="save_bins", default=None)
     p.add_argument("-embed", default=None)
     p.add_argument("-device", default="cuda:0")
+    p.add_argument("-similar-emb", dest="similar_emb", default=None)
+    p.add_argument("-similar-ratio", dest="similar_ratio", type=float, default=None)
+    p.add_argument("-similar-target", dest="similar_target", default=None)
+    p.add_argument("-similar-name", dest="similar_name", default="cosine_onetenth")
     # split_embedding.sh's command line; everything else as src/main.py's defaults
     p.add_argument("--num-walks", dest="num_walks", type=int, default=3)
     p.add_argument("--walk-length", dest="walk_length", type=int, default=40)
@@ -48,6 +56,10 @@ def parse_args(argv=None):
         p.error("-split-n must be at least 1")
     if not (a.out or a.embed or a.save_bins):
         p.error("nothing to do: give -out, -embed or -save-bins")
+    if (a.similar_emb is None) != (a.similar_ratio is None):
+        p.error("-similar-emb and -similar-ratio go together")
+    if a.similar_emb is not None and not a.out:
+        p.error("-similar-emb writes its edge list under -out")
     for name in ("num_walks", "walk_length", "dimensions", "window_size", "iter"):
         if getattr(a, name) < 1:
             p.error("--%s must be at least 1" % name.replace("_", "-"))
@@ -79,6 +91,21 @@ def embed(split, a):
     return written
 
 
+def similar_users_graph(split, a):
+    """<out>/<prefix><name>.edgelist: the rows of the users find_similar_users names, in file order."""
+    from n2v_hip import neighbors
+    similar = neighbors.find_similar_users(a.similar_emb, a.similar_ratio, target=a.similar_target, seed=a.seed,
+                                           device=a.device)
+    rows = split.rows_of_users(similar)
+    g = split.graph_of_rows(rows, device=a.device)
+    name = a.prefix + a.similar_name + ".edgelist"
+    print("%s: %d nodes, %d entries" % (name, g.n_nodes, g.nnz))
+    os.makedirs(a.out, exist_ok=True)
+    with open(os.path.join(a.out, name), "w") as f:
+        f.write(split.edgelist_text(rows=rows))
+    return similar
+
+
 def main(a):
     import main_rec
     from n2v_hip import eccsplit
@@ -93,6 +120,8 @@ def main(a):
         write_bins(a.save_bins, split)
     if a.embed:
         embed(split, a)
+    if a.similar_emb:
+        similar_users_graph(split, a)
     return split
 
 

@@ -106,6 +106,10 @@ SIGNATURES = {
     "n2v_sim_rows_count": (C.c_int, [_ptr, _i64, _i64, _i64, C.c_float, _ptr, _ptr]),
     "n2v_sim_rows_fill": (C.c_int, [_ptr, _i64, _i64, _i64, C.c_float, _ptr, _ptr, _ptr, _ptr]),
     "n2v_sim_rows_topk": (C.c_int, [_ptr, _i64, _i64, _i64, _i32, _ptr, _ptr, _ptr]),
+    "n2v_sim_knn_max_k": (C.c_int32, []),
+    "n2v_sim_knn_max_seg": (C.c_int32, []),
+    "n2v_sim_knn_scratch": (C.c_int64, [_i64, _i32, _i32]),
+    "n2v_sim_knn": (C.c_int, [_ptr, _i64, _ptr, _i64, _i32, _i32, _ptr, _i32, _i32, _ptr, _ptr, _ptr, _ptr]),
     "n2v_eccknn_max_k": (C.c_int32, []),
     "n2v_eccknn_max_dense": (C.c_int64, []),
     "n2v_eccknn_densify": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]),

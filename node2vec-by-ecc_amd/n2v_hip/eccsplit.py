@@ -267,9 +267,20 @@ class Split:
             raise ValueError("eccsplit: graph %r, expected 0 .. %d" % (k, self.n))
         return np.arange(len(self._u)) if k == 0 else np.nonzero(self.user_bin[self._u] == k)[0]
 
-    def edgelist_text(self, k):
-        r = self.rows_of(k)
+    def rows_of_users(self, uids):
+        """Row numbers, ascending, of the users named by the raw uids given (compared as user_name does: by integer
+        value; a uid the split does not know selects nothing)."""
+        sel = np.isin(self._un, np.array([user_name(r) for r in uids], dtype=np.int64))
+        return np.nonzero(sel[self._u])[0]
+
+    def edgelist_text(self, k=None, rows=None):
+        """The reference's file text of graph k, or of the given row numbers."""
+        r = self.rows_of(k) if rows is None else np.asarray(rows, dtype=np.int64)
         return edgelist_text(self._un[self._u[r]], self._in[self._i[r]], self._fb[r])
+
+    def graph_of_rows(self, rows, device="cuda:0"):
+        """The CsrGraph of the given row numbers (ascending), as graph_from_ratings builds it."""
+        return graph_from_ratings(self._u, self._i, self._fb, self._un, self._in, rows=rows, device=device)
 
     def file_names(self, prefix=""):
         return [prefix + "ue.edgelist"] + [prefix + "ue_%d.edgelist" % k for k in range(1, self.n + 1)]

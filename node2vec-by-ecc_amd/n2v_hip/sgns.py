@@ -571,6 +571,26 @@ class KeyedVectors:
         a, b = self[w1], self[w2]
         return float(np.dot(a / np.linalg.norm(a), b / np.linalg.norm(b)))
 
+    # ---- neighbour queries (n2v_hip/neighbors.py, csrc/n2v_knn.hip): gensim 3.x's surface restated from memory, parity
+    # with gensim itself UNPINNED; scores are the device's fp32 cosines, ranked by csrc/n2v_rank.h's order
+    def init_sims(self, device=None):
+        """The unit rows on the device, built once and kept (a later call with another device rebuilds them)."""
+        from . import neighbors
+        ix = getattr(self, "_sims", None)
+        if ix is None or (device is not None and torch.device(device) != ix.device):
+            ix = self._sims = neighbors.SimilarityIndex(self, "cuda:0" if device is None else device)
+        return ix
+
+    def most_similar(self, positive=None, negative=None, topn=10, restrict_vocab=None):
+        from . import neighbors
+        return neighbors.most_similar(self, positive, negative, topn, restrict_vocab)
+
+    def similar_by_word(self, word, topn=10, restrict_vocab=None):
+        return self.most_similar(positive=[word], topn=topn, restrict_vocab=restrict_vocab)
+
+    def similar_by_vector(self, vector, topn=10, restrict_vocab=None):
+        return self.most_similar(positive=[np.asarray(vector, dtype=np.float32)], topn=topn, restrict_vocab=restrict_vocab)
+
     def save_word2vec_format(self, fname):
         with open(fname, "w") as f:
             f.write("%d %d\n" % (len(self.index2word), self.vector_size))
