@@ -7,7 +7,8 @@ pure function of (seed, sentence id, position), so the tables after the launch a
 tables before it — with chunk == 0 an item is a sentence, with chunk >= 1 a run of at most `chunk` centres of one.  A
 launch with many wavefronts stays deterministic when no two ITEMS share a row: whole sentences (chunk 0) on disjoint
 vocabulary blocks with negative=0.  The items of one chunked sentence do share rows, so a chunked multi-wave launch is
-held to its pair count only.
+held here to its pair count only; tests/test_gpu_w2v_ledger.py pins its events (pairs, draws, learning rates) through
+counting tables.
 
 Tolerance: TOL = 1e-5 of a table's largest magnitude, tests/test_gpu_sgns_exact.py's bound for this same arithmetic
 (2.7e-6 measured there).  MEASURED here on an MI355X: at most 2.35e-6.  The planted
@@ -176,7 +177,8 @@ def test_many_wavefronts_on_disjoint_rows_are_deterministic(torch_cuda, disjoint
 
 @pytest.mark.parametrize("blocks,counter", [(0, True), (7, True), (7, False)])
 def test_chunked_launch_trains_every_pair_once(torch_cuda, disjoint_case, blocks, counter):
-    """chunk 16: the items of a sentence race on its rows, so the tables are not pinned; every (centre, context) pair is
+    """chunk 16: the items of a sentence race on its rows, so the VALUES of the tables are not pinned (which pairs, draws
+    and learning rates a chunked launch trains is: tests/test_gpu_w2v_ledger.py); every (centre, context) pair is
     still trained exactly once (the count is the restatement's), nothing leaves the tables' columns."""
     torch = torch_cuda
     stats = disjoint_case[7]

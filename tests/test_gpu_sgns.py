@@ -2,8 +2,9 @@
 
 The SGNS half has no bit-level oracle for gensim itself (gensim absent; Hogwild is
 order-dependent).  The single-wave algorithm is pinned to fp32 rounding against the float64
-restatement of the kernels' own schedule in tests/test_gpu_sgns_exact.py; racing waves on shared
-rows and walk_splits > 1 stay unpinned.  What is checked here: exact properties of one update
+restatement of the kernels' own schedule in tests/test_gpu_sgns_exact.py; for racing waves on shared
+rows and walk_splits > 1, tests/test_gpu_w2v_ledger.py pins WHICH events are trained (pairs, draws, learning
+rates), while the values such a race leaves stay unpinned.  What is checked here: exact properties of one update
 (against a numpy restatement of fast_sentence_sg_neg on a corpus where every quantity is
 deterministic), structural invariants, and the acceptance band of BASELINE.json —
 link-prediction AUC within +-0.002 of the single-thread CPU comparator (oracle/sgns_oracle.c)
