@@ -249,6 +249,36 @@ int n2v_svd_estimate(const double* bu, const double* bi, const double* pu, const
                      int64_t n_items, int32_t n_factors, double mu, int32_t biased, const int32_t* q_u, const int32_t* q_i,
                      int64_t n_q, double* est, uint8_t* impossible, void* stream);
 
+/* ---- Top-N lists of the rating predictors (csrc/n2v_eccknn.hip, n2v_svd.hip, n2v_topn.h) ------------------------------
+ * What src/recsys.py sketches ("Get the top songs" per user) and surprise's recipe algo.test(build_anti_testset()) +
+ * get_top_n compute, without storing the n_users x n_items predictions.  tests/topn_reference.py is the definition.
+ * An owner is an inner user id (owners: int32[n_owners]; an id outside [0, n_users), such as -1, is an unknown user who
+ * has seen nothing).  Its candidates are the inner items 0 .. n_items - 1 it has not rated: seen_ptr int64[n_users + 1],
+ * seen_i int32[n_seen], the rated items of every user strictly ascending (a CSR that passes n2v_eccknn_csr_check; the
+ * kernels clamp every row range to [0, n_seen], so a malformed one gives wrong lists, never a fault).  A candidate's
+ * score is n2v_eccknn_estimate's (n2v_svd_estimate's) value through n2v_eccknn_predict's fallback and clip, by the same
+ * device functions: the same bits.  Ranking is the one total order of csrc/n2v_rank.h with the item id as the position:
+ * higher score first, equal scores by lower item id, -0.0 ties +0.0 (Python's stable sort(key=est, reverse=True) over the
+ * anti-testset in inner-id order).  items: int32[n_owners][top_n], score: fp64[n_owners][top_n]; an owner with fewer than
+ * top_n candidates ends in (-1, NaN) entries.  One wavefront per (owner, segment of the items), `segments` of them per
+ * owner (0: n2v_topn_segments), each with its best-top_n list in LDS; part_score fp64 / part_pos int32
+ * [n_owners][segments][top_n] are the caller's scratch, and a second kernel merges them under the same order, so the
+ * result does not depend on `segments`.  1 <= top_n <= N2V_TOPN_MAX_N, 0 <= segments <= 64, n_owners >= 1,
+ * n_items < 2^31 - 1.  n2v_eccknn_topn: (x, y) = (owner, item) when user_based, (item, owner) otherwise, so n_users is
+ * n_x or n_y; sim, yr_*, k and min_k as n2v_eccknn_estimate.  n2v_svd_topn: the tables of n2v_svd_estimate; global_mean
+ * is the fallback of an impossible estimate (the training mean), which mu is not when biased == 0.                   */
+#define N2V_TOPN_MAX_N 256
+int32_t n2v_topn_segments(int64_t n_owners, int64_t n_candidates);
+int n2v_eccknn_topn(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                    int64_t n_y, int32_t user_based, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                    const int32_t* owners, int64_t n_owners, int32_t k, int32_t min_k, double global_mean, double lo,
+                    double hi, int32_t top_n, int32_t segments, double* part_score, int32_t* part_pos, int32_t* items,
+                    double* score, void* stream);
+int n2v_svd_topn(const double* bu, const double* bi, const double* pu, const double* qi, int64_t n_users, int64_t n_items,
+                 int32_t n_factors, double mu, int32_t biased, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                 const int32_t* owners, int64_t n_owners, double global_mean, double lo, double hi, int32_t top_n,
+                 int32_t segments, double* part_score, int32_t* part_pos, int32_t* items, double* score, void* stream);
+
 /* ---- Eccentricity statistics: the ir / ie / ire / ier item weights and the per-user ue (csrc/n2v_eccstats.hip) -----
  * Replaces src/utils.py:53-153 (pandas group-bys and merges).  Rows are (user, item, feedback, timewindow) with inner
  * ids; a group is a distinct (item, timewindow) pair, numbered in ascending (item, timewindow) order.  Everything is

@@ -31,9 +31,14 @@
 //                    -0.0 ties +0.0, NaN below everything) and sums in rank order.
 //   predict_kernel   one workgroup: global-mean fallback, clip to the rating scale, and the squared errors added one
 //                    after the other in query order (rmse).
+//   eccknn_topn_kernel one wavefront per (owner, segment of the items): the owner's unseen items ascending, each through
+//                    the same knn_estimate and predict_value as the two kernels above, folded into a best-N list in LDS;
+//                    nothing of size owners x items is stored.  The S segment lists of an owner are merged under the
+//                    same order (n2v_topn.h), so the result does not depend on S.
 #include "n2v_common.h"
 #include "n2v_sim.h"
 #include "n2v_rank.h"
+#include "n2v_topn.h"
 
 namespace {
 
@@ -475,23 +480,22 @@ __global__ void __launch_bounds__(64) baselines_kernel(const int64_t* __restrict
 
 using n2v::POS_NONE, n2v::order_key, n2v::beats, n2v::list_insert;   // n2v_rank.h
 
-struct EstArgs {
+using n2v::predict_value, n2v::Seen, n2v::SeenCursor, n2v::TopList;   // n2v_topn.h
+
+struct KnnModel {
     const double* sim; int64_t n_x; const int64_t* yr_ptr; const int32_t* yr_x; const double* yr_r; int64_t n_y;
-    const int32_t* qx; const int32_t* qy; int64_t n_q; int k; int min_k;
-    double* est; int32_t* actual_k; uint8_t* impossible;
+    int k; int min_k;
 };
 
-__global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
-    __shared__ double ls[N2V_ECCKNN_MAX_K];
-    __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
-    const int64_t q = blockIdx.x;
-    const int lane = threadIdx.x;
-    const int64_t x = a.qx[q], y = a.qy[q];
-    if (x < 0 || x >= a.n_x || y < 0 || y >= a.n_y) {            // 'User and/or item is unkown.'
-        if (lane == 0) { a.est[q] = 0.0; a.actual_k[q] = 0; a.impossible[q] = 1; }
-        return;
-    }
+// The estimate of (x, y), the one copy behind estimate_kernel and eccknn_topn_kernel: all 64 lanes of a 64-thread
+// workgroup together, x and y the same in every lane, ls / lp the k-entry selection list in LDS.  Every lane leaves with
+// the same est, actual_k and return value (true: the estimate is impossible, est = 0).
+__device__ __forceinline__ bool knn_estimate(const KnnModel& a, int64_t x, int64_t y, double* ls, int32_t* lp, int lane,
+                                             double& est, int& n_pos) {
+    est = 0.0; n_pos = 0;
+    if (x < 0 || x >= a.n_x || y < 0 || y >= a.n_y) return true; // 'User and/or item is unkown.'
     const int k = a.k;
+    __syncthreads();                                              // the previous estimate's list has been read
     // the list starts as k entries (NaN, POS_NONE): below any real entry, so it is always "full"
     for (int i = lane; i < k; i += 64) { ls[i] = __builtin_nan(""); lp[i] = POS_NONE; }
     __syncthreads();
@@ -538,12 +542,64 @@ __global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
             if (sj > 0) { sum_sim = sum_sim + sj; sum_ratings = sum_ratings + tj; ++actual_k; }
         }
     }
-    if (lane == 0) {
-        const bool imp = actual_k < a.min_k;                      // 'Not enough neighbors.'
-        a.est[q] = imp ? 0.0 : sum_ratings / sum_sim;
-        a.actual_k[q] = actual_k;
-        a.impossible[q] = imp ? 1 : 0;
+    const bool imp = actual_k < a.min_k;                          // 'Not enough neighbors.'
+    est = imp ? 0.0 : sum_ratings / sum_sim;
+    n_pos = actual_k;
+    return imp;
+}
+
+struct EstArgs {
+    KnnModel m; const int32_t* qx; const int32_t* qy; int64_t n_q;
+    double* est; int32_t* actual_k; uint8_t* impossible;
+};
+
+__global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
+    __shared__ double ls[N2V_ECCKNN_MAX_K];
+    __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
+    const int64_t q = blockIdx.x;
+    const int lane = threadIdx.x;
+    double est;
+    int actual_k;
+    const bool imp = knn_estimate(a.m, a.qx[q], a.qy[q], ls, lp, lane, est, actual_k);
+    if (lane == 0) { a.est[q] = est; a.actual_k[q] = actual_k; a.impossible[q] = imp ? 1 : 0; }
+}
+
+// ---- top-N ------------------------------------------------------------------------------------------------------------
+
+struct TopnArgs {
+    KnnModel m; int user_based; Seen seen; int64_t n_items;
+    const int32_t* owners; int N; int S;
+    double global_mean, lo, hi;
+    double* part_score; int32_t* part_pos;
+};
+
+// One wavefront per (owner, segment of candidates): the owner's unseen items of the segment, ascending, each estimated
+// as (x, y) = (owner, item) when user_based and (item, owner) otherwise, clipped, and folded into the segment's best-N
+// list under the order of n2v_rank.h with the item id as the position.  An owner outside the seen CSR's rows (-1) has
+// seen nothing and every estimate of it is impossible.
+__global__ void __launch_bounds__(64) eccknn_topn_kernel(TopnArgs a) {
+    __shared__ double ls[N2V_ECCKNN_MAX_K];
+    __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
+    __shared__ double ts[N2V_TOPN_MAX_N];
+    __shared__ int32_t tp[N2V_TOPN_MAX_N];
+    const int64_t o = blockIdx.x;
+    const int seg = blockIdx.y, lane = threadIdx.x;
+    const int64_t u = a.owners[o];
+    int64_t c0, c1;
+    n2v::segment_range(a.n_items, seg, a.S, c0, c1);
+    SeenCursor cur;
+    cur.open(a.seen, u, c0);
+    TopList top;
+    top.init(ts, tp, a.N, lane);
+    for (int64_t i = c0; i < c1; ++i) {
+        if (cur.has(i)) continue;
+        double est;
+        int actual_k;
+        const bool imp = knn_estimate(a.m, a.user_based ? u : i, a.user_based ? i : u, ls, lp, lane, est, actual_k);
+        top.offer(predict_value(est, imp, a.global_mean, a.lo, a.hi), (int)i, lane);
     }
+    const int64_t base = (o * a.S + seg) * a.N;
+    top.store(a.part_score + base, a.part_pos + base, lane);
 }
 
 // ---- predict + rmse ---------------------------------------------------------------------------------------------------
@@ -557,9 +613,7 @@ __global__ void __launch_bounds__(256) predict_kernel(const double* __restrict__
     for (int64_t base = 0; base < n; base += 256) {
         const int64_t i = base + threadIdx.x;
         if (i < n) {
-            double e = imp[i] ? global_mean : est[i];
-            e = (e < hi) ? e : hi;                                // min(higher_bound, est)
-            e = (e > lo) ? e : lo;                                // max(lower_bound, est)
+            const double e = predict_value(est[i], imp[i] != 0, global_mean, lo, hi);
             pred[i] = e;
             if (r_true) { const double d = r_true[i] - e; sq[threadIdx.x] = d * d; }
         }
@@ -728,9 +782,39 @@ int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, c
     if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_q %lld outside [1, 2^31)", (long long)n_q);
     if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
     if (!sim || !yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: null pointer");
-    EstArgs a{sim, n_x, yr_ptr, yr_x, yr_r, n_y, qx, qy, n_q, k, min_k, est, actual_k, impossible};
+    EstArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, est, actual_k, impossible};
     estimate_kernel<<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a);
     return n2v::check_launch("eccknn_estimate");
+}
+
+int32_t n2v_topn_segments(int64_t n_owners, int64_t n_candidates) {
+    if (n_owners < 1 || n_candidates < 1) return 1;
+    int64_t s = (65536 + n_owners - 1) / n_owners;               // 256 one-wavefront workgroups per compute unit: the
+                                                                  // candidates' costs differ widely, short segments even them out
+    if (s > n_candidates) s = n_candidates;
+    if (s > n2v::TOPN_MAX_SEG) s = n2v::TOPN_MAX_SEG;
+    return (int32_t)(s < 1 ? 1 : s);
+}
+
+int n2v_eccknn_topn(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                    int64_t n_y, int32_t user_based, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                    const int32_t* owners, int64_t n_owners, int32_t k, int32_t min_k, double global_mean, double lo,
+                    double hi, int32_t top_n, int32_t segments, double* part_score, int32_t* part_pos, int32_t* items,
+                    double* score, void* stream) {
+    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
+    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: min_k %d < 1 (an empty neighbourhood has no mean)", min_k);
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
+    const int64_t n_users = user_based ? n_x : n_y, n_items = user_based ? n_y : n_x;
+    if (const int rc = n2v::topn_args("eccknn_topn", n_owners, n_items, top_n, segments, seen_ptr, seen_i, n_seen, owners,
+                                      part_score, part_pos, items, score))
+        return rc;
+    if (!sim || !yr_ptr) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: null pointer");
+    const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
+    TopnArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, user_based ? 1 : 0, Seen{seen_ptr, seen_i, n_users, n_seen},
+               n_items, owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
+    eccknn_topn_kernel<<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(a);
+    if (const int rc = n2v::check_launch("eccknn_topn")) return rc;
+    return n2v::topn_merge("eccknn_topn (merge)", part_score, part_pos, n_owners, S, top_n, items, score, (hipStream_t)stream);
 }
 
 int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,

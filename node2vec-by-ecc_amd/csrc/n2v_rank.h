@@ -58,4 +58,36 @@ __device__ __forceinline__ void list_insert(S* ls, int32_t* lp, int k, S cs, int
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");      // the stores are seen by this wavefront's next loads
 }
 
+// Merge S sorted lists of k entries each (list s at part_score / part_pos + s * k, S <= 64) into the k best of all of
+// them, one wavefront: lane s holds the head of list s, and k times the best head leaves.  Entry i goes to ranked[i] /
+// score[i]; an empty entry (NaN, POS_NONE) that reaches the result has its position written as `none`.
+__device__ __forceinline__ void merge_lists(const double* __restrict__ part_score, const int32_t* __restrict__ part_pos,
+                                            int S, int k, int lane, int32_t* __restrict__ ranked,
+                                            double* __restrict__ score, int none) {
+    const int64_t base = (int64_t)lane * k;
+    int h = 0;
+    double s = __builtin_nan("");
+    int p = POS_NONE;
+    if (lane < S) { s = part_score[base]; p = part_pos[base]; }
+    for (int i = 0; i < k; ++i) {
+        uint64_t bk = order_key(s);
+        int bp = p, bl = lane;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint64_t ok = __shfl_xor((unsigned long long)bk, o, 64);
+            const int op = __shfl_xor(bp, o, 64), ol = __shfl_xor(bl, o, 64);
+            if (beats(ok, op, bk, bp)) { bk = ok; bp = op; bl = ol; }
+        }
+        bl = __shfl(bl, 0, 64);
+        const double ws = __shfl(s, bl, 64);
+        const int wp = __shfl(p, bl, 64);
+        if (lane == 0) { ranked[i] = wp == POS_NONE ? none : wp; score[i] = ws; }
+        if (lane == bl) {
+            ++h;
+            s = __builtin_nan(""); p = POS_NONE;
+            if (h < k) { s = part_score[base + h]; p = part_pos[base + h]; }
+        }
+    }
+}
+
 }  // namespace n2v

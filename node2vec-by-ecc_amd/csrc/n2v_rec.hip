@@ -27,7 +27,7 @@ constexpr int LP = KC + 1;       // LDS pitch of a staged row (doubles): the 4 k
 constexpr int SP = BN + 16;      // LDS pitch of a score row: the 4 rows one accumulator register writes land 32 banks apart
 constexpr int MAX_SEG = 64;      // segments per user: one lane each in the merge
 
-using n2v::POS_NONE, n2v::order_key, n2v::beats, n2v::list_insert;   // n2v_rank.h
+using n2v::POS_NONE, n2v::order_key, n2v::beats, n2v::list_insert, n2v::merge_lists;   // n2v_rank.h
 
 struct RecArgs {
     const double* emb; int64_t n_rows; int dim; int stride;
@@ -171,37 +171,14 @@ __global__ void __launch_bounds__(256) rec_topn_kernel(RecArgs a) {
     }
 }
 
-// One wavefront per user, lane s holds the head of segment s's list; k times the best head leaves.
+// One wavefront per user merges the user's S segment lists (merge_lists, n2v_rank.h).
 __global__ void __launch_bounds__(256)
 rec_merge_kernel(const double* __restrict__ part_score, const int32_t* __restrict__ part_pos, int64_t n_users, int S, int k,
                  int32_t* __restrict__ ranked, double* __restrict__ score) {
     const int lane = threadIdx.x & 63;
     const int64_t u = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (u >= n_users) return;
-    const int64_t base = (u * S + lane) * k;
-    int h = 0;
-    double s = __builtin_nan("");
-    int p = POS_NONE;
-    if (lane < S) { s = part_score[base]; p = part_pos[base]; }
-    for (int i = 0; i < k; ++i) {
-        uint64_t bk = order_key(s);
-        int bp = p, bl = lane;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const uint64_t ok = __shfl_xor((unsigned long long)bk, o, 64);
-            const int op = __shfl_xor(bp, o, 64), ol = __shfl_xor(bl, o, 64);
-            if (beats(ok, op, bk, bp)) { bk = ok; bp = op; bl = ol; }
-        }
-        bl = __shfl(bl, 0, 64);
-        const double ws = __shfl(s, bl, 64);
-        const int wp = __shfl(p, bl, 64);
-        if (lane == 0) { ranked[u * k + i] = wp; score[u * k + i] = ws; }
-        if (lane == bl) {
-            ++h;
-            s = __builtin_nan(""); p = POS_NONE;
-            if (h < k) { s = part_score[base + h]; p = part_pos[base + h]; }
-        }
-    }
+    merge_lists(part_score + u * S * k, part_pos + u * S * k, S, k, lane, ranked + u * k, score + u * k, POS_NONE);
 }
 
 // precision_and_racall, AP, RR, nDCG (src/bine_train.py:361-406) of one user: additions in index order and divisions only.

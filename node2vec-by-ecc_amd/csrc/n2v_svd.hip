@@ -12,9 +12,12 @@
 //                        current rating's arithmetic; where the next item is the current one, the registers just
 //                        computed are handed over instead.  Neither changes an operation or its order.
 //   estimate_kernel<NS>  one wavefront per query, the same lane_dot.
+//   svd_topn_kernel<NS>  one wavefront per (owner, segment of the items): the best-N unseen items of the owner through
+//                        the same lane_dot and estimate_value, without storing the owners x items predictions.
 // fp64 throughout; -ffp-contract=off (csrc/Makefile) keeps every multiply and add separately rounded.
 #include "n2v_common.h"
 #include "n2v_sim.h"
+#include "n2v_topn.h"
 
 namespace {
 
@@ -160,11 +163,31 @@ __global__ void __launch_bounds__(64) epoch_kernel(EpochArgs a) {
 
 // ---- estimate ---------------------------------------------------------------------------------------------------------
 
-struct EstArgs {
+struct Model {
     const double* bu; const double* bi; const double* pu; const double* qi;
-    int64_t n_users, n_items, n_q;
+    int64_t n_users, n_items;
     int nf, biased;
     double mu;
+};
+
+// The estimate from the dot, the one copy behind estimate_kernel and svd_topn_kernel: ku / ki say whether u / i are
+// inside their tables, dot is lane_dot of the two rows when both are.  Returns true where the estimate is impossible.
+__device__ __forceinline__ bool estimate_value(const Model& m, bool ku, bool ki, int64_t u, int64_t i, double dot, double& est) {
+    bool imp = false;
+    if (m.biased) {
+        est = m.mu;
+        if (ku) est = est + m.bu[u];
+        if (ki) est = est + m.bi[i];
+        if (ku && ki) est = est + dot;
+    } else {
+        imp = !(ku && ki);                                        // 'User and item are unknown.'
+        est = imp ? 0.0 : dot;
+    }
+    return imp;
+}
+
+struct EstArgs {
+    Model m; int64_t n_q;
     const int32_t* q_u; const int32_t* q_i;
     double* est; uint8_t* impossible;
 };
@@ -174,28 +197,65 @@ __global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
     const int lane = threadIdx.x;
     const int64_t qn = blockIdx.x;
     const int64_t u = a.q_u[qn], i = a.q_i[qn];
-    const bool ku = u >= 0 && u < a.n_users, ki = i >= 0 && i < a.n_items;
+    const bool ku = u >= 0 && u < a.m.n_users, ki = i >= 0 && i < a.m.n_items;
     double dot = 0.0;
     if (ku && ki) {                                               // wave-uniform
         double p[NS], q[NS];
-        load_row<NS>(a.pu + u * a.nf, a.nf, lane, p);
-        load_row<NS>(a.qi + i * a.nf, a.nf, lane, q);
-        dot = lane_dot<NS>(q, p, a.nf, lane);
+        load_row<NS>(a.m.pu + u * a.m.nf, a.m.nf, lane, p);
+        load_row<NS>(a.m.qi + i * a.m.nf, a.m.nf, lane, q);
+        dot = lane_dot<NS>(q, p, a.m.nf, lane);
     }
     if (lane != 0) return;
     double est;
-    bool imp = false;
-    if (a.biased) {
-        est = a.mu;
-        if (ku) est = est + a.bu[u];
-        if (ki) est = est + a.bi[i];
-        if (ku && ki) est = est + dot;
-    } else {
-        imp = !(ku && ki);                                        // 'User and item are unknown.'
-        est = imp ? 0.0 : dot;
-    }
+    const bool imp = estimate_value(a.m, ku, ki, u, i, dot, est);
     a.est[qn] = est;
     a.impossible[qn] = imp ? 1 : 0;
+}
+
+// ---- top-N ------------------------------------------------------------------------------------------------------------
+
+struct TopnArgs {
+    Model m; n2v::Seen seen;
+    const int32_t* owners; int N; int S;
+    double global_mean, lo, hi;
+    double* part_score; int32_t* part_pos;
+};
+
+// One wavefront per (owner, segment of the items), the frame of eccknn_topn_kernel (n2v_topn.h): the owner's p row is
+// loaded once, every unseen item of the segment is one q row, the same lane_dot and estimate_value as estimate_kernel,
+// the fallback and clip of predict_value, and a fold into the segment's best-N list.
+template <int NS>
+__global__ void __launch_bounds__(64) svd_topn_kernel(TopnArgs a) {
+    __shared__ double ts[N2V_TOPN_MAX_N];
+    __shared__ int32_t tp[N2V_TOPN_MAX_N];
+    const int64_t o = blockIdx.x;
+    const int seg = blockIdx.y, lane = threadIdx.x;
+    const int64_t u = a.owners[o];
+    const bool ku = u >= 0 && u < a.m.n_users;
+    int64_t c0, c1;
+    n2v::segment_range(a.m.n_items, seg, a.S, c0, c1);
+    n2v::SeenCursor cur;
+    cur.open(a.seen, u, c0);
+    n2v::TopList top;
+    top.init(ts, tp, a.N, lane);
+    double p[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) p[k] = 0.0;
+    if (ku) load_row<NS>(a.m.pu + u * a.m.nf, a.m.nf, lane, p);
+    for (int64_t i = c0; i < c1; ++i) {
+        if (cur.has(i)) continue;
+        double dot = 0.0;
+        if (ku) {
+            double q[NS];
+            load_row<NS>(a.m.qi + i * a.m.nf, a.m.nf, lane, q);
+            dot = lane_dot<NS>(q, p, a.m.nf, lane);
+        }
+        double est;
+        const bool imp = estimate_value(a.m, ku, true, u, i, dot, est);
+        top.offer(n2v::predict_value(est, imp, a.global_mean, a.lo, a.hi), (int)i, lane);
+    }
+    const int64_t base = (o * a.S + seg) * a.N;
+    top.store(a.part_score + base, a.part_pos + base, lane);
 }
 
 #define N2V_SVD_DISPATCH(KERNEL, nf, ...)                                     \
@@ -258,9 +318,28 @@ int n2v_svd_estimate(const double* bu, const double* bi, const double* pu, const
         return n2v::fail(N2V_ERR_INVALID, "svd_estimate: n_factors %d outside [1, %d]", n_factors, MAX_FACTORS);
     if (!pu || !qi || !q_u || !q_i || !est || !impossible || (biased && (!bu || !bi)))
         return n2v::fail(N2V_ERR_INVALID, "svd_estimate: null pointer");
-    EstArgs a{bu, bi, pu, qi, n_users, n_items, n_q, n_factors, biased ? 1 : 0, mu, q_u, q_i, est, impossible};
+    EstArgs a{Model{bu, bi, pu, qi, n_users, n_items, n_factors, biased ? 1 : 0, mu}, n_q, q_u, q_i, est, impossible};
     N2V_SVD_DISPATCH(estimate_kernel, n_factors, <<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a));
     return n2v::check_launch("svd_estimate");
+}
+
+int n2v_svd_topn(const double* bu, const double* bi, const double* pu, const double* qi, int64_t n_users, int64_t n_items,
+                 int32_t n_factors, double mu, int32_t biased, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                 const int32_t* owners, int64_t n_owners, double global_mean, double lo, double hi, int32_t top_n,
+                 int32_t segments, double* part_score, int32_t* part_pos, int32_t* items, double* score, void* stream) {
+    if (n_users < 1 || n_items < 1) return n2v::fail(N2V_ERR_INVALID, "svd_topn: n_users=%lld n_items=%lld", (long long)n_users, (long long)n_items);
+    if (n_factors < 1 || n_factors > MAX_FACTORS)
+        return n2v::fail(N2V_ERR_INVALID, "svd_topn: n_factors %d outside [1, %d]", n_factors, MAX_FACTORS);
+    if (const int rc = n2v::topn_args("svd_topn", n_owners, n_items, top_n, segments, seen_ptr, seen_i, n_seen, owners,
+                                      part_score, part_pos, items, score))
+        return rc;
+    if (!pu || !qi || (biased && (!bu || !bi))) return n2v::fail(N2V_ERR_INVALID, "svd_topn: null pointer");
+    const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
+    TopnArgs a{Model{bu, bi, pu, qi, n_users, n_items, n_factors, biased ? 1 : 0, mu}, n2v::Seen{seen_ptr, seen_i, n_users, n_seen},
+               owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
+    N2V_SVD_DISPATCH(svd_topn_kernel, n_factors, <<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(a));
+    if (const int rc = n2v::check_launch("svd_topn")) return rc;
+    return n2v::topn_merge("svd_topn (merge)", part_score, part_pos, n_owners, S, top_n, items, score, (hipStream_t)stream);
 }
 
 }  // extern "C"

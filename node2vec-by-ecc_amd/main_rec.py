@@ -7,6 +7,7 @@ plain k-NN (surprise's KNNBasic) it is compared against.
                        [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
     python main_rec.py -input ratings.csv -algo mf [-factors 100] [-epochs 20] [-lr 0.005] [-reg 0.02] [-strata N|auto]
                        [-unbiased] [-test-ratio 0.2] [-seed 0] [-cv N]
+    either form:       [-topn N [-threshold T] [-save-recs FILE]]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
 -algo     eccen (the default) or knn: KNNBasic, which also takes -sim pearson and pearson_baseline (surprise's functions,
@@ -29,6 +30,14 @@ plain k-NN (surprise's KNNBasic) it is compared against.
 The split is seeded: a permutation of the ratings by numpy's RandomState(seed), the first round(n * ratio) of it are
 the test set and the rest, in file order, the training set.  -cv N runs N folds of the same permutation instead.
 Prints `RMSE: <repr>` per split (and their mean for -cv).
+-topn     with every -algo: after each split's RMSE line, rank for every test user the N training items they have not
+          rated by predicted rating (equal predictions by first appearance in the training data; fused on the device,
+          the users x items predictions are never stored) and print `F1 / MAP / MRR / NDCG @N: ...` against the split's
+          test set (the metrics of BiNE's top_N).  1 <= N <= 256.  main() then returns (rmse, (f1, map, mrr, ndcg)) per split.
+-threshold  only test items rated at least T are a user's ground truth (absent: all of them); users left without any
+          are not counted.
+-save-recs  write `user,item,score` lines, every training user's list best first; under -cv one file per fold, FILE.0,
+          FILE.1, ...
 """
 import argparse
 import sys
@@ -61,7 +70,21 @@ def parse_args(argv=None):
     p.add_argument("-strata", default=None)
     p.add_argument("-unbiased", action="store_true")
     p.add_argument("-device", default="cuda:0")
+    p.add_argument("-topn", type=int, default=None)
+    p.add_argument("-threshold", type=float, default=None)
+    p.add_argument("-save-recs", dest="save_recs", default=None)
     a = p.parse_args(argv)
+    if a.topn is None:
+        for flag, v in (("-threshold", a.threshold), ("-save-recs", a.save_recs)):
+            if v is not None:
+                p.error("%s needs -topn" % flag)
+    else:
+        from n2v_hip import eccknn
+        try:
+            eccknn.topn_options(a.topn, None)
+            eccknn.threshold_option(a.threshold)
+        except ValueError as e:
+            p.error("-topn / -threshold: %s" % e)
     if a.algo == "svd":
         p.error("-algo svd is not built: surprise's SVD applies the ratings in one sequential order.  -algo mf is the same "
                 "model and update under a deterministic stratified order (equal to surprise's only with -strata 1)")
@@ -190,7 +213,8 @@ def folds(n, n_folds, seed):
         yield np.sort(np.setdiff1d(perm, part)), part
 
 
-def run_split(args, users, items, ratings, weights, train, test):
+def fit_split(args, users, items, ratings, weights, train):
+    """The fitted algorithm of one split."""
     from n2v_hip import eccknn
     ts = eccknn.Trainset.from_ratings([users[i] for i in train], [items[i] for i in train], ratings[train],
                                       rating_scale=(float(ratings.min()), float(ratings.max())))
@@ -198,21 +222,47 @@ def run_split(args, users, items, ratings, weights, train, test):
         from n2v_hip import svd
         algo = svd.SVD(n_factors=args.factors, n_epochs=args.epochs, biased=not args.unbiased, lr_all=args.lr,
                        reg_all=args.reg, random_state=args.seed, n_strata=args.strata, device=args.device)
-        algo.fit(ts)
-        return algo.rmse([(users[i], items[i], ratings[i]) for i in test])
+        return algo.fit(ts)
     sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
     if args.algo == "knn":
         sim_options["shrinkage"] = args.shrinkage
         algo = eccknn.KNNBasic(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
-        algo.fit(ts, weights)
-        return algo.rmse([(users[i], items[i], ratings[i]) for i in test])
+        return algo.fit(ts, weights)
     algo = eccknn.EccenKNN(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
     if weights is None:
         w = np.ones(ts.n_users if args.item_based else ts.n_items)
     else:
         w = weights
-    algo.fit(ts, w)
-    return algo.rmse([(users[i], items[i], ratings[i]) for i in test])
+    return algo.fit(ts, w)
+
+
+def write_recs(path, recs):
+    with open(path, "w") as f:
+        for user, lst in recs.items():
+            for item, score in lst:
+                f.write("%s,%s,%r\n" % (user, item, score))
+
+
+def run_split(args, users, items, ratings, weights, train, test, recs_path=None):
+    """The split's rmse; with -topn, (rmse, (f1, map, mrr, ndcg)), and the lists written to recs_path when it is given."""
+    algo = fit_split(args, users, items, ratings, weights, train)
+    testset = [(users[i], items[i], ratings[i]) for i in test]
+    err = algo.rmse(testset)
+    if args.topn is None:
+        return err
+    metrics = algo.ranking_metrics(testset, args.topn, args.threshold)[:4]
+    if recs_path:
+        write_recs(recs_path, algo.recommend(args.topn))
+    return err, metrics
+
+
+def report(args, result):
+    """Prints one split's lines."""
+    if args.topn is None:
+        print("RMSE: %r" % result)
+        return
+    print("RMSE: %r" % result[0])
+    print("F1 / MAP / MRR / NDCG @%d: %r / %r / %r / %r" % ((args.topn,) + tuple(result[1])))
 
 
 def main(argv=None):
@@ -225,16 +275,17 @@ def main(argv=None):
     if args.save_weights:
         write_weights(args.save_weights, weights)
     if args.cv:
-        errs = []
-        for train, test in folds(len(ratings), args.cv, args.seed):
-            errs.append(run_split(args, users, items, ratings, weights, train, test))
-            print("RMSE: %r" % errs[-1])
-        print("mean RMSE: %r" % float(np.mean(errs)))
-        return errs
+        results = []
+        for fold, (train, test) in enumerate(folds(len(ratings), args.cv, args.seed)):
+            recs_path = "%s.%d" % (args.save_recs, fold) if args.save_recs else None
+            results.append(run_split(args, users, items, ratings, weights, train, test, recs_path))
+            report(args, results[-1])
+        print("mean RMSE: %r" % float(np.mean([r if args.topn is None else r[0] for r in results])))
+        return results
     train, test = split(len(ratings), args.test_ratio, args.seed)
-    err = run_split(args, users, items, ratings, weights, train, test)
-    print("RMSE: %r" % err)
-    return err
+    result = run_split(args, users, items, ratings, weights, train, test, args.save_recs)
+    report(args, result)
+    return result
 
 
 if __name__ == "__main__":

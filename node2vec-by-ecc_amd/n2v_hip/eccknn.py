@@ -27,6 +27,13 @@ with the ALS baselines the second one needs (src/main_rec.py:181-189).  Parity w
 same reason as above: the restatement is the definition and the kernels equal it bit for bit.  Optional weights multiply
 each co-rating's product, which is what the reference meant by passing its per-item dictionary to every similarity (:197).
 
+Top-N lists (`top_n`, and `TopN.top_n_lists` / `recommend` / `ranking_metrics` on every fitted class, n2v_hip.svd.SVD
+included): what the reference's unfinished src/recsys.py sketches and surprise documents as
+algo.test(trainset.build_anti_testset()) plus a per-user stable sort.  One fused kernel forms a user's predictions for all
+unrated items, by the same device functions as estimate_batch + predict and so by the same bits, and keeps the best n;
+the n_users x n_items predictions are never stored.  Equal predictions rank by inner item id.  The definition is
+tests/topn_reference.py; parity with surprise is unpinned as above.
+
 There is no CPU fallback.
 """
 import numpy as np
@@ -35,6 +42,8 @@ import torch
 from . import _lib
 
 MAX_K = 256                      # N2V_ECCKNN_MAX_K
+MAX_TOP_N = 256                  # N2V_TOPN_MAX_N
+MAX_SEGMENTS = 64                # segments of the candidate range per owner in the top-N kernels
 SIM_NAMES = ("cosine", "msd", "pearson", "pearson_baseline")   # the reference's construction_func keys
 _METHOD = {"cosine": 0, "msd": 1}
 _PEARSON_KIND = {"pearson": 0, "pearson_baseline": 1}          # N2V_ECCKNN_PEARSON, N2V_ECCKNN_PEARSON_BASELINE
@@ -364,9 +373,143 @@ def predict(est, impossible, global_mean, rating_scale, r_true=None):
     return (pred, float(out.item())) if r_true is not None else pred
 
 
+# ---- top-N lists ------------------------------------------------------------------------------------------------------
+
+def topn_options(n, segments):
+    """(n, segments) as the top-N calls take them; host only.  n in [1, MAX_TOP_N]; segments None (the library's choice,
+    passed on as 0) or in [1, MAX_SEGMENTS]."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)):
+        raise ValueError("n %r: an integer in [1, %d]" % (n, MAX_TOP_N))
+    if not 1 <= n <= MAX_TOP_N:
+        raise ValueError("n %d outside [1, %d]" % (n, MAX_TOP_N))
+    if segments is None:
+        return int(n), 0
+    if isinstance(segments, bool) or not isinstance(segments, (int, np.integer)):
+        raise ValueError("segments %r: None or an integer in [1, %d]" % (segments, MAX_SEGMENTS))
+    if not 1 <= segments <= MAX_SEGMENTS:
+        raise ValueError("segments %d outside [1, %d]" % (segments, MAX_SEGMENTS))
+    return int(n), int(segments)
+
+
+def threshold_option(threshold):
+    """ranking_metrics' threshold: None (every test item is ground truth) or a number that is not NaN; host only."""
+    if threshold is None:
+        return None
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or threshold != threshold:
+        raise ValueError("threshold %r: None or a number" % (threshold,))
+    return float(threshold)
+
+
+def _topn_inputs(seen, n_users, n_items, owners, dev):
+    """The checked seen CSR and the int32 owners on `dev` (every user when owners is None)."""
+    if len(seen) < 2 or seen[0].dtype != torch.int64 or seen[1].dtype != torch.int32:
+        raise ValueError("top_n: seen must be (int64 ptr, int32 item[, r]), the CSR of csr_by_x(u, i, r, n_users, n_items)")
+    if seen[0].numel() != int(n_users) + 1:
+        raise ValueError("top_n: seen has %d rows for %d users" % (seen[0].numel() - 1, n_users))
+    csr_check(seen, n_items)
+    if owners is None:
+        owners = torch.arange(int(n_users), dtype=torch.int32, device=dev)
+    owners = torch.as_tensor(owners).to(device=dev, dtype=torch.int32).contiguous()
+    if owners.dim() != 1 or owners.numel() == 0:
+        raise ValueError("top_n: owners must be a non-empty list of inner user ids")
+    return owners
+
+
+def _topn_buffers(n_owners, S, n, dev):
+    return (torch.empty((n_owners, S, n), dtype=torch.float64, device=dev),
+            torch.empty((n_owners, S, n), dtype=torch.int32, device=dev),
+            torch.empty((n_owners, n), dtype=torch.int32, device=dev),
+            torch.empty((n_owners, n), dtype=torch.float64, device=dev))
+
+
+def top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, owners=None, segments=None):
+    """(items int32 [n_owners][n], score fp64 [n_owners][n]) device tensors: per owner (inner user id, -1 = unknown) the n
+    unseen inner items with the best predictions, each prediction the bits of estimate_batch + predict for that pair, ranked
+    by descending score and ascending item id; (-1, NaN) where an owner has fewer than n candidates (n2v_eccknn_topn).
+    seen: the owner-major CSR csr_by_x(u, i, r, n_users, n_items) of the training ratings; it is checked first and a
+    malformed one is a ValueError.  owners None: every user.  segments None: the library's choice; the result does not
+    depend on it."""
+    n, segments = topn_options(n, segments)
+    _require_gpu()
+    k, min_k = int(k), int(min_k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
+    if min_k < 1:
+        raise ValueError("min_k %d < 1" % min_k)
+    n_x, n_y = sim.shape[0], yr[0].numel() - 1
+    n_users, n_items = (n_x, n_y) if user_based else (n_y, n_x)
+    dev = sim.device
+    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
+    lib = _lib.load()
+    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
+    with torch.cuda.device(dev):
+        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, dev)
+        n_seen = seen[1].numel()
+        _lib.check(lib.n2v_eccknn_topn(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y,
+                                       1 if user_based else 0, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None,
+                                       n_seen, _lib.ptr(owners), owners.numel(), k, min_k, float(global_mean),
+                                       float(rating_scale[0]), float(rating_scale[1]), n, S, _lib.ptr(part_score),
+                                       _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score), _lib.stream_ptr(dev)))
+    return items, score
+
+
+class TopN:
+    """What the fitted rating predictors share above their top-N kernel: raw ids in, lists or metrics out.  A subclass
+    has self.trainset after fit and implements _top_n(owners, n, segments) and _device()."""
+
+    def _seen(self):
+        """The owner-major CSR of the training ratings on the device, built once per fit."""
+        ts = self.trainset
+        if getattr(self, "_seen_of", None) is not ts:
+            dev = self._device()
+            to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
+            self._seen_csr = csr_by_x(to(ts.u, torch.int32), to(ts.i, torch.int32), to(ts.r, torch.float64), ts.n_users,
+                                      ts.n_items)
+            self._seen_of = ts
+        return self._seen_csr
+
+    def top_n_lists(self, n=10, users=None, segments=None):
+        """(items int32 [len(users)][n], score fp64) device tensors for raw user ids (None: every training user in
+        inner-id order); a user the trainset does not know is owner -1: items 0 .. n - 1 at the clipped training mean."""
+        topn_options(n, segments)
+        owners = None if users is None else self.trainset.inner_uids(list(users))
+        return self._top_n(owners, n, segments)
+
+    def recommend(self, n=10, users=None):
+        """{raw user: [(raw item, score), ...]} best first, at most n entries each."""
+        ts = self.trainset
+        users = list(ts._raw2inner_u) if users is None else list(users)
+        items, score = self.top_n_lists(n, users)
+        items, score = items.cpu().numpy(), score.cpu().numpy()
+        raw_items = list(ts._raw2inner_i)
+        return {ru: [(raw_items[i], float(s)) for i, s in zip(items[row], score[row]) if i >= 0]
+                for row, ru in enumerate(users)}
+
+    def ranking_metrics(self, testset, n=10, threshold=None):
+        """(f1, map, mrr, ndcg, per_user) of the top-n lists against the testset's (raw user, raw item, rating) triples,
+        through recommend.user_metrics / averages (BiNE's top_N metrics).  A user's ground truth is their test items, those
+        rated >= threshold when it is given; users without any are left out; the others keep their order of first
+        appearance.  Test items the trainset does not know count in the ground truth's length only."""
+        from . import recommend as rec
+        topn_options(n, None)
+        threshold = threshold_option(threshold)
+        truth = {}
+        for ru, ri, r in testset:
+            rated = truth.setdefault(ru, {})
+            if threshold is None or r >= threshold:
+                rated[ri] = r
+        users = [ru for ru, rated in truth.items() if rated]
+        if not users:
+            raise ValueError("ranking_metrics: no user of the testset has a ground-truth item")
+        ptr, pos, lens = rec.truth_csr(users, list(self.trainset._raw2inner_i), truth)
+        items, _ = self.top_n_lists(n, users)
+        per_user = rec.user_metrics(items, ptr, pos, lens).cpu().numpy()
+        return rec.averages(per_user) + (per_user,)
+
+
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
 
-class _SymmetricKNN:
+class _SymmetricKNN(TopN):
     """What EccenKNN and KNNBasic share: the options, the weights, the device fit and estimate / test / rmse.  A subclass
     names its similarities (_check_name) and may add to them (_similarity)."""
 
@@ -461,6 +604,14 @@ class _SymmetricKNN:
 
     def rmse(self, testset):
         return self._test(testset)[3]
+
+    def _device(self):
+        return self.sim.device
+
+    def _top_n(self, owners, n, segments):
+        ts = self.trainset
+        return top_n(self.sim, self.yr, self._seen(), self.sim_options["user_based"], self.k, self.min_k, ts.global_mean,
+                     ts.rating_scale, n, owners, segments)
 
 
 class EccenKNN(_SymmetricKNN):

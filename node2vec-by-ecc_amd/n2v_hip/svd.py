@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eccknn import PredictionImpossible, _require_gpu, predict
+from .eccknn import PredictionImpossible, TopN, _require_gpu, _topn_buffers, _topn_inputs, predict, topn_options
 
 MAX_FACTORS = 256                # n2v_svd_max_factors()
 MAX_STRATA = 32768               # n2v_svd_max_strata()
@@ -142,9 +142,31 @@ def estimate_batch(mu, biased, bu, bi, pu, qi, qu, qi_ids):
     return est, imp
 
 
+def top_n(mu, biased, bu, bi, pu, qi, seen, global_mean, rating_scale, n, owners=None, segments=None):
+    """eccknn.top_n for the factor tables (n2v_svd_topn): per owner the n unseen inner items with the best predictions,
+    each the bits of estimate_batch + eccknn.predict for that pair.  global_mean is predict's fallback (the training mean),
+    mu the model's (0.0 when not biased)."""
+    n, segments = topn_options(n, segments)
+    _require_gpu()
+    n_users, n_items = pu.shape[0], qi.shape[0]
+    dev = pu.device
+    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
+    lib = _lib.load()
+    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
+    with torch.cuda.device(dev):
+        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, dev)
+        n_seen = seen[1].numel()
+        _lib.check(lib.n2v_svd_topn(_lib.ptr(bu), _lib.ptr(bi), _lib.ptr(pu), _lib.ptr(qi), n_users, n_items, pu.shape[1],
+                                    float(mu), 1 if biased else 0, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None,
+                                    n_seen, _lib.ptr(owners), owners.numel(), float(global_mean), float(rating_scale[0]),
+                                    float(rating_scale[1]), n, S, _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items),
+                                    _lib.ptr(score), _lib.stream_ptr(dev)))
+    return items, score
+
+
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
 
-class SVD:
+class SVD(TopN):
     """surprise's SVD with its options and defaults, plus n_strata (an integer, or "auto": auto_strata) and device.
     fit(trainset) takes an eccknn.Trainset; afterwards bu, bi, pu, qi are device fp64 tensors."""
 
@@ -229,3 +251,11 @@ class SVD:
 
     def rmse(self, testset):
         return self._test(testset)[2]
+
+    def _device(self):
+        return self.pu.device
+
+    def _top_n(self, owners, n, segments):
+        ts = self.trainset
+        return top_n(self.mu, self.biased, self.bu, self.bi, self.pu, self.qi, self._seen(), ts.global_mean, ts.rating_scale,
+                     n, owners, segments)
