@@ -194,6 +194,41 @@ int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, c
                         int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
                         double* est, int32_t* actual_k, uint8_t* impossible, void* stream);
 
+/* ---- Centred k-NN: surprise's KNNWithMeans, KNNWithZScore and KNNBaseline (csrc/n2v_eccknn.hip) ------------------------
+ * The other three k-NN predictors of surprise 1.0.6, restated from memory of its source: parity with surprise itself is
+ * UNPINNED, and tests/knn_centered_reference.py is the definition the kernels equal bit for bit (fp64, no fused
+ * multiply-add, every parenthesis below one rounding).  The neighbours are selected exactly as by n2v_eccknn_estimate, by
+ * the same device function; the modes differ in what a kept neighbour (x2, s = sim[x, x2] > 0, r) adds and in the finish:
+ *   sum_sim += s; actual_k += 1; sum_ratings += t with
+ *     MEANS     t = s * (r - mu[x2])
+ *     ZSCORE    t = s * ((r - mu[x2]) / sd[x2])
+ *     BASELINE  t = s * (r - ((global_mean + bx[x2]) + by[y]))
+ *   actual_k < min_k: sum_ratings = 0 (NOT impossible, unlike n2v_eccknn_estimate);
+ *   base = mu[x] (MEANS, ZSCORE) or (global_mean + bu[u]) + bi[i] (BASELINE: the user's bias first, whichever side x is);
+ *   est = base if actual_k == 0, else base + sum_ratings / sum_sim (ZSCORE: base + (sum_ratings / sum_sim) * sd[x]).
+ * MEANS / ZSCORE: an unknown x or y is impossible (est 0, actual_k 0) and nothing else is.  BASELINE: nothing is; an
+ * unknown user drops bu[u], an unknown item drops bi[i] (both: est = global_mean), the neighbours are not visited and
+ * actual_k = 0.  tx: fp64[n_x], mu (MEANS, ZSCORE) or bx (BASELINE); sd: fp64[n_x], read by ZSCORE only; by: fp64[n_y],
+ * read by BASELINE only; (bx, by) = (bu, bi) when user_based, (bi, bu) otherwise.  A table the mode reads may not be
+ * NULL; a centering other than the three below is N2V_ERR_INVALID.  An entry of yr_x outside [0, n_x) is never used as
+ * an index: its similarity is NaN, it adds nothing and no table is read for it.
+ *
+ * n2v_eccknn_row_moments, one wavefront per row of the CSR (ptr int64[n_rows + 1], r fp64[n]; row ranges clamped to [0, n]):
+ *   mu[row] = (sum of the row's r, from 0.0, in list order) / count
+ *   sd[row] = sqrt((sum of (r - mu[row]) * (r - mu[row]), in list order) / count)
+ * An empty row gives 0 / 0.  A sd equal to 0.0 is replaced by zero_sigma unless zero_sigma is NaN (no replacement).
+ * surprise's overall sigma is the same call on one row that holds every rating.  DEVIATION: numpy's mean / std add
+ * pairwise above 8 elements; these sums are sequential.                                                               */
+#define N2V_ECCKNN_CENTER_MEANS 1
+#define N2V_ECCKNN_CENTER_ZSCORE 2
+#define N2V_ECCKNN_CENTER_BASELINE 3
+int n2v_eccknn_row_moments(const int64_t* ptr, const double* r, int64_t n_rows, int64_t n, double zero_sigma, double* mu,
+                           double* sd, void* stream);
+int n2v_eccknn_estimate_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                                 int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
+                                 int32_t centering, int32_t user_based, double global_mean, const double* tx, const double* sd,
+                                 const double* by, double* est, int32_t* actual_k, uint8_t* impossible, void* stream);
+
 /* surprise's AlgoBase.predict, restated from its documented behaviour: pred = global_mean where impossible, then
  * min(hi, .) and max(lo, .) (a NaN becomes hi).  r_true (may be NULL): *rmse = sqrt(sum((r_true - pred)^2) / n_q),
  * the sum taken in query order by one workgroup.                                                                   */
@@ -274,6 +309,14 @@ int n2v_eccknn_topn(const double* sim, int64_t n_x, const int64_t* yr_ptr, const
                     const int32_t* owners, int64_t n_owners, int32_t k, int32_t min_k, double global_mean, double lo,
                     double hi, int32_t top_n, int32_t segments, double* part_score, int32_t* part_pos, int32_t* items,
                     double* score, void* stream);
+/* n2v_eccknn_topn with the estimates of n2v_eccknn_estimate_centered (centering, tx, sd, by as there; global_mean is both
+ * the centring's and the fallback's).  Under BASELINE an unknown owner's candidates score global_mean + bi[item], clipped. */
+int n2v_eccknn_topn_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                             int64_t n_y, int32_t user_based, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                             const int32_t* owners, int64_t n_owners, int32_t k, int32_t min_k, double global_mean, double lo,
+                             double hi, int32_t top_n, int32_t segments, int32_t centering, const double* tx, const double* sd,
+                             const double* by, double* part_score, int32_t* part_pos, int32_t* items, double* score,
+                             void* stream);
 int n2v_svd_topn(const double* bu, const double* bi, const double* pu, const double* qi, int64_t n_users, int64_t n_items,
                  int32_t n_factors, double mu, int32_t biased, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
                  const int32_t* owners, int64_t n_owners, double global_mean, double lo, double hi, int32_t top_n,

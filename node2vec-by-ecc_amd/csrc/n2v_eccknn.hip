@@ -28,7 +28,11 @@
 //                    baselines 64 at a time and adds the terms (r - mean) - b in list order.
 //   estimate_kernel  one wavefront per query: gathers sim[x, x2] over the raters of y, keeps the best k of them in a
 //                    sorted LDS list under the one order of n2v_rank.h (higher sim first, equal sims by list position,
-//                    -0.0 ties +0.0, NaN below everything) and sums in rank order.
+//                    -0.0 ties +0.0, NaN below everything) and sums in rank order.  A template over the centring mode of
+//                    knn_estimate: none (EccenKNN, KNNBasic: n2v_eccknn_estimate), or the row mean, the z-score or the
+//                    baseline of surprise's KNNWithMeans / KNNWithZScore / KNNBaseline (n2v_eccknn_estimate_centered):
+//                    the same selection, three more fp64 gathers per kept neighbour, no more LDS.
+//   row_moments_kernel one wavefront per row: the mean and the population sigma of a row's ratings, each sum in list order.
 //   predict_kernel   one workgroup: global-mean fallback, clip to the rating scale, and the squared errors added one
 //                    after the other in query order (rmse).
 //   eccknn_topn_kernel one wavefront per (owner, segment of the items): the owner's unseen items ascending, each through
@@ -476,6 +480,40 @@ __global__ void __launch_bounds__(64) baselines_kernel(const int64_t* __restrict
     if (lane == 0) b_out[row] = sum / (reg + (double)cnt);
 }
 
+// ---- row moments ------------------------------------------------------------------------------------------------------
+
+// mu[row] and sd[row] of the ratings r[ptr[row] .. ptr[row + 1]), one wavefront per row, two passes: the sum from 0.0 in
+// list order over the count, then sqrt of the sum of (r - mu) * (r - mu) in list order over the count.  The lanes gather
+// 64 terms at a time; every lane then adds them one after the other.  Row ranges are clamped to [0, n]; an empty row is
+// 0 / 0.  A sigma equal to 0.0 becomes zero_sigma unless that is NaN.
+__global__ void __launch_bounds__(64) row_moments_kernel(const int64_t* __restrict__ ptr, const double* __restrict__ r,
+                                                         int64_t n, double zero_sigma, double* __restrict__ mu,
+                                                         double* __restrict__ sd) {
+    const int64_t row = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t pb = clamp64(ptr[row], 0, n), pe = clamp64(ptr[row + 1], pb, n);
+    const double cnt = (double)(pe - pb);
+    double sum = 0.0;
+    for (int64_t base = pb; base < pe; base += 64) {
+        const int64_t p = base + lane;
+        const double v = p < pe ? r[p] : 0.0;
+        const int m = pe - base < 64 ? (int)(pe - base) : 64;
+        for (int j = 0; j < m; ++j) sum = sum + __shfl(v, j, 64);  // in list order; wave-uniform
+    }
+    const double mean = sum / cnt;
+    double ss = 0.0;
+    for (int64_t base = pb; base < pe; base += 64) {
+        const int64_t p = base + lane;
+        double v = 0.0;
+        if (p < pe) { const double d = r[p] - mean; v = d * d; }
+        const int m = pe - base < 64 ? (int)(pe - base) : 64;
+        for (int j = 0; j < m; ++j) ss = ss + __shfl(v, j, 64);
+    }
+    double sigma = sqrt(ss / cnt);
+    if (sigma == 0.0 && zero_sigma == zero_sigma) sigma = zero_sigma;
+    if (lane == 0) { mu[row] = mean; sd[row] = sigma; }
+}
+
 // ---- estimate ---------------------------------------------------------------------------------------------------------
 
 using n2v::POS_NONE, n2v::order_key, n2v::beats, n2v::list_insert;   // n2v_rank.h
@@ -487,13 +525,37 @@ struct KnnModel {
     int k; int min_k;
 };
 
+// What a neighbour's rating is centred on, a compile-time mode of knn_estimate: nothing (EccenKNN, KNNBasic), the row
+// mean of x2 (KNNWithMeans), the same over the row's sigma (KNNWithZScore), or the baseline of the pair (KNNBaseline).
+constexpr int C_NONE = 0;         // then N2V_ECCKNN_CENTER_MEANS, _ZSCORE, _BASELINE
+// tx: mu[n_x] (means, z-score) or bx[n_x] (baseline); sd: sigma[n_x] (z-score); by[n_y] (baseline).  Mode none reads none.
+struct Centering {
+    double gm; int user_based; const double* tx; const double* sd; const double* by;
+};
+
 // The estimate of (x, y), the one copy behind estimate_kernel and eccknn_topn_kernel: all 64 lanes of a 64-thread
 // workgroup together, x and y the same in every lane, ls / lp the k-entry selection list in LDS.  Every lane leaves with
 // the same est, actual_k and return value (true: the estimate is impossible, est = 0).
-__device__ __forceinline__ bool knn_estimate(const KnnModel& a, int64_t x, int64_t y, double* ls, int32_t* lp, int lane,
-                                             double& est, int& n_pos) {
+// The centred modes select the same neighbours and differ in the sums and the finish: a kept neighbour adds
+// s * (r - mu[x2]), s * ((r - mu[x2]) / sd[x2]) or s * (r - ((gm + bx[x2]) + by[y])); fewer than min_k of them zero
+// sum_ratings instead of making the estimate impossible; est = base [+ sum_ratings / sum_sim [* sd[x]]] with base mu[x] or
+// (gm + bu[u]) + bi[i].  Under the baseline mode nothing is impossible: an unknown user or item drops its bias.
+template <int MODE>
+__device__ __forceinline__ bool knn_estimate(const KnnModel& a, const Centering& c, int64_t x, int64_t y, double* ls,
+                                             int32_t* lp, int lane, double& est, int& n_pos) {
     est = 0.0; n_pos = 0;
-    if (x < 0 || x >= a.n_x || y < 0 || y >= a.n_y) return true; // 'User and/or item is unkown.'
+    if (MODE == N2V_ECCKNN_CENTER_BASELINE) {
+        const bool kx = x >= 0 && x < a.n_x, ky = y >= 0 && y < a.n_y;
+        if (!(kx && ky)) {                                        // the user's bias first, whichever side x is
+            double e = c.gm;
+            if (c.user_based) { if (kx) e = e + c.tx[x]; if (ky) e = e + c.by[y]; }
+            else { if (ky) e = e + c.by[y]; if (kx) e = e + c.tx[x]; }
+            est = e;
+            return false;
+        }
+    } else {
+        if (x < 0 || x >= a.n_x || y < 0 || y >= a.n_y) return true; // 'User and/or item is unkown.'
+    }
     const int k = a.k;
     __syncthreads();                                              // the previous estimate's list has been read
     // the list starts as k entries (NaN, POS_NONE): below any real entry, so it is always "full"
@@ -526,14 +588,30 @@ __device__ __forceinline__ bool knn_estimate(const KnnModel& a, int64_t x, int64
     double sum_sim = 0.0, sum_ratings = 0.0;
     int actual_k = 0;
     const int n_sel = L < k ? L : k;
+    const double pby = MODE == N2V_ECCKNN_CENTER_BASELINE ? c.by[y] : 0.0;
     for (int base = 0; base < n_sel; base += 64) {
         const int i = base + lane;
         double s = 0.0, sr = 0.0;
         if (i < n_sel) {
             const int p = lp[i];
             if (p < L) {                                          // always: a filler is below every real entry
-                s = ls[i];
-                sr = s * a.yr_r[beg + p];                         // sim * r, rounded before it is added
+                if (MODE == C_NONE) {
+                    s = ls[i];
+                    sr = s * a.yr_r[beg + p];                     // sim * r, rounded before it is added
+                } else {
+                    // the neighbour's tables are read from the position the list kept, under the selection's own test:
+                    // an id outside [0, n_x) is in the list only with a NaN score; it adds nothing and reads nothing
+                    const int64_t x2 = a.yr_x[beg + p];
+                    if (x2 >= 0 && x2 < a.n_x) {
+                        s = ls[i];
+                        const double r = a.yr_r[beg + p];
+                        double d;
+                        if (MODE == N2V_ECCKNN_CENTER_MEANS) d = r - c.tx[x2];
+                        else if (MODE == N2V_ECCKNN_CENTER_ZSCORE) d = (r - c.tx[x2]) / c.sd[x2];
+                        else d = r - ((c.gm + c.tx[x2]) + pby);
+                        sr = s * d;
+                    }
+                }
             }
         }
         const int cnt = n_sel - base < 64 ? n_sel - base : 64;
@@ -542,10 +620,20 @@ __device__ __forceinline__ bool knn_estimate(const KnnModel& a, int64_t x, int64
             if (sj > 0) { sum_sim = sum_sim + sj; sum_ratings = sum_ratings + tj; ++actual_k; }
         }
     }
-    const bool imp = actual_k < a.min_k;                          // 'Not enough neighbors.'
-    est = imp ? 0.0 : sum_ratings / sum_sim;
     n_pos = actual_k;
-    return imp;
+    if (MODE == C_NONE) {
+        const bool imp = actual_k < a.min_k;                      // 'Not enough neighbors.'
+        est = imp ? 0.0 : sum_ratings / sum_sim;
+        return imp;
+    }
+    if (actual_k < a.min_k) sum_ratings = 0.0;                    // too few neighbours: the base alone, not impossible
+    double b;
+    if (MODE == N2V_ECCKNN_CENTER_BASELINE) b = c.user_based ? (c.gm + c.tx[x]) + pby : (c.gm + pby) + c.tx[x];
+    else b = c.tx[x];
+    if (actual_k == 0) est = b;                                   // `except ZeroDivisionError: pass`
+    else if (MODE == N2V_ECCKNN_CENTER_ZSCORE) est = b + (sum_ratings / sum_sim) * c.sd[x];
+    else est = b + sum_ratings / sum_sim;
+    return false;
 }
 
 struct EstArgs {
@@ -553,14 +641,15 @@ struct EstArgs {
     double* est; int32_t* actual_k; uint8_t* impossible;
 };
 
-__global__ void __launch_bounds__(64) estimate_kernel(EstArgs a) {
+template <int MODE>
+__global__ void __launch_bounds__(64) estimate_kernel(EstArgs a, Centering c) {
     __shared__ double ls[N2V_ECCKNN_MAX_K];
     __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
     const int64_t q = blockIdx.x;
     const int lane = threadIdx.x;
     double est;
     int actual_k;
-    const bool imp = knn_estimate(a.m, a.qx[q], a.qy[q], ls, lp, lane, est, actual_k);
+    const bool imp = knn_estimate<MODE>(a.m, c, a.qx[q], a.qy[q], ls, lp, lane, est, actual_k);
     if (lane == 0) { a.est[q] = est; a.actual_k[q] = actual_k; a.impossible[q] = imp ? 1 : 0; }
 }
 
@@ -576,8 +665,9 @@ struct TopnArgs {
 // One wavefront per (owner, segment of candidates): the owner's unseen items of the segment, ascending, each estimated
 // as (x, y) = (owner, item) when user_based and (item, owner) otherwise, clipped, and folded into the segment's best-N
 // list under the order of n2v_rank.h with the item id as the position.  An owner outside the seen CSR's rows (-1) has
-// seen nothing and every estimate of it is impossible.
-__global__ void __launch_bounds__(64) eccknn_topn_kernel(TopnArgs a) {
+// seen nothing and every estimate of it is impossible (under the baseline mode: global_mean + bi[item]).
+template <int MODE>
+__global__ void __launch_bounds__(64) eccknn_topn_kernel(TopnArgs a, Centering c) {
     __shared__ double ls[N2V_ECCKNN_MAX_K];
     __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
     __shared__ double ts[N2V_TOPN_MAX_N];
@@ -595,7 +685,7 @@ __global__ void __launch_bounds__(64) eccknn_topn_kernel(TopnArgs a) {
         if (cur.has(i)) continue;
         double est;
         int actual_k;
-        const bool imp = knn_estimate(a.m, a.user_based ? u : i, a.user_based ? i : u, ls, lp, lane, est, actual_k);
+        const bool imp = knn_estimate<MODE>(a.m, c, a.user_based ? u : i, a.user_based ? i : u, ls, lp, lane, est, actual_k);
         top.offer(predict_value(est, imp, a.global_mean, a.lo, a.hi), (int)i, lane);
     }
     const int64_t base = (o * a.S + seg) * a.N;
@@ -783,8 +873,46 @@ int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, c
     if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
     if (!sim || !yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: null pointer");
     EstArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, est, actual_k, impossible};
-    estimate_kernel<<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a);
+    estimate_kernel<C_NONE><<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a, Centering{0.0, 1, nullptr, nullptr, nullptr});
     return n2v::check_launch("eccknn_estimate");
+}
+
+// The checks the two centred calls share; 0 or the error.  A table the mode reads may not be NULL.
+static int centering_args(const char* who, int32_t centering, const double* tx, const double* sd, const double* by) {
+    if (centering != N2V_ECCKNN_CENTER_MEANS && centering != N2V_ECCKNN_CENTER_ZSCORE && centering != N2V_ECCKNN_CENTER_BASELINE)
+        return n2v::fail(N2V_ERR_INVALID, "%s: centering %d (1 means, 2 z-score, 3 baseline)", who, centering);
+    if (!tx) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (tx, the mu or bx table over x)", who);
+    if (centering == N2V_ECCKNN_CENTER_ZSCORE && !sd) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (sd, required by centering 2)", who);
+    if (centering == N2V_ECCKNN_CENTER_BASELINE && !by) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (by, required by centering 3)", who);
+    return N2V_OK;
+}
+
+int n2v_eccknn_estimate_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                                 int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
+                                 int32_t centering, int32_t user_based, double global_mean, const double* tx, const double* sd,
+                                 const double* by, double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
+    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
+    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: min_k %d < 1", min_k);
+    if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: n_q %lld outside [1, 2^31)", (long long)n_q);
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
+    if (const int rc = centering_args("eccknn_estimate_centered", centering, tx, sd, by)) return rc;
+    if (!sim || !yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: null pointer");
+    EstArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, est, actual_k, impossible};
+    const Centering c{global_mean, user_based ? 1 : 0, tx, sd, by};
+    hipStream_t s = (hipStream_t)stream;
+    if (centering == N2V_ECCKNN_CENTER_MEANS) estimate_kernel<N2V_ECCKNN_CENTER_MEANS><<<(unsigned)n_q, 64, 0, s>>>(a, c);
+    else if (centering == N2V_ECCKNN_CENTER_ZSCORE) estimate_kernel<N2V_ECCKNN_CENTER_ZSCORE><<<(unsigned)n_q, 64, 0, s>>>(a, c);
+    else estimate_kernel<N2V_ECCKNN_CENTER_BASELINE><<<(unsigned)n_q, 64, 0, s>>>(a, c);
+    return n2v::check_launch("eccknn_estimate_centered");
+}
+
+int n2v_eccknn_row_moments(const int64_t* ptr, const double* r, int64_t n_rows, int64_t n, double zero_sigma, double* mu,
+                           double* sd, void* stream) {
+    if (n_rows < 1 || n_rows > 0x7fffffff || n < 0)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_row_moments: n_rows=%lld outside [1, 2^31) or n=%lld < 0", (long long)n_rows, (long long)n);
+    if (!ptr || !mu || !sd || (n > 0 && !r)) return n2v::fail(N2V_ERR_INVALID, "eccknn_row_moments: null pointer");
+    row_moments_kernel<<<(unsigned)n_rows, 64, 0, (hipStream_t)stream>>>(ptr, r, n, zero_sigma, mu, sd);
+    return n2v::check_launch("eccknn_row_moments");
 }
 
 int32_t n2v_topn_segments(int64_t n_owners, int64_t n_candidates) {
@@ -812,9 +940,38 @@ int n2v_eccknn_topn(const double* sim, int64_t n_x, const int64_t* yr_ptr, const
     const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
     TopnArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, user_based ? 1 : 0, Seen{seen_ptr, seen_i, n_users, n_seen},
                n_items, owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
-    eccknn_topn_kernel<<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(a);
+    eccknn_topn_kernel<C_NONE><<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(
+        a, Centering{0.0, 1, nullptr, nullptr, nullptr});
     if (const int rc = n2v::check_launch("eccknn_topn")) return rc;
     return n2v::topn_merge("eccknn_topn (merge)", part_score, part_pos, n_owners, S, top_n, items, score, (hipStream_t)stream);
+}
+
+int n2v_eccknn_topn_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                             int64_t n_y, int32_t user_based, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                             const int32_t* owners, int64_t n_owners, int32_t k, int32_t min_k, double global_mean, double lo,
+                             double hi, int32_t top_n, int32_t segments, int32_t centering, const double* tx, const double* sd,
+                             const double* by, double* part_score, int32_t* part_pos, int32_t* items, double* score,
+                             void* stream) {
+    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
+    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: min_k %d < 1", min_k);
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
+    if (const int rc = centering_args("eccknn_topn_centered", centering, tx, sd, by)) return rc;
+    const int64_t n_users = user_based ? n_x : n_y, n_items = user_based ? n_y : n_x;
+    if (const int rc = n2v::topn_args("eccknn_topn_centered", n_owners, n_items, top_n, segments, seen_ptr, seen_i, n_seen, owners,
+                                      part_score, part_pos, items, score))
+        return rc;
+    if (!sim || !yr_ptr) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: null pointer");
+    const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
+    TopnArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, user_based ? 1 : 0, Seen{seen_ptr, seen_i, n_users, n_seen},
+               n_items, owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
+    const Centering c{global_mean, user_based ? 1 : 0, tx, sd, by};
+    const dim3 grid((unsigned)n_owners, (unsigned)S);
+    hipStream_t s = (hipStream_t)stream;
+    if (centering == N2V_ECCKNN_CENTER_MEANS) eccknn_topn_kernel<N2V_ECCKNN_CENTER_MEANS><<<grid, 64, 0, s>>>(a, c);
+    else if (centering == N2V_ECCKNN_CENTER_ZSCORE) eccknn_topn_kernel<N2V_ECCKNN_CENTER_ZSCORE><<<grid, 64, 0, s>>>(a, c);
+    else eccknn_topn_kernel<N2V_ECCKNN_CENTER_BASELINE><<<grid, 64, 0, s>>>(a, c);
+    if (const int rc = n2v::check_launch("eccknn_topn_centered")) return rc;
+    return n2v::topn_merge("eccknn_topn_centered (merge)", part_score, part_pos, n_owners, S, top_n, items, score, s);
 }
 
 int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,

@@ -1,7 +1,7 @@
 """Drop-in for the working part of the reference's src/main_rec.py: EccenKNN rating prediction on the device, and the
 plain k-NN (surprise's KNNBasic) it is compared against.
 
-    python main_rec.py -input ratings.csv [-algo eccen|knn] [-k 40] [-mink 1] [-sim cosine|msd|pearson|pearson_baseline]
+    python main_rec.py -input ratings.csv [-algo eccen|knn|knnmeans|knnzscore|knnbaseline] [-k 40] [-mink 1] [-sim cosine|msd|pearson|pearson_baseline]
                        [-shrinkage 100] [-item-based] [-weights FILE]
                        [-mode ir|ie|ire|ier] [-window-col timestamp|timewindow] [-save-weights FILE]
                        [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
@@ -18,6 +18,11 @@ plain k-NN (surprise's KNNBasic) it is compared against.
           -epochs, -lr and -reg are surprise's n_factors, n_epochs, lr_all and reg_all, -strata the number of strata (auto:
           chosen from the size of the training set; 1: surprise's own order), -unbiased drops the biases, and -seed also
           seeds the factors.  It takes none of -sim, -k, -mink, -weights, -mode, -item-based and -form.
+          knnmeans, knnzscore, knnbaseline: surprise's KNNWithMeans, KNNWithZScore and KNNBaseline (restated; parity with
+          surprise is unpinned), the centred k-NN predictors: the neighbours of knn, each neighbour's rating taken relative
+          to its row mean, to its row mean in units of its row sigma, or to the ALS baseline of the pair, and too few
+          neighbours leave the base estimate instead of the training mean.  They take every flag -algo knn takes, -weights /
+          -mode included (the eccentricity-weighted, centred k-NN), and none of the mf flags.
           svd itself is not built: surprise's order of the ratings is sequential, and -algo mf follows it only with -strata 1.
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
 -mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
@@ -43,6 +48,9 @@ import argparse
 import sys
 
 import numpy as np
+
+
+KNN_ALGOS = ("knn", "knnmeans", "knnzscore", "knnbaseline")     # surprise's KNNBasic and its three centred siblings
 
 
 def parse_args(argv=None):
@@ -88,8 +96,8 @@ def parse_args(argv=None):
     if a.algo == "svd":
         p.error("-algo svd is not built: surprise's SVD applies the ratings in one sequential order.  -algo mf is the same "
                 "model and update under a deterministic stratified order (equal to surprise's only with -strata 1)")
-    if a.algo not in ("eccen", "knn", "mf"):
-        p.error("-algo %s: eccen, knn or mf" % a.algo)
+    if a.algo not in ("eccen", "mf") + KNN_ALGOS:
+        p.error("-algo %s: eccen, %s or mf" % (a.algo, ", ".join(KNN_ALGOS)))
     knn_flags = (("-sim", a.sim), ("-k", a.k), ("-mink", a.mink), ("-weights", a.weights), ("-mode", a.mode),
                  ("-item-based", a.item_based or None), ("-form", a.form))
     mf_flags = (("-factors", a.factors), ("-epochs", a.epochs), ("-lr", a.lr), ("-reg", a.reg), ("-strata", a.strata),
@@ -112,8 +120,8 @@ def parse_args(argv=None):
             svd.SVD(n_factors=a.factors, n_epochs=a.epochs, lr_all=a.lr, reg_all=a.reg, n_strata=a.strata)
         except ValueError as e:
             p.error(str(e))
-    if a.sim in ("pearson", "pearson_baseline") and a.algo != "knn":
-        p.error("-sim %s is surprise's own similarity: it needs -algo knn" % a.sim)
+    if a.sim in ("pearson", "pearson_baseline") and a.algo not in KNN_ALGOS:
+        p.error("-sim %s is surprise's own similarity: it needs -algo knn (or knnmeans, knnzscore, knnbaseline)" % a.sim)
     if not 0.0 < a.test_ratio < 1.0:
         p.error("-test-ratio must be inside (0, 1)")
     if a.cv == 1 or a.cv < 0:
@@ -224,9 +232,11 @@ def fit_split(args, users, items, ratings, weights, train):
                        reg_all=args.reg, random_state=args.seed, n_strata=args.strata, device=args.device)
         return algo.fit(ts)
     sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
-    if args.algo == "knn":
+    if args.algo in KNN_ALGOS:
         sim_options["shrinkage"] = args.shrinkage
-        algo = eccknn.KNNBasic(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
+        cls = {"knn": eccknn.KNNBasic, "knnmeans": eccknn.KNNWithMeans, "knnzscore": eccknn.KNNWithZScore,
+               "knnbaseline": eccknn.KNNBaseline}[args.algo]
+        algo = cls(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
         return algo.fit(ts, weights)
     algo = eccknn.EccenKNN(k=args.k, min_k=args.mink, device=args.device, sim_options=sim_options)
     if weights is None:

@@ -125,6 +125,12 @@ SIGNATURES = {
                                             _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_eccknn_estimate": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr,
                                       _ptr]),
+    "n2v_eccknn_row_moments": (C.c_int, [_ptr, _ptr, _i64, _i64, _f64, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_estimate_centered": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _i32, _i32, _i32,
+                                               _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_topn_centered": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _i32, _i32,
+                                           _f64, _f64, _f64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                           _ptr]),
     "n2v_eccknn_predict": (C.c_int, [_ptr, _ptr, _ptr, _i64, _f64, _f64, _f64, _ptr, _ptr, _ptr]),
     "n2v_svd_max_factors": (C.c_int32, []),
     "n2v_svd_max_strata": (C.c_int32, []),

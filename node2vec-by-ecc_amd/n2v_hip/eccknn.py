@@ -27,6 +27,15 @@ with the ALS baselines the second one needs (src/main_rec.py:181-189).  Parity w
 same reason as above: the restatement is the definition and the kernels equal it bit for bit.  Optional weights multiply
 each co-rating's product, which is what the reference meant by passing its per-item dictionary to every similarity (:197).
 
+KNNWithMeans, KNNWithZScore and KNNBaseline are surprise's other three k-NN predictors on top of KNNBasic: the same
+neighbours, each neighbour's rating centred on its row mean, on its row mean in units of its row sigma, or on the ALS
+baseline of the pair, and too few neighbours leave the base estimate instead of an impossible prediction
+(`row_moments`, `estimate_batch_centered`, `top_n_centered`; three more instantiations of the one estimate function).
+fit(trainset, weights) weights the co-ratings as for KNNBasic, which gives the eccentricity-weighted centred k-NN.  The
+rules are restated from memory of scikit-surprise 1.0.6 (tests/knn_centered_reference.py); parity with surprise itself is
+unpinned, the restatement is the definition and the kernels equal it bit for bit.  Deviation: the row means and sigmas
+are sequential sums in training order, where numpy's mean / std add pairwise above 8 elements.
+
 Top-N lists (`top_n`, and `TopN.top_n_lists` / `recommend` / `ranking_metrics` on every fitted class, n2v_hip.svd.SVD
 included): what the reference's unfinished src/recsys.py sketches and surprise documents as
 algo.test(trainset.build_anti_testset()) plus a per-user stable sort.  One fused kernel forms a user's predictions for all
@@ -36,6 +45,8 @@ tests/topn_reference.py; parity with surprise is unpinned as above.
 
 There is no CPU fallback.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -50,6 +61,7 @@ _PEARSON_KIND = {"pearson": 0, "pearson_baseline": 1}          # N2V_ECCKNN_PEAR
 _PEARSON_ACC = {"pearson": ("sqi", "sqj", "si", "sj"), "pearson_baseline": ("sq_diff_i", "sq_diff_j")}   # a1 .. a4
 BSL_DEFAULTS = {"method": "als", "n_epochs": 10, "reg_u": 15, "reg_i": 10}   # surprise's baseline_als
 FORMS = ("auto", "dense", "sparse")
+CENTERINGS = {"means": 1, "zscore": 2, "baseline": 3}          # N2V_ECCKNN_CENTER_MEANS, _ZSCORE, _BASELINE
 MAX_DENSE = 1 << 31              # n2v_eccknn_max_dense()
 CSR_BAD = ((1, "xr_ptr is not monotone or leaves [0, n]"), (2, "a y outside [0, n_y)"),
            (4, "a row is not strictly ascending in y (a duplicate (x, y) pair?)"))
@@ -359,6 +371,95 @@ def estimate_batch(sim, yr, qx, qy, k, min_k):
     return est, actual_k, imp
 
 
+# ---- centred k-NN: KNNWithMeans, KNNWithZScore, KNNBaseline -------------------------------------------------------------
+
+def row_moments(ptr, r, zero_sigma=None):
+    """(mu, sd) device fp64 tensors over the rows of the CSR (ptr int64[n_rows + 1], r fp64): each row's mean and
+    population sigma, both sums sequential in list order (n2v_eccknn_row_moments).  An empty row is NaN.  zero_sigma: what
+    replaces a sigma equal to 0.0; None leaves it.  surprise's overall sigma is row_moments(tensor([0, n]), r)[1]."""
+    _require_gpu()
+    if ptr.dtype != torch.int64 or r.dtype != torch.float64 or ptr.dim() != 1 or r.dim() != 1 or ptr.numel() < 2:
+        raise ValueError("row_moments: ptr must be int64[n_rows + 1] with n_rows >= 1, r fp64[n]")
+    dev = r.device
+    lib = _lib.load()
+    n_rows, n = ptr.numel() - 1, r.numel()
+    with torch.cuda.device(dev):
+        mu = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        sd = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        _lib.check(lib.n2v_eccknn_row_moments(_lib.ptr(ptr), _lib.ptr(r) if n else None, n_rows, n,
+                                              float("nan") if zero_sigma is None else float(zero_sigma), _lib.ptr(mu),
+                                              _lib.ptr(sd), _lib.stream_ptr(dev)))
+    return mu, sd
+
+
+class Centering(collections.namedtuple("Centering", "mode user_based global_mean tx sd by")):
+    """What the centred estimates read beside sim and yr.  mode: "means", "zscore" or "baseline"; tx: mu[n_x] (means,
+    zscore) or bx[n_x] (baseline); sd: sigma[n_x] (zscore, else None); by[n_y] (baseline, else None); (bx, by) = (bu, bi)
+    when user_based, (bi, bu) otherwise.  Device fp64 tensors."""
+    __slots__ = ()
+
+
+def _centering_args(c, n_x, n_y):
+    """(code, tx, sd, by pointers) after the host checks; a table the mode reads must be there and of the right length."""
+    if not isinstance(c, Centering) or c.mode not in CENTERINGS:
+        raise ValueError("centering: a Centering whose mode is one of %s" % ", ".join(CENTERINGS))
+    need = {"means": (("tx", n_x),), "zscore": (("tx", n_x), ("sd", n_x)), "baseline": (("tx", n_x), ("by", n_y))}[c.mode]
+    for name, length in need:
+        t = getattr(c, name)
+        if t is None or t.dtype != torch.float64 or t.numel() != int(length):
+            raise ValueError("centering %s: %s must be a device fp64 tensor of %d entries" % (c.mode, name, length))
+    used = dict(need)
+    return (CENTERINGS[c.mode], _lib.ptr(c.tx), _lib.ptr(c.sd) if "sd" in used else None,
+            _lib.ptr(c.by) if "by" in used else None)
+
+
+def yr_check(yr, n_x):
+    """Raises ValueError when the rating lists yr = (ptr int64[n_y + 1], x int32, r fp64) are malformed: the centred
+    estimates index their tables with yr's x ids.  The lists are in training order, not ascending, so csr_check does not
+    apply; a minimum and a maximum on the device are enough."""
+    _require_gpu()
+    if len(yr) != 3 or yr[0].dtype != torch.int64 or yr[1].dtype != torch.int32 or yr[2].dtype != torch.float64:
+        raise ValueError("yr must be (int64 ptr, int32 x, fp64 r)")
+    ptr_, xs, rs = yr
+    n = xs.numel()
+    if ptr_.numel() < 2 or rs.numel() != n:
+        raise ValueError("yr: %d ptr entries, %d x, %d r" % (ptr_.numel(), n, rs.numel()))
+    if int(ptr_[0].item()) != 0 or int(ptr_[-1].item()) != n or bool((ptr_[1:] < ptr_[:-1]).any().item()):
+        raise ValueError("yr: malformed lists: ptr is not monotone from 0 to %d" % n)
+    if n and (int(xs.min().item()) < 0 or int(xs.max().item()) >= int(n_x)):
+        raise ValueError("yr: malformed lists: an x outside [0, %d)" % n_x)
+
+
+def estimate_batch_centered(sim, yr, qx, qy, k, min_k, centering, check=True):
+    """estimate_batch under a Centering (n2v_eccknn_estimate_centered): the same neighbours, centred sums.  Too few
+    neighbours is not impossible here (the estimate is the base alone); under "baseline" nothing is.  yr is checked first
+    (yr_check): a malformed list is a ValueError, not a launch.  check False: the caller has run yr_check on these lists."""
+    _require_gpu()
+    k, min_k = int(k), int(min_k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
+    if min_k < 1:
+        raise ValueError("min_k %d < 1" % min_k)
+    n_q = qx.numel()
+    if n_q == 0 or qy.numel() != n_q:
+        raise ValueError("estimate: %d x and %d y queries: nothing to estimate" % (n_q, qy.numel()))
+    n_x, n_y = sim.shape[0], yr[0].numel() - 1
+    code, tx, sd, by = _centering_args(centering, n_x, n_y)
+    if check:
+        yr_check(yr, n_x)
+    dev = sim.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        est = torch.empty(n_q, dtype=torch.float64, device=dev)
+        actual_k = torch.empty(n_q, dtype=torch.int32, device=dev)
+        imp = torch.empty(n_q, dtype=torch.uint8, device=dev)
+        _lib.check(lib.n2v_eccknn_estimate_centered(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y,
+                                                    _lib.ptr(qx), _lib.ptr(qy), n_q, k, min_k, code,
+                                                    1 if centering.user_based else 0, float(centering.global_mean), tx, sd, by,
+                                                    _lib.ptr(est), _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
+    return est, actual_k, imp
+
+
 def predict(est, impossible, global_mean, rating_scale, r_true=None):
     """pred (device fp64), and the rmse (a Python float) when r_true is given."""
     _require_gpu()
@@ -450,6 +551,40 @@ def top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, own
                                        n_seen, _lib.ptr(owners), owners.numel(), k, min_k, float(global_mean),
                                        float(rating_scale[0]), float(rating_scale[1]), n, S, _lib.ptr(part_score),
                                        _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score), _lib.stream_ptr(dev)))
+    return items, score
+
+
+def top_n_centered(sim, yr, seen, k, min_k, rating_scale, n, centering, owners=None, segments=None, check=True):
+    """top_n under a Centering (n2v_eccknn_topn_centered): every prediction the bits of estimate_batch_centered + predict.
+    user_based and global_mean are the centering's.  Under "baseline" an unknown owner's items score global_mean + bi[i],
+    clipped, and so are ranked by it.  yr is checked first as estimate_batch_centered checks it."""
+    n, segments = topn_options(n, segments)
+    _require_gpu()
+    k, min_k = int(k), int(min_k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
+    if min_k < 1:
+        raise ValueError("min_k %d < 1" % min_k)
+    n_x, n_y = sim.shape[0], yr[0].numel() - 1
+    code, tx, sd, by = _centering_args(centering, n_x, n_y)
+    user_based = bool(centering.user_based)
+    n_users, n_items = (n_x, n_y) if user_based else (n_y, n_x)
+    if check:
+        yr_check(yr, n_x)
+    dev = sim.device
+    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
+    lib = _lib.load()
+    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
+    with torch.cuda.device(dev):
+        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, dev)
+        n_seen = seen[1].numel()
+        _lib.check(lib.n2v_eccknn_topn_centered(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y,
+                                                1 if user_based else 0, _lib.ptr(seen[0]),
+                                                _lib.ptr(seen[1]) if n_seen else None, n_seen, _lib.ptr(owners),
+                                                owners.numel(), k, min_k, float(centering.global_mean),
+                                                float(rating_scale[0]), float(rating_scale[1]), n, S, code, tx, sd, by,
+                                                _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score),
+                                                _lib.stream_ptr(dev)))
     return items, score
 
 
@@ -575,12 +710,14 @@ class _SymmetricKNN(TopN):
         i = torch.as_tensor(np.asarray(i)).to(device=self.sim.device, dtype=torch.int32).contiguous()
         return (u, i) if self.sim_options["user_based"] else (i, u)
 
+    def _estimate_batch(self, qx, qy):
+        return estimate_batch(self.sim, self.yr, qx, qy, self.k, self.min_k)
+
     def estimate(self, u, i):
         """(est, {'actual_k': n}) for inner ids u, i; PredictionImpossible as the reference raises it."""
         if not (self.trainset.knows_user(u) and self.trainset.knows_item(i)):
             raise PredictionImpossible("User and/or item is unkown.")
-        qx, qy = self._queries([u], [i])
-        est, ak, imp = estimate_batch(self.sim, self.yr, qx, qy, self.k, self.min_k)
+        est, ak, imp = self._estimate_batch(*self._queries([u], [i]))
         if int(imp.item()):
             raise PredictionImpossible("Not enough neighbors.")
         return float(est.item()), {"actual_k": int(ak.item())}
@@ -592,7 +729,7 @@ class _SymmetricKNN(TopN):
             raise ValueError("test: empty testset")
         ts = self.trainset
         qx, qy = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
-        est, ak, imp = estimate_batch(self.sim, self.yr, qx, qy, self.k, self.min_k)
+        est, ak, imp = self._estimate_batch(qx, qy)
         r_true = torch.as_tensor(np.array([t[2] for t in testset], dtype=np.float64)).to(self.sim.device)
         pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
         return pred, ak, imp, err
@@ -645,14 +782,21 @@ class KNNBasic(_SymmetricKNN):
             return _SymmetricKNN._similarity(self, dense_mask, xr, dw)
         kw = {"w": dw, "min_support": self.sim_options.get("min_support", 1)}
         if self.name == "pearson_baseline":
-            bu, bi = baselines(self.trainset, self.bsl_options, self.device)
-            self.bx, self.by = (bu, bi) if self.sim_options["user_based"] else (bi, bu)
+            self._bsl()
             kw.update(global_mean=self.trainset.global_mean, bx=self.bx, by=self.by, shrinkage=self.shrinkage)
         if dense_mask is not None:
             return similarity_pearson(dense_mask[0], dense_mask[1], self.name, **kw)
         return similarity_pearson_sparse(xr, self.n_y, self.name, **kw)
 
+    def _bsl(self):
+        """The ALS baselines of the trainset being fitted as (self.bx, self.by), computed once per fit."""
+        if self._bsl_of is not self.trainset:
+            bu, bi = baselines(self.trainset, self.bsl_options, self.device)
+            self.bx, self.by = (bu, bi) if self.sim_options["user_based"] else (bi, bu)
+            self._bsl_of = self.trainset
+
     def fit(self, trainset, weights=None):
+        self._bsl_of = None
         if weights is not None:
             w = self._weights(trainset, weights)
         elif self.name in _METHOD:                              # the old kernels take their weights as given: ones
@@ -660,3 +804,85 @@ class KNNBasic(_SymmetricKNN):
         else:
             w = None
         return self._fit(trainset, w)
+
+
+class _CenteredKNN(KNNBasic):
+    """What KNNWithMeans, KNNWithZScore and KNNBaseline share above KNNBasic: its constructor, similarities, forms, weights,
+    bsl_options and shrinkage; after the fit a Centering (_tables), and estimate / test / rmse / top-N through the centred
+    kernels (_estimate_batch, _top_n).  The rules are surprise 1.0.6's, restated from memory (tests/knn_centered_reference.py is the definition; parity
+    with surprise itself is unpinned): the neighbours of KNNBasic, each rating centred before it is weighted, and too few
+    neighbours leave the base estimate instead of making the prediction impossible."""
+    MODE = None
+
+    def fit(self, trainset, weights=None):
+        KNNBasic.fit(self, trainset, weights)
+        yr_check(self.yr, self.n_x)                             # once per fit: the kernels index their tables with yr's ids
+        self.centering = self._tables()
+        return self
+
+    def _x_rows(self):
+        """The rating lists of the x side on the device, (ptr, r), each in training order."""
+        ts = self.trainset
+        xr = ts.ur if self.sim_options["user_based"] else ts.ir
+        dev = torch.device(self.device)
+        return (torch.as_tensor(np.ascontiguousarray(xr[0])).to(device=dev, dtype=torch.int64),
+                torch.as_tensor(np.ascontiguousarray(xr[2])).to(device=dev, dtype=torch.float64))
+
+    def _estimate_batch(self, qx, qy):
+        return estimate_batch_centered(self.sim, self.yr, qx, qy, self.k, self.min_k, self.centering, check=False)
+
+    def estimate(self, u, i):
+        """(est, {'actual_k': n}) for inner ids u, i.  PredictionImpossible only for an unknown user or item."""
+        if not (self.trainset.knows_user(u) and self.trainset.knows_item(i)):
+            raise PredictionImpossible("User and/or item is unkown.")
+        est, ak, _ = self._estimate_batch(*self._queries([u], [i]))
+        return float(est.item()), {"actual_k": int(ak.item())}
+
+    def _top_n(self, owners, n, segments):
+        return top_n_centered(self.sim, self.yr, self._seen(), self.k, self.min_k, self.trainset.rating_scale, n,
+                              self.centering, owners, segments, check=False)
+
+
+class KNNWithMeans(_CenteredKNN):
+    """surprise's KNNWithMeans: est = mu[x] + sum sim * (r - mu[x2]) / sum sim, mu the mean of a row's ratings summed in
+    training order (numpy's pairwise sum above 8 elements is a documented deviation)."""
+    MODE = "means"
+
+    def _tables(self):
+        ptr_, r = self._x_rows()
+        self.means, _ = row_moments(ptr_, r)
+        return Centering(self.MODE, self.sim_options["user_based"], self.trainset.global_mean, self.means, None, None)
+
+
+class KNNWithZScore(_CenteredKNN):
+    """surprise's KNNWithZScore: est = mu[x] + sd[x] * sum sim * ((r - mu[x2]) / sd[x2]) / sum sim.  A row whose sigma is 0.0
+    takes the sigma of all ratings; where that is 0.0 too (every rating equal) the NaN that follows is kept, and predict
+    turns it into the upper end of the scale."""
+    MODE = "zscore"
+
+    def _tables(self):
+        ptr_, r = self._x_rows()
+        dev = r.device
+        all_r = torch.as_tensor(np.ascontiguousarray(self.trainset.r)).to(device=dev, dtype=torch.float64)
+        one_row = torch.tensor([0, all_r.numel()], dtype=torch.int64, device=dev)
+        self.overall_sigma = float(row_moments(one_row, all_r)[1].item())
+        self.means, self.sigmas = row_moments(ptr_, r, zero_sigma=self.overall_sigma)
+        return Centering(self.MODE, self.sim_options["user_based"], self.trainset.global_mean, self.means, self.sigmas, None)
+
+
+class KNNBaseline(_CenteredKNN):
+    """surprise's KNNBaseline: est = b_ui + sum sim * (r - b_vi) / sum sim with the ALS baselines of bsl_options, computed
+    once per fit; -sim pearson_baseline reads the same pair.  Nothing is impossible: an unknown user drops bu, an unknown
+    item bi, and estimate never raises.  So an unknown owner's top-N list is not a constant: it is the items ranked by the
+    clipped global_mean + bi[i]."""
+    MODE = "baseline"
+
+    def _tables(self):
+        self._bsl()
+        return Centering(self.MODE, self.sim_options["user_based"], self.trainset.global_mean, self.bx, None, self.by)
+
+    def estimate(self, u, i):
+        """(est, {'actual_k': n}) for inner ids u, i, anything else being an unknown id.  Never raises."""
+        ts = self.trainset
+        est, ak, _ = self._estimate_batch(*self._queries([u if ts.knows_user(u) else -1], [i if ts.knows_item(i) else -1]))
+        return float(est.item()), {"actual_k": int(ak.item())}

@@ -4,6 +4,7 @@ kernels compute is the business of tests/test_gpu_eccknn.py.
     python tools/eccknn_probe.py [--users 6040 --items 3706 --ratings 1000000 --queries 200000 --k 20 --repeats 7]
                                  [--form dense|sparse|both] [--shape ml1m|30music-users]
                                  [--sim cosine|msd|pearson|pearson_baseline] [--baselines]
+                                 [--algo knn|knnmeans|knnzscore|knnbaseline]
 
 Prints one JSON line: medians over `repeats` timed runs after two warm-up runs, each run bracketed by device events;
 pair-y updates per second of the similarity kernel (every pair of the upper triangle of 64x64 tiles visits every y, the
@@ -18,6 +19,9 @@ published MI355X figure; an update is counted as the 5 flops of the cosine form)
 --sim     cosine / msd (EccenKNN's kernels) or pearson / pearson_baseline (KNNBasic's, with the same weights; the second
           one with the trainset's ALS baselines, computed once outside the timed region).  The numpy restatement is timed
           for cosine / msd only.  ml1m shape only for the Pearson names.
+--algo    knn (the default) times the plain estimate kernel only; knnmeans / knnzscore / knnbaseline also time the centred
+          one (KNNWithMeans / KNNWithZScore / KNNBaseline) on the same similarity, lists and queries, the two alternating run
+          by run: `estimate_ms` and `estimate_centered_ms`, and `tables_ms`, the row moments or ALS baselines of the mode.
 --baselines  also time eccknn.baselines (10 ALS epochs, both sides, uploads included) as `baselines_ms`.
 --shape   ml1m (the default; --users / --items / --ratings apply) or 30music-users: 4e4 users x 5e6 items, 3e7 ratings,
           power-law items and users, de-duplicated on (user, item).  Past the dense limit, so sparse only; the estimate
@@ -136,6 +140,39 @@ def timed(fn, repeats, warmup=2):
     return statistics.median(out), min(out), max(out)
 
 
+def timed_pair(f, g, repeats, warmup=2):
+    """timed() of two calls that alternate run by run."""
+    import torch
+    out = ([], [])
+    for n in range(warmup + repeats):
+        for which, fn in enumerate((f, g)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            if n >= warmup:
+                out[which].append(a.elapsed_time(b))
+    return tuple((statistics.median(v), min(v), max(v)) for v in out)
+
+
+def centering_tables(algo, ts, dev):
+    """The user-based Centering of one centred algorithm, from the trainset: uploads, row moments or ALS baselines."""
+    import torch
+    from n2v_hip import eccknn
+    if algo == "knnbaseline":
+        bu, bi = eccknn.baselines(ts, device=dev)
+        return eccknn.Centering("baseline", True, ts.global_mean, bu, None, bi)
+    to = lambda v, dt: torch.as_tensor(np.ascontiguousarray(v)).to(device=dev, dtype=dt)
+    ptr, r = to(ts.ur[0], torch.int64), to(ts.ur[2], torch.float64)
+    if algo == "knnmeans":
+        return eccknn.Centering("means", True, ts.global_mean, eccknn.row_moments(ptr, r)[0], None, None)
+    all_r = to(ts.r, torch.float64)
+    overall = float(eccknn.row_moments(to([0, len(ts.r)], torch.int64), all_r)[1].item())
+    mu, sd = eccknn.row_moments(ptr, r, zero_sigma=overall)
+    return eccknn.Centering("zscore", True, ts.global_mean, mu, sd, None)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--users", type=int, default=6040)
@@ -147,6 +184,7 @@ def main(argv=None):
     ap.add_argument("--numpy-subset", type=int, default=300)
     ap.add_argument("--sim", default="cosine", choices=["cosine", "msd", "pearson", "pearson_baseline"])
     ap.add_argument("--baselines", action="store_true")
+    ap.add_argument("--algo", default="knn", choices=["knn", "knnmeans", "knnzscore", "knnbaseline"])
     ap.add_argument("--form", default="dense", choices=["dense", "sparse", "both"])
     ap.add_argument("--shape", default="ml1m", choices=["ml1m", "30music-users"])
     a = ap.parse_args(argv)
@@ -205,7 +243,17 @@ def main(argv=None):
     yr = tuple(to(v, dt) for v, dt in zip(ts.ir, (torch.int64, torch.int32, torch.float64)))
     rs = np.random.RandomState(2)
     qx, qy = to(rs.randint(0, n_x, a.queries), torch.int32), to(rs.randint(0, n_y, a.queries), torch.int32)
-    res["estimate_ms"] = timed(lambda: eccknn.estimate_batch(sim, yr, qx, qy, a.k, 1), a.repeats)
+    if a.algo == "knn":
+        res["estimate_ms"] = timed(lambda: eccknn.estimate_batch(sim, yr, qx, qy, a.k, 1), a.repeats)
+    else:
+        res["algo"] = a.algo
+        res["tables_ms"] = timed(lambda: centering_tables(a.algo, ts, dev), a.repeats)
+        c = centering_tables(a.algo, ts, dev)
+        eccknn.yr_check(yr, n_x)
+        res["estimate_ms"], res["estimate_centered_ms"] = timed_pair(
+            lambda: eccknn.estimate_batch(sim, yr, qx, qy, a.k, 1),
+            lambda: eccknn.estimate_batch_centered(sim, yr, qx, qy, a.k, 1, c, check=False), a.repeats)
+        res["centered_over_plain"] = res["estimate_centered_ms"][0] / res["estimate_ms"][0]
     est, _, imp = eccknn.estimate_batch(sim, yr, qx, qy, a.k, 1)
     rt = to(rs.randint(1, 11, a.queries) * 0.5, torch.float64)
     res["predict_rmse_ms"] = timed(lambda: eccknn.predict(est, imp, ts.global_mean, ts.rating_scale, rt), a.repeats)
