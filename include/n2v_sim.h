@@ -430,6 +430,64 @@ int n2v_eccsplit_pairs(const int64_t* key_sorted, const int64_t* perm, int64_t n
 int n2v_eccsplit_fill(const int64_t* ekey_sorted, const int64_t* perm, int64_t nnz, const double* ew, int64_t n_nodes,
                       int64_t* row_ptr, int32_t* col, double* w, void* stream);
 
+/* ---- Eccentricity consistency: two-period join, n x n transition table, per-user ie profile, feature rows
+ * (csrc/n2v_ecccons.hip) -----
+ * Replaces the joins and group-bys of src/utils.py:163-226 (septile_for_plot) and :326-379 (calculate_uie_dist,
+ * calculate_uvec, make_data).  Integers are counted exactly and fp64 values are moved by their bytes; the only rounded
+ * operations are the final divisions and, in the weighted profile, sums whose order is stated below.  Workgroups meet
+ * only through 64-bit integer atomic adds (which commute) and at launch boundaries: every result is the same on every
+ * run.  Every size is at most 2^31 - 1 and a bin count at most N2V_ECCCONS_MAX_BINS; beyond them N2V_ERR_INVALID.  The
+ * kernels skip an index outside its range; the check functions below tell the caller that there was one.  Compactions
+ * are the stable one of n2v_eccsplit_select: scratch is int64[n2v_eccsplit_scratch(n)].                            */
+#define N2V_ECCCONS_MAX_BINS 256
+#define N2V_ECCCONS_CELLS 4096                       /* int32 counters of the crosstab's LDS histogram: 16 KiB      */
+#define N2V_ECCCONS_CHUNK 16384                      /* elements per workgroup of the crosstab                      */
+#define N2V_ECCCONS_BAD_RANGE 1                      /* status bits of the check functions                          */
+#define N2V_ECCCONS_BAD_PTR 2
+
+/* *status |= N2V_ECCCONS_BAD_RANGE if some a[k], k < n, lies outside lo .. hi.  status: one int32 device word.     */
+int n2v_ecccons_check_i32(const int32_t* a, int64_t n, int32_t lo, int32_t hi, int32_t* status, void* stream);
+int n2v_ecccons_check_i64(const int64_t* a, int64_t n, int64_t lo, int64_t hi, int32_t* status, void* stream);
+/* *status |= N2V_ECCCONS_BAD_PTR unless ptr[0] == 0, ptr[n_seg] == total and ptr never descends.                   */
+int n2v_ecccons_check_ptr(const int64_t* ptr, int64_t n_seg, int64_t total, int32_t* status, void* stream);
+
+/* Entities e < n of one index space with the values v1 / v2 and the row counts c1 / c2 of two periods (a count of 0:
+ * absent).  ids[0 .. *count): the e with c1[e] > min_count and c2[e] > min_count (and both > 0), ascending; o1 / o2 their
+ * values.  ids / o1 / o2 hold n words and are untouched past *count.                                               */
+int n2v_ecccons_join(const double* v1, const double* v2, const int64_t* c1, const int64_t* c2, int64_t n, int64_t min_count,
+                     int64_t* scratch, int64_t* ids, double* o1, double* o2, int64_t* count, void* stream);
+
+/* bins1 / bins2: int32[m] in 1 .. n_bins.  count[a - 1][b - 1] = elements with bins1 == a and bins2 == b (int64[n][n]),
+ * count_sum[a - 1] = the sum of row a - 1, ratio = count * 1.0 / count_sum (fp64[n][n]; the row of a bin that bins1
+ * never names is NaN).  A histogram of at most N2V_ECCCONS_CELLS int32 counters per workgroup in LDS: all n x n cells
+ * when n <= 64, otherwise stripes of N2V_ECCCONS_CELLS / n values of bins1, one sweep of the workgroup's
+ * N2V_ECCCONS_CHUNK elements per stripe.  m may be 0.                                                              */
+int n2v_ecccons_crosstab(const int32_t* bins1, const int32_t* bins2, int64_t m, int32_t n_bins, int64_t* count,
+                         int64_t* count_sum, double* ratio, void* stream);
+
+/* The rows of user u are perm[user_ptr[u] .. user_ptr[u + 1]) (file order inside a user: the stable sort by user).
+ * item_bin[item]: 1 .. n_bins, or 0 for an item without a bin, whose rows are skipped.  One wavefront per user.
+ *   weighted == 0:  profile[u][b - 1] = (rows of u in bin b) / (rows of u in any bin), integers counted exactly and
+ *                   divided in fp64
+ *   weighted != 0:  profile[u][b - 1] = (sum of feedback over those rows) / (sum of feedback over the rows of u in
+ *                   any bin), each sum from +0.0 in the order of the user's rows
+ * A user without a row in any bin gets 0 / 0 = NaN.  profile: fp64[n_users][n_bins].                                */
+int n2v_ecccons_profile(const int64_t* user_ptr, const int64_t* perm, int64_t n_users, const int64_t* item,
+                        const double* feedback, int64_t n_rows, const int32_t* item_bin, int64_t n_items, int32_t n_bins,
+                        int32_t weighted, double* profile, void* stream);
+
+/* rows[0 .. *count): the rows k whose item has a vector (vec_slot[item[k]] in 0 .. n_vec - 1; vec_slot NULL: every row),
+ * ascending; y[slot] = feedback[k].  rows / y hold n_rows words.                                                    */
+int n2v_ecccons_feature_rows(const int64_t* item, const double* feedback, int64_t n_rows, int64_t n_items,
+                             const int32_t* vec_slot, int64_t n_vec, int64_t* scratch, int64_t* rows, double* y,
+                             int64_t* count, void* stream);
+/* X[t] = profile[user[k]] ++ vec[vec_slot[item[k]]] widened to fp64 (row length n_bins + d), or, with vec NULL,
+ * profile[user[k]] ++ [item_value[item[k]]] (row length n_bins + 1), k = rows[t], t < n_kept.  One wavefront per row;
+ * 16-byte accesses when n_bins, the row length and the pointers allow.                                             */
+int n2v_ecccons_features(const int64_t* rows, int64_t n_kept, const int64_t* user, const int64_t* item, int64_t n_rows,
+                         int64_t n_users, int64_t n_items, const double* profile, int32_t n_bins, const int32_t* vec_slot,
+                         const float* vec, int64_t n_vec, int32_t d, const double* item_value, double* X, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,11 +16,12 @@
 //   keys       dense_u * N + dense_i of every selected row.
 //   fill       sorted entries -> row_ptr / col / w.
 #include "n2v_common.h"
+#include "n2v_compact.h"
 #include "n2v_sim.h"
 
 namespace {
 
-constexpr int TILE = N2V_ECCSPLIT_TILE;                  // elements per workgroup of the compaction passes
+constexpr int TILE = n2v::COMPACT_TILE;                  // elements per workgroup of the compaction passes
 constexpr long long NONE = 0x7fffffffffffffffll;         // N2V_ECCSPLIT_NONE: a node no selected row names
 constexpr int64_t LIMIT = 0x7fffffff;                    // every size is below 2^31
 
@@ -47,70 +48,9 @@ __global__ void __launch_bounds__(256) mark_kernel(const int64_t* __restrict__ o
     bin[u] = (int32_t)b;
 }
 
-// ---- the stable compaction --------------------------------------------------------------------------------------------
-// P: test(k) keeps element k; emit(k, slot) writes a kept element; skip(k) sees a dropped one.
+// ---- the stable compaction: n2v_compact.h ------------------------------------------------------------------------------
 
-template <class P>
-__global__ void __launch_bounds__(256) compact_count_kernel(P p, int64_t n, int64_t* __restrict__ tile_cnt) {
-    __shared__ int wave_cnt[4];
-    const int t = threadIdx.x;
-    int c = 0;
-    for (int it = 0; it < TILE / 256; ++it) {
-        const int64_t k = (int64_t)blockIdx.x * TILE + it * 256 + t;
-        c += __popcll(__ballot(k < n && p.test(k)));                     // the wavefront's count, in every lane
-    }
-    if ((t & 63) == 0) wave_cnt[t >> 6] = c;
-    __syncthreads();
-    if (t == 0) tile_cnt[blockIdx.x] = wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-}
-
-// exclusive scan of the tile counts in place; *count = their sum
-__global__ void __launch_bounds__(256) compact_scan_kernel(int64_t* __restrict__ tile_cnt, int64_t n_tiles, int64_t* __restrict__ count) {
-    __shared__ int64_t part[256];
-    const int t = threadIdx.x;
-    const int64_t per = (n_tiles + 255) / 256;
-    const int64_t lo = t * per < n_tiles ? t * per : n_tiles, hi = lo + per < n_tiles ? lo + per : n_tiles;
-    int64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += tile_cnt[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < 256; ++i) { const int64_t v = part[i]; part[i] = run; run += v; }
-        *count = run;
-    }
-    __syncthreads();
-    int64_t run = part[t];
-    for (int64_t i = lo; i < hi; ++i) { const int64_t v = tile_cnt[i]; tile_cnt[i] = run; run += v; }
-}
-
-template <class P>
-__global__ void __launch_bounds__(256) compact_scatter_kernel(P p, int64_t n, const int64_t* __restrict__ tile_off) {
-    __shared__ int wave_cnt[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int64_t base = tile_off[blockIdx.x];                                 // kept elements before this tile
-    for (int it = 0; it < TILE / 256; ++it) {
-        const int64_t k = (int64_t)blockIdx.x * TILE + it * 256 + t;
-        const bool keep = k < n && p.test(k);
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) wave_cnt[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, total = 0;
-        for (int w = 0; w < 4; ++w) { before += w < wave ? wave_cnt[w] : 0; total += wave_cnt[w]; }
-        __syncthreads();
-        if (keep) p.emit(k, base + before + __popcll(b & ((1ull << lane) - 1)));
-        else if (k < n) p.skip(k);
-        base += total;
-    }
-}
-
-template <class P>
-void compact(const P& p, int64_t n, int64_t* scratch, int64_t* count, hipStream_t s) {
-    const int64_t n_tiles = (n + TILE - 1) / TILE;
-    compact_count_kernel<P><<<(unsigned)n_tiles, 256, 0, s>>>(p, n, scratch);
-    compact_scan_kernel<<<1, 256, 0, s>>>(scratch, n_tiles, count);
-    compact_scatter_kernel<P><<<(unsigned)n_tiles, 256, 0, s>>>(p, n, scratch);
-}
+using n2v::compact;
 
 struct SelectP {
     const int64_t* user; const int32_t* bin; int64_t n_users; int32_t which; int64_t* rows;

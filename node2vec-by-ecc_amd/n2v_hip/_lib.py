@@ -162,6 +162,15 @@ SIGNATURES = {
     "n2v_eccsplit_keys": (C.c_int, [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i64, _ptr, _ptr]),
     "n2v_eccsplit_pairs": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_eccsplit_fill": (C.c_int, [_ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_ecccons_check_i32": (C.c_int, [_ptr, _i64, _i32, _i32, _ptr, _ptr]),
+    "n2v_ecccons_check_i64": (C.c_int, [_ptr, _i64, _i64, _i64, _ptr, _ptr]),
+    "n2v_ecccons_check_ptr": (C.c_int, [_ptr, _i64, _i64, _ptr, _ptr]),
+    "n2v_ecccons_join": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_ecccons_crosstab": (C.c_int, [_ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_ecccons_profile": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i32, _i32, _ptr, _ptr]),
+    "n2v_ecccons_feature_rows": (C.c_int, [_ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_ecccons_features": (C.c_int, [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr,
+                                       _ptr]),
 }
 
 _lib = None
