@@ -284,6 +284,42 @@ int n2v_svd_estimate(const double* bu, const double* bi, const double* pu, const
                      int64_t n_items, int32_t n_factors, double mu, int32_t biased, const int32_t* q_u, const int32_t* q_i,
                      int64_t n_q, double* est, uint8_t* impossible, void* stream);
 
+/* ---- Non-negative matrix factorisation: surprise's NMF in surprise's own order (csrc/n2v_nmf.hip) ---------------------
+ * surprise 1.0.6's NMF with biased = False (Luo et al. 2014).  surprise is not a dependency: the update below is its
+ * arithmetic restated from memory, parity with surprise itself is UNPINNED, and tests/nmf_reference.py is the definition
+ * the kernels equal bit for bit.  The model is the unbiased one above (est = dot, the same dot), so n2v_svd_estimate and
+ * n2v_svd_topn serve it with biased = 0.  Everything is fp64 without fused multiply-add, as written, left to right.
+ * One epoch reads pu and qi as they were when it began and writes pu_out and qi_out.  For every user u, over its
+ * ratings (i, r) in the order of the user-major list, num and den starting from +0.0 per factor:
+ *   est = dot(qi[i], pu[u]);  num[f] = num[f] + qi[i][f] * r;  den[f] = den[f] + qi[i][f] * est
+ * and after the list, with len its length as a double:
+ *   den[f] = den[f] + (len * reg_pu) * pu[u][f];  pu_out[u][f] = pu[u][f] * (num[f] / den[f])
+ * For every item i the same with the roles swapped (rows pu[u] of its raters, reg_qi, qi_out), over the item-major list,
+ * which holds each item's raters ascending in u: surprise's all_ratings() order.  There is no special case: a zero
+ * denominator gives the NaN or infinity of the arithmetic (an empty list: 0 / 0), and they propagate.  (A NaN's sign and
+ * payload are not part of the contract.)
+ * A list is (ptr int64[n_rows + 1], other int32[n], r fp64[n]), row k being [ptr[k], ptr[k + 1]).  n2v_nmf_lists_check
+ * (integers only; scratch: int32[n_users + n_items], cleared by the call; *status: int32, device, cleared by the caller)
+ * names what is wrong with the pair of lists by bits of *status.  n2v_nmf_epoch is only defined on lists that pass it:
+ * it clamps every row range to [0, n] and skips an entry whose id is out of range, so a malformed list is no
+ * out-of-bounds access.                                                                                                */
+#define N2V_NMF_BAD_PTR 1       /* a ptr does not start at 0, is not monotone, or leaves [0, n]                       */
+#define N2V_NMF_BAD_END 2       /* a ptr does not end at n                                                             */
+#define N2V_NMF_BAD_ID 4        /* an item id outside [0, n_items) or a user id outside [0, n_users)                   */
+#define N2V_NMF_UNSORTED 8      /* a row of the item-major list not strictly ascending in u                            */
+#define N2V_NMF_BAD_COUNT 16    /* an id occurs in one list another number of times than its row of the other is long  */
+int32_t n2v_nmf_depth(void);         /* rows of the other table a wavefront fetches ahead of the entry it works on     */
+int n2v_nmf_lists_check(const int64_t* u_ptr, const int32_t* u_i, const int64_t* i_ptr, const int32_t* i_u, int64_t n_users,
+                        int64_t n_items, int64_t n, int32_t* scratch, int32_t* status, void* stream);
+/* One epoch, one launch: one wavefront per user and per item.  u_order int32[n_users] / i_order int32[n_items]: the row
+ * the k-th wavefront of a side takes (a permutation; longest lists first is the fast one; NULL: the identity); it changes
+ * no bit.  pu, qi: the tables read; pu_out, qi_out: the tables written, each disjoint from both inputs and from the other
+ * output, else N2V_ERR_INVALID before any launch.  1 <= n_factors <= 256, n >= 1.                                      */
+int n2v_nmf_epoch(const int64_t* u_ptr, const int32_t* u_i, const double* u_r, const int64_t* i_ptr, const int32_t* i_u,
+                  const double* i_r, const int32_t* u_order, const int32_t* i_order, int64_t n_users, int64_t n_items,
+                  int64_t n, int32_t n_factors, double reg_pu, double reg_qi, const double* pu, const double* qi,
+                  double* pu_out, double* qi_out, void* stream);
+
 /* ---- Top-N lists of the rating predictors (csrc/n2v_eccknn.hip, n2v_svd.hip, n2v_topn.h) ------------------------------
  * What src/recsys.py sketches ("Get the top songs" per user) and surprise's recipe algo.test(build_anti_testset()) +
  * get_top_n compute, without storing the n_users x n_items predictions.  tests/topn_reference.py is the definition.

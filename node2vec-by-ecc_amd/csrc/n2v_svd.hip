@@ -14,17 +14,22 @@
 //   estimate_kernel<NS>  one wavefront per query, the same lane_dot.
 //   svd_topn_kernel<NS>  one wavefront per (owner, segment of the items): the best-N unseen items of the owner through
 //                        the same lane_dot and estimate_value, without storing the owners x items predictions.
+// load_row / store_row / lane_dot are shared with the NMF kernels (n2v_mf_device.h).
 // fp64 throughout; -ffp-contract=off (csrc/Makefile) keeps every multiply and add separately rounded.
 #include "n2v_common.h"
+#include "n2v_mf_device.h"
 #include "n2v_sim.h"
 #include "n2v_topn.h"
 
 namespace {
 
-constexpr int MAX_FACTORS = 256;
+constexpr int MAX_FACTORS = n2v::MF_MAX_FACTORS;
 constexpr int MAX_STRATA = 32768;
 
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
+using n2v::clamp64;
+using n2v::lane_dot;                                              // n2v_mf_device.h: the rows and the dot
+using n2v::load_row;
+using n2v::store_row;
 
 // ---- the block list ---------------------------------------------------------------------------------------------------
 
@@ -52,33 +57,6 @@ __global__ void __launch_bounds__(256) blocks_check_kernel(const int64_t* __rest
         }
     }
     if (bits) atomicOr(status, bits);
-}
-
-// ---- the rows and the dot ---------------------------------------------------------------------------------------------
-
-template <int NS>
-__device__ __forceinline__ void load_row(const double* row, int nf, int lane, double (&x)[NS]) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k) x[k] = lane + 64 * k < nf ? row[lane + 64 * k] : 0.0;
-}
-
-template <int NS>
-__device__ __forceinline__ void store_row(double* row, int nf, int lane, const double (&x)[NS]) {
-#pragma unroll
-    for (int k = 0; k < NS; ++k)
-        if (lane + 64 * k < nf) row[lane + 64 * k] = x[k];
-}
-
-// The dot of the definition; every lane returns the same value.
-template <int NS>
-__device__ __forceinline__ double lane_dot(const double (&q)[NS], const double (&p)[NS], int nf, int lane) {
-    double v = 0.0;
-#pragma unroll
-    for (int k = 0; k < NS; ++k)
-        if (lane + 64 * k < nf) v = v + q[k] * p[k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return v;
 }
 
 // ---- one stratum ------------------------------------------------------------------------------------------------------
@@ -258,14 +236,6 @@ __global__ void __launch_bounds__(64) svd_topn_kernel(TopnArgs a) {
     top.store(a.part_score + base, a.part_pos + base, lane);
 }
 
-#define N2V_SVD_DISPATCH(KERNEL, nf, ...)                                     \
-    do {                                                                      \
-        if ((nf) <= 64) KERNEL<1> __VA_ARGS__;                                \
-        else if ((nf) <= 128) KERNEL<2> __VA_ARGS__;                          \
-        else if ((nf) <= 192) KERNEL<3> __VA_ARGS__;                          \
-        else KERNEL<4> __VA_ARGS__;                                           \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -303,7 +273,7 @@ int n2v_svd_epoch(const int64_t* blk_ptr, const int32_t* blk_u, const int32_t* b
                 lr_bu, lr_bi, lr_pu, lr_qi, reg_bu, reg_bi, reg_pu, reg_qi, bu, bi, pu, qi};
     for (int64_t s = 0; s < n_strata; ++s) {                      // stream order is the barrier between strata
         a.s = s;
-        N2V_SVD_DISPATCH(epoch_kernel, n_factors, <<<(unsigned)n_strata, 64, 0, (hipStream_t)stream>>>(a));
+        N2V_MF_DISPATCH(epoch_kernel, n_factors, <<<(unsigned)n_strata, 64, 0, (hipStream_t)stream>>>(a));
     }
     return n2v::check_launch("svd_epoch");
 }
@@ -319,7 +289,7 @@ int n2v_svd_estimate(const double* bu, const double* bi, const double* pu, const
     if (!pu || !qi || !q_u || !q_i || !est || !impossible || (biased && (!bu || !bi)))
         return n2v::fail(N2V_ERR_INVALID, "svd_estimate: null pointer");
     EstArgs a{Model{bu, bi, pu, qi, n_users, n_items, n_factors, biased ? 1 : 0, mu}, n_q, q_u, q_i, est, impossible};
-    N2V_SVD_DISPATCH(estimate_kernel, n_factors, <<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a));
+    N2V_MF_DISPATCH(estimate_kernel, n_factors, <<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a));
     return n2v::check_launch("svd_estimate");
 }
 
@@ -337,7 +307,7 @@ int n2v_svd_topn(const double* bu, const double* bi, const double* pu, const dou
     const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
     TopnArgs a{Model{bu, bi, pu, qi, n_users, n_items, n_factors, biased ? 1 : 0, mu}, n2v::Seen{seen_ptr, seen_i, n_users, n_seen},
                owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
-    N2V_SVD_DISPATCH(svd_topn_kernel, n_factors, <<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(a));
+    N2V_MF_DISPATCH(svd_topn_kernel, n_factors, <<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(a));
     if (const int rc = n2v::check_launch("svd_topn")) return rc;
     return n2v::topn_merge("svd_topn (merge)", part_score, part_pos, n_owners, S, top_n, items, score, (hipStream_t)stream);
 }

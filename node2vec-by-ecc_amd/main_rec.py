@@ -7,7 +7,8 @@ plain k-NN (surprise's KNNBasic) it is compared against.
                        [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
     python main_rec.py -input ratings.csv -algo mf [-factors 100] [-epochs 20] [-lr 0.005] [-reg 0.02] [-strata N|auto]
                        [-unbiased] [-test-ratio 0.2] [-seed 0] [-cv N]
-    either form:       [-topn N [-threshold T] [-save-recs FILE]]
+    python main_rec.py -input ratings.csv -algo nmf [-factors 15] [-epochs 50] [-reg 0.06] [-test-ratio 0.2] [-seed 0] [-cv N]
+    every form:        [-topn N [-threshold T] [-save-recs FILE]]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
 -algo     eccen (the default) or knn: KNNBasic, which also takes -sim pearson and pearson_baseline (surprise's functions,
@@ -23,6 +24,10 @@ plain k-NN (surprise's KNNBasic) it is compared against.
           to its row mean, to its row mean in units of its row sigma, or to the ALS baseline of the pair, and too few
           neighbours leave the base estimate instead of the training mean.  They take every flag -algo knn takes, -weights /
           -mode included (the eccentricity-weighted, centred k-NN), and none of the mf flags.
+          nmf: surprise's NMF (restated; parity with surprise is unpinned), the non-negative factor model with the
+          multiplicative update, trained on the device in surprise's own order of the ratings (n2v_hip.nmf): -factors,
+          -epochs and -reg are surprise's n_factors, n_epochs and reg_pu = reg_qi, and -seed also seeds the factors.  It
+          has no biases, no learning rate and no schedule: it takes none of -lr, -strata, -unbiased and the k-NN flags.
           svd itself is not built: surprise's order of the ratings is sequential, and -algo mf follows it only with -strata 1.
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
 -mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
@@ -96,17 +101,19 @@ def parse_args(argv=None):
     if a.algo == "svd":
         p.error("-algo svd is not built: surprise's SVD applies the ratings in one sequential order.  -algo mf is the same "
                 "model and update under a deterministic stratified order (equal to surprise's only with -strata 1)")
-    if a.algo not in ("eccen", "mf") + KNN_ALGOS:
-        p.error("-algo %s: eccen, %s or mf" % (a.algo, ", ".join(KNN_ALGOS)))
+    if a.algo not in ("eccen", "mf", "nmf") + KNN_ALGOS:
+        p.error("-algo %s: eccen, %s, mf or nmf" % (a.algo, ", ".join(KNN_ALGOS)))
     knn_flags = (("-sim", a.sim), ("-k", a.k), ("-mink", a.mink), ("-weights", a.weights), ("-mode", a.mode),
                  ("-item-based", a.item_based or None), ("-form", a.form))
     mf_flags = (("-factors", a.factors), ("-epochs", a.epochs), ("-lr", a.lr), ("-reg", a.reg), ("-strata", a.strata),
                 ("-unbiased", a.unbiased or None))
-    for flag, v in (knn_flags if a.algo == "mf" else mf_flags):
+    sgd_flags = tuple(f for f in mf_flags if f[0] in ("-lr", "-strata", "-unbiased"))     # what mf has and nmf has not
+    for flag, v in {"mf": knn_flags, "nmf": knn_flags + sgd_flags}.get(a.algo, mf_flags):
         if v is not None:
             p.error("%s does not go with -algo %s" % (flag, a.algo))
-    for name, v in (("k", 40), ("mink", 1), ("sim", "cosine"), ("form", "auto"), ("factors", 100), ("epochs", 20),
-                    ("lr", 0.005), ("reg", 0.02), ("strata", "auto")):
+    factor_defaults = (("factors", 15), ("epochs", 50), ("reg", 0.06)) if a.algo == "nmf" else ()
+    for name, v in factor_defaults + (("k", 40), ("mink", 1), ("sim", "cosine"), ("form", "auto"), ("factors", 100), ("epochs", 20),
+                                      ("lr", 0.005), ("reg", 0.02), ("strata", "auto")):
         if getattr(a, name) is None:
             setattr(a, name, v)
     if a.strata != "auto":
@@ -118,6 +125,12 @@ def parse_args(argv=None):
         from n2v_hip import svd
         try:
             svd.SVD(n_factors=a.factors, n_epochs=a.epochs, lr_all=a.lr, reg_all=a.reg, n_strata=a.strata)
+        except ValueError as e:
+            p.error(str(e))
+    if a.algo == "nmf":
+        from n2v_hip import nmf
+        try:
+            nmf.NMF(n_factors=a.factors, n_epochs=a.epochs, reg_pu=a.reg, reg_qi=a.reg)
         except ValueError as e:
             p.error(str(e))
     if a.sim in ("pearson", "pearson_baseline") and a.algo not in KNN_ALGOS:
@@ -230,6 +243,11 @@ def fit_split(args, users, items, ratings, weights, train):
         from n2v_hip import svd
         algo = svd.SVD(n_factors=args.factors, n_epochs=args.epochs, biased=not args.unbiased, lr_all=args.lr,
                        reg_all=args.reg, random_state=args.seed, n_strata=args.strata, device=args.device)
+        return algo.fit(ts)
+    if args.algo == "nmf":
+        from n2v_hip import nmf
+        algo = nmf.NMF(n_factors=args.factors, n_epochs=args.epochs, reg_pu=args.reg, reg_qi=args.reg, random_state=args.seed,
+                       device=args.device)
         return algo.fit(ts)
     sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
     if args.algo in KNN_ALGOS:

@@ -138,6 +138,10 @@ SIGNATURES = {
     "n2v_svd_epoch": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _f64, _i32, _f64, _f64, _f64, _f64, _f64,
                                 _f64, _f64, _f64, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_svd_estimate": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _f64, _i32, _ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "n2v_nmf_depth": (C.c_int32, []),
+    "n2v_nmf_lists_check": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]),
+    "n2v_nmf_epoch": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i32, _f64, _f64, _ptr, _ptr,
+                                _ptr, _ptr, _ptr]),
     "n2v_topn_segments": (C.c_int32, [_i64, _i64]),
     "n2v_eccknn_topn": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _i32, _i32, _f64,
                                   _f64, _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
