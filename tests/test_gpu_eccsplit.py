@@ -75,16 +75,19 @@ def c_mark(ue, n, tie_rank=None):
     return out[:n_users]
 
 
-def c_select(user, bins, which):
+def c_select(user, bins, which, pad=0):
+    """pad: sentinel words kept behind the scratch the call is told about; they must come back untouched."""
     import torch
     L = _L(); lib = L.load()
     du, db = _dev(user, np.int64), _dev(bins, np.int32)
     n_rows = len(user)
-    scratch = _full(int(lib.n2v_eccsplit_scratch(n_rows)), ISENT, torch.int64)
+    n_scratch = int(lib.n2v_eccsplit_scratch(n_rows))
+    scratch = _full(n_scratch + pad, ISENT, torch.int64)
     rows, count = _full(n_rows, ISENT, torch.int64), _full(1, ISENT, torch.int64)
     L.check(lib.n2v_eccsplit_select(L.ptr(du), n_rows, L.ptr(db), len(bins), which, L.ptr(scratch), L.ptr(rows), L.ptr(count),
                                     L.stream_ptr(du.device)))
     c = int(count.item())
+    assert (scratch[n_scratch:] == ISENT).all()
     rows = rows.cpu().numpy()
     assert 0 <= c <= n_rows and (rows[c:] == ISENT).all()
     return rows[:c]
