@@ -358,6 +358,45 @@ int n2v_svd_topn(const double* bu, const double* bi, const double* pu, const dou
                  const int32_t* owners, int64_t n_owners, double global_mean, double lo, double hi, int32_t top_n,
                  int32_t segments, double* part_score, int32_t* part_pos, int32_t* items, double* score, void* stream);
 
+/* ---- SlopeOne: surprise's parameter-free item-deviation predictor (csrc/n2v_eccknn.hip, csrc/n2v_slopeone.hip) -------
+ * surprise 1.0.6's SlopeOne (Lemire and Maclachlan 2005), restated from memory of its source: parity with surprise itself
+ * is UNPINNED, and tests/slopeone_reference.py is the definition the kernels equal bit for bit (fp64, every operation
+ * below one rounding; a NaN's sign and payload are not part of the contract).  x = items, y = users.
+ * The table: for every pair of items i < j, over the users u who rated both, ascending in u,
+ *   freq[i][j] += 1;  acc[i][j] = acc[i][j] + (r[u][i] - r[u][j])                  (from 0 and +0.0)
+ *   dev[i][j] = acc[i][j] / (double)freq[i][j]      (freq 0: 0.0 / 0 = NaN; n2v_slopeone_estimate never reads it)
+ *   dev[j][i] = -dev[i][j]                          (the stored value with its sign bit flipped, a zero included)
+ *   dev[i][i] = 0.0;  freq[j][i] = freq[i][j];  freq[i][i] = the raters of i
+ * dev: fp64[n_items][n_items]; freq: int32[n_items][n_items]; acc (may be NULL): fp64[n_items][n_items], the raw sums of
+ * surprise's loop over every ordered pair, acc[j][i] being the sum of (r[u][j] - r[u][i]): -acc[i][j], and +0.0 where
+ * that is a zero.  They are one more method of the two tile kernels behind n2v_eccknn_sim / n2v_eccknn_sim_sparse, whose
+ * inputs (dense, mask of n2v_eccknn_densify; the x-major CSR), frame, clamping and error rules they share; there is no
+ * w and no min_support.  n_items * n_items <= 2^31 (16 GiB of dev and 8 GiB of freq at the limit), and for the dense
+ * form n_items * n_users <= n2v_eccknn_max_dense().                                                                    */
+int n2v_slopeone_dev(const double* dense, const uint8_t* mask, int64_t n_items, int64_t n_users, double* dev, int32_t* freq,
+                     double* acc, void* stream);
+int n2v_slopeone_dev_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_items, int64_t n_users,
+                            int64_t n, double* dev, int32_t* freq, double* acc, void* stream);
+/* One wavefront per query (q_u[q], q_i[q]).  ur_ptr: int64[n_users + 1], ur_i: int32[n] — the items every user rated, in
+ * training order; user_mean: fp64[n_users] (n2v_eccknn_row_moments over the same lists).  Over the entries j of ur[u] in
+ * list order with freq[i][j] > 0 (the item itself included, when u rated it): s = s + dev[i][j] from +0.0, n_dev += 1;
+ *   est = user_mean[u] if n_dev == 0, else user_mean[u] + s / (double)n_dev       (before any fallback or clipping)
+ * A u or i outside its range (-1) is unknown: impossible = 1, est = 0, n_dev = 0; nothing else is impossible.  Row ranges
+ * are clamped to [0, n] and an entry of ur_i outside [0, n_items) is no entry, so a malformed list is no out-of-bounds
+ * access.  n_q >= 1.                                                                                                   */
+int n2v_slopeone_estimate(const double* dev, const int32_t* freq, int64_t n_items, const int64_t* ur_ptr, const int32_t* ur_i,
+                          int64_t n_users, int64_t n, const double* user_mean, const int32_t* q_u, const int32_t* q_i,
+                          int64_t n_q, double* est, int32_t* n_dev, uint8_t* impossible, void* stream);
+/* The top-N lists of the section above with n2v_slopeone_estimate's value as the score, by the bits: one wavefront per
+ * (owner, segment), 64 neighbouring candidates at a time, one a lane; every rated j adds -dev[j][c], which has the bits of
+ * dev[c][j], to the lane's own sum in list order, so a candidate's reads are two contiguous pieces of row j.  Owners,
+ * seen_*, top_n, segments, the scratch and the outputs as n2v_eccknn_topn.                                             */
+int n2v_slopeone_topn(const double* dev, const int32_t* freq, int64_t n_items, const int64_t* ur_ptr, const int32_t* ur_i,
+                      int64_t n_users, int64_t n, const double* user_mean, const int64_t* seen_ptr, const int32_t* seen_i,
+                      int64_t n_seen, const int32_t* owners, int64_t n_owners, double global_mean, double lo, double hi,
+                      int32_t top_n, int32_t segments, double* part_score, int32_t* part_pos, int32_t* items, double* score,
+                      void* stream);
+
 /* ---- Eccentricity statistics: the ir / ie / ire / ier item weights and the per-user ue (csrc/n2v_eccstats.hip) -----
  * Replaces src/utils.py:53-153 (pandas group-bys and merges).  Rows are (user, item, feedback, timewindow) with inner
  * ids; a group is a distinct (item, timewindow) pair, numbered in ascending (item, timewindow) order.  Everything is

@@ -24,6 +24,10 @@
 //                    baseline form carries prods, sq_diff_i, sq_diff_j of the ratings' deviations from
 //                    global_mean + by[y] + bx[x], with the thread's 4 + 4 bx in registers and global_mean + by[y]
 //                    staged beside w[y].  w may be absent there: the factor is 1.0, which changes no bit.
+//                    SlopeOne's deviation table (n2v_slopeone_dev, n2v_slopeone_dev_sparse) is a fifth METHOD with the
+//                    lightest accumulator, one count and one sum of ri - rj a pair, and a finishing step of its own
+//                    (finish_tile_slope): the lower half is the upper value with its sign bit flipped, also inside a
+//                    diagonal tile.  The estimate and the top-N kernel that read the table are in n2v_slopeone.hip.
 //   baselines_kernel one half-epoch of surprise's baseline_als: one wavefront per row gathers the other side's
 //                    baselines 64 at a time and adds the terms (r - mean) - b in list order.
 //   estimate_kernel  one wavefront per query: gathers sim[x, x2] over the raters of y, keeps the best k of them in a
@@ -67,6 +71,7 @@ __global__ void __launch_bounds__(256) densify_kernel(const int32_t* __restrict_
 
 constexpr int M_PEARSON = 2;      // METHOD values after N2V_ECCKNN_COSINE / N2V_ECCKNN_MSD; the C-ABI reaches them only
 constexpr int M_PBASE = 3;        // through n2v_eccknn_pearson[_sparse] (kind 0 / 1), never through the old method enum
+constexpr int M_SLOPE = 4;        // SlopeOne's deviations, through n2v_slopeone_dev[_sparse] only: p0 the sum of ri - rj
 
 struct SimOut {
     int64_t n_x; int min_support;
@@ -142,6 +147,33 @@ __device__ __forceinline__ void finish_tile(const SimOut& o, int64_t i0, int64_t
                     if (o.sj) o.sj[m] = p3[u][v];
                 }
             }
+        }
+    }
+}
+
+// SlopeOne's finishing step: o.sim is dev, o.prods the optional raw sums.  The pair i < j writes both of its entries:
+// dev[i][j] = p0 / fr (no rater in common: 0.0 / 0 = NaN) and dev[j][i] = -dev[i][j], the negation of the stored value,
+// so two items every co-rater rated alike get +0.0 above the diagonal and -0.0 below it.  A pair i > j of a diagonal tile
+// writes nothing: its entries are its mirror pair's.  The raw sum of the pair (j, i) is the sum of the negated terms from
+// +0.0: -p0, and +0.0 where p0 is a zero (x + -x and 0.0 + -0.0 are +0.0).
+__device__ __forceinline__ void finish_tile_slope(const SimOut& o, int64_t i0, int64_t j0, int ty, int tx,
+                                                  const int32_t (&fr)[4][4], const double (&p0)[4][4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int64_t i = i0 + 4 * ty + u;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+            const int64_t j = j0 + 4 * tx + v;
+            if (i >= o.n_x || j >= o.n_x || i > j) continue;
+            const int64_t k = i * o.n_x + j, m = j * o.n_x + i;
+            const double d = i == j ? 0.0 : p0[u][v] / (double)fr[u][v];
+            o.sim[k] = d;
+            o.freq[k] = fr[u][v];
+            if (o.prods) o.prods[k] = p0[u][v];
+            if (i == j) continue;
+            o.sim[m] = -d;
+            o.freq[m] = fr[u][v];
+            if (o.prods) o.prods[m] = p0[u][v] == 0.0 ? 0.0 : -p0[u][v];
         }
     }
 }
@@ -256,6 +288,15 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
                         p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
                         p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
                     }
+            } else if (METHOD == M_SLOPE) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
+                        fr[u][v] += co ? 1 : 0;
+                        p0[u][v] = co ? p0[u][v] + (ri[u] - rj[v]) : p0[u][v];
+                    }
             } else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -270,7 +311,8 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
         }
     }
 
-    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2, p3, p4);
+    if (METHOD == M_SLOPE) finish_tile_slope(a.o, i0, j0, ty, tx, fr, p0);
+    else finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2, p3, p4);
 }
 
 // ---- similarity, sparse -----------------------------------------------------------------------------------------------
@@ -290,7 +332,7 @@ template <int METHOD>
 __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
     __shared__ int32_t sy[2 * TB][SP];                            // rows 0..63: the tile's rows, 64..127: its columns
     __shared__ double sr[2 * TB][SP];
-    __shared__ double sw[TB][SP];                                 // w[y] of the staged entries of the tile's rows
+    __shared__ double sw[METHOD == M_SLOPE ? 1 : TB][SP];         // w[y] of the staged entries of the tile's rows
     __shared__ double sp[METHOD == M_PBASE ? TB : 1][SP];         // global_mean + by[y] of the same entries
     __shared__ int64_t pos[2 * TB], end[2 * TB];                  // cursor and end of every row, inside [0, n]
     __shared__ int32_t ready[2 * TB];
@@ -338,7 +380,7 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
                 const int32_t y = a.xr_y[p];
                 sy[row][k] = y;
                 sr[row][k] = a.xr_r[p];
-                if (row < TB) {
+                if (METHOD != M_SLOPE && row < TB) {
                     const bool in = y >= 0 && y < a.n_y;
                     sw[row][k] = in ? (a.w ? a.w[y] : 1.0) : __builtin_nan("");
                     if (METHOD == M_PBASE) sp[row][k] = in ? a.b.global_mean + a.b.by[y] : __builtin_nan("");
@@ -380,7 +422,7 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
                 int32_t ya = sy[ra][0], yb = sy[rb][0];
                 for (;;) {                                        // y ascending: the order of every accumulator
                     if (ya == yb) {
-                        const double ri = sr[ra][ka], rj = sr[rb][kb], wy = sw[ra][ka];
+                        const double ri = sr[ra][ka], rj = sr[rb][kb], wy = METHOD == M_SLOPE ? 1.0 : sw[ra][ka];
                         fr[u][v] += 1;
                         if (METHOD == N2V_ECCKNN_COSINE) {
                             p0[u][v] = p0[u][v] + (ri * rj) * wy; // `ri * rj * i_dict[y]`: left to right
@@ -398,6 +440,8 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
                             p0[u][v] = p0[u][v] + (di * dj) * wy;
                             p1[u][v] = p1[u][v] + di * di;
                             p2[u][v] = p2[u][v] + dj * dj;
+                        } else if (METHOD == M_SLOPE) {
+                            p0[u][v] = p0[u][v] + (ri - rj);
                         } else {
                             const double d = (ri - rj) * wy;
                             p0[u][v] = p0[u][v] + d * d;
@@ -417,7 +461,8 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
         par ^= 1;
         __syncthreads();                                          // the staged segments have been consumed
     }
-    finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2, p3, p4);
+    if (METHOD == M_SLOPE) finish_tile_slope(a.o, i0, j0, ty, tx, fr, p0);
+    else finish_tile<METHOD>(a.o, i0, j0, ty, tx, ti == tj, fr, p0, p1, p2, p3, p4);
 }
 
 // One lane per row and per entry; integers only.
@@ -842,6 +887,43 @@ int n2v_eccknn_pearson_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const 
     if (kind == N2V_ECCKNN_PEARSON) sim_sparse_kernel<M_PEARSON><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     else sim_sparse_kernel<M_PBASE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
     return n2v::check_launch("eccknn_pearson_sparse");
+}
+
+// What the two SlopeOne table calls check of their outputs; 0 or the error.
+static int slope_args(const char* who, int64_t n_items, const double* dev, const int32_t* freq) {
+    if (n_items > 65535 || n_items * n_items > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "%s: n_items^2 = %lld^2 exceeds the table limit of %lld elements", who,
+                         (long long)n_items, (long long)MAX_DENSE);
+    if (!dev || !freq) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    return N2V_OK;
+}
+
+int n2v_slopeone_dev(const double* dense, const uint8_t* mask, int64_t n_items, int64_t n_users, double* dev, int32_t* freq,
+                     double* acc, void* stream) {
+    if (n_items < 1 || n_users < 1) return n2v::fail(N2V_ERR_INVALID, "slopeone_dev: n_items=%lld n_users=%lld", (long long)n_items, (long long)n_users);
+    if (const int rc = slope_args("slopeone_dev", n_items, dev, freq)) return rc;
+    if (n_users > MAX_DENSE || n_items * n_users > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "slopeone_dev: n_items * n_users = %lld x %lld exceeds the dense limit of %lld elements",
+                         (long long)n_items, (long long)n_users, (long long)MAX_DENSE);
+    if (!dense || !mask) return n2v::fail(N2V_ERR_INVALID, "slopeone_dev: null pointer");
+    const int64_t T = (n_items + TB - 1) / TB;
+    SimArgs a{dense, mask, n_users, nullptr, SimOut{n_items, 0, dev, freq, acc, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0},
+              Baselines{nullptr, nullptr, 0.0}};
+    sim_kernel<M_SLOPE><<<dim3((unsigned)T, (unsigned)T), 256, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("slopeone_dev");
+}
+
+int n2v_slopeone_dev_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_items, int64_t n_users,
+                            int64_t n, double* dev, int32_t* freq, double* acc, void* stream) {
+    if (n_items < 1 || n_users < 1 || n_users > Y_MAX || n < 0)
+        return n2v::fail(N2V_ERR_INVALID, "slopeone_dev_sparse: n_items=%lld n_users=%lld n=%lld", (long long)n_items, (long long)n_users, (long long)n);
+    if (const int rc = slope_args("slopeone_dev_sparse", n_items, dev, freq)) return rc;
+    if (!xr_ptr || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "slopeone_dev_sparse: null pointer");
+    const int64_t T = (n_items + TB - 1) / TB;
+    SparseArgs a{xr_ptr, xr_y, xr_r, n_users, n, nullptr, T,
+                 SimOut{n_items, 0, dev, freq, acc, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0}, Baselines{nullptr, nullptr, 0.0}};
+    sim_sparse_kernel<M_SLOPE><<<(unsigned)(T * (T + 1) / 2), 256, 0, (hipStream_t)stream>>>(a);
+    return n2v::check_launch("slopeone_dev_sparse");
 }
 
 int n2v_eccknn_baselines(const int64_t* ur_ptr, const int32_t* ur_i, const double* ur_r, int64_t n_users,

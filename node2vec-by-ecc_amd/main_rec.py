@@ -8,6 +8,7 @@ plain k-NN (surprise's KNNBasic) it is compared against.
     python main_rec.py -input ratings.csv -algo mf [-factors 100] [-epochs 20] [-lr 0.005] [-reg 0.02] [-strata N|auto]
                        [-unbiased] [-test-ratio 0.2] [-seed 0] [-cv N]
     python main_rec.py -input ratings.csv -algo nmf [-factors 15] [-epochs 50] [-reg 0.06] [-test-ratio 0.2] [-seed 0] [-cv N]
+    python main_rec.py -input ratings.csv -algo slopeone [-form auto|dense|sparse] [-test-ratio 0.2] [-seed 0] [-cv N]
     every form:        [-topn N [-threshold T] [-save-recs FILE]]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
@@ -28,6 +29,11 @@ plain k-NN (surprise's KNNBasic) it is compared against.
           multiplicative update, trained on the device in surprise's own order of the ratings (n2v_hip.nmf): -factors,
           -epochs and -reg are surprise's n_factors, n_epochs and reg_pu = reg_qi, and -seed also seeds the factors.  It
           has no biases, no learning rate and no schedule: it takes none of -lr, -strata, -unbiased and the k-NN flags.
+          slopeone: surprise's SlopeOne (restated; parity with surprise is unpinned), the parameter-free baseline: the mean
+          difference of every pair of items over the users who rated both, fitted on the device by the co-rated pair pass of
+          the similarities (n2v_hip.slopeone), and a prediction is the user's mean plus the mean difference to the items
+          they rated.  It has no hyper-parameter and no random state: beside the split, -topn and -device flags it takes
+          -form alone, and none of -k, -mink, -sim, -shrinkage, -weights, -mode, -item-based and the factor flags.
           svd itself is not built: surprise's order of the ratings is sequential, and -algo mf follows it only with -strata 1.
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
 -mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
@@ -62,7 +68,7 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="EccenKNN / KNNBasic rating prediction (HIP, gfx950)")
     p.add_argument("-input", required=True)
     p.add_argument("-algo", default="eccen")
-    p.add_argument("-shrinkage", type=float, default=100)
+    p.add_argument("-shrinkage", type=float, default=None)
     p.add_argument("-k", type=int, default=None)
     p.add_argument("-mink", type=int, default=None)
     p.add_argument("-sim", default=None)
@@ -101,19 +107,20 @@ def parse_args(argv=None):
     if a.algo == "svd":
         p.error("-algo svd is not built: surprise's SVD applies the ratings in one sequential order.  -algo mf is the same "
                 "model and update under a deterministic stratified order (equal to surprise's only with -strata 1)")
-    if a.algo not in ("eccen", "mf", "nmf") + KNN_ALGOS:
-        p.error("-algo %s: eccen, %s, mf or nmf" % (a.algo, ", ".join(KNN_ALGOS)))
+    if a.algo not in ("eccen", "mf", "nmf", "slopeone") + KNN_ALGOS:
+        p.error("-algo %s: eccen, %s, mf, nmf or slopeone" % (a.algo, ", ".join(KNN_ALGOS)))
     knn_flags = (("-sim", a.sim), ("-k", a.k), ("-mink", a.mink), ("-weights", a.weights), ("-mode", a.mode),
                  ("-item-based", a.item_based or None), ("-form", a.form))
     mf_flags = (("-factors", a.factors), ("-epochs", a.epochs), ("-lr", a.lr), ("-reg", a.reg), ("-strata", a.strata),
                 ("-unbiased", a.unbiased or None))
     sgd_flags = tuple(f for f in mf_flags if f[0] in ("-lr", "-strata", "-unbiased"))     # what mf has and nmf has not
-    for flag, v in {"mf": knn_flags, "nmf": knn_flags + sgd_flags}.get(a.algo, mf_flags):
+    slope_flags = tuple(f for f in knn_flags if f[0] != "-form") + (("-shrinkage", a.shrinkage),) + mf_flags   # all but -form
+    for flag, v in {"mf": knn_flags, "nmf": knn_flags + sgd_flags, "slopeone": slope_flags}.get(a.algo, mf_flags):
         if v is not None:
             p.error("%s does not go with -algo %s" % (flag, a.algo))
     factor_defaults = (("factors", 15), ("epochs", 50), ("reg", 0.06)) if a.algo == "nmf" else ()
-    for name, v in factor_defaults + (("k", 40), ("mink", 1), ("sim", "cosine"), ("form", "auto"), ("factors", 100), ("epochs", 20),
-                                      ("lr", 0.005), ("reg", 0.02), ("strata", "auto")):
+    for name, v in factor_defaults + (("shrinkage", 100), ("k", 40), ("mink", 1), ("sim", "cosine"), ("form", "auto"),
+                                      ("factors", 100), ("epochs", 20), ("lr", 0.005), ("reg", 0.02), ("strata", "auto")):
         if getattr(a, name) is None:
             setattr(a, name, v)
     if a.strata != "auto":
@@ -249,6 +256,9 @@ def fit_split(args, users, items, ratings, weights, train):
         algo = nmf.NMF(n_factors=args.factors, n_epochs=args.epochs, reg_pu=args.reg, reg_qi=args.reg, random_state=args.seed,
                        device=args.device)
         return algo.fit(ts)
+    if args.algo == "slopeone":
+        from n2v_hip import slopeone
+        return slopeone.SlopeOne(sim_options={"form": args.form}, device=args.device).fit(ts)
     sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
     if args.algo in KNN_ALGOS:
         sim_options["shrinkage"] = args.shrinkage

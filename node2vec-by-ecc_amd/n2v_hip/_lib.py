@@ -147,7 +147,13 @@ SIGNATURES = {
                                   _f64, _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_svd_topn": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _f64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _f64, _f64,
                                _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
-    "n2v_eccstats_log_table": (C.c_int, [_i64, _ptr]),
+    "n2v_slopeone_dev": (C.c_int, [_ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_slopeone_dev_sparse": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_slopeone_estimate": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr,
+                                        _ptr]),
+    "n2v_slopeone_topn": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _f64, _f64,
+                                    _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccstats_log_table":(C.c_int, [_i64, _ptr]),
     "n2v_eccstats_groups_scratch": (C.c_int64, [_i64]),
     "n2v_eccstats_groups": (C.c_int, [_ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_eccstats_irg": (C.c_int, [_ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr]),

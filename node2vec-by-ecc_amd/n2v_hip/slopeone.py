@@ -1,0 +1,204 @@
+"""SlopeOne rating prediction on the device (csrc/n2v_eccknn.hip and csrc/n2v_slopeone.hip, C-ABI include/n2v_sim.h).
+
+surprise 1.0.6's SlopeOne (Lemire and Maclachlan 2005), the parameter-free baseline of its prediction_algorithms package:
+dev[i][j] is the mean of r[u][i] - r[u][j] over the users who rated both items, and a prediction is the user's mean plus
+the mean of dev[i][j] over the items j the user rated that share a rater with i.  Parity is UNPINNED: `surprise` is not a
+dependency here, the rules are restated from memory (tests/slopeone_reference.py, which is the definition) and the kernels
+are held to that restatement bit for bit.  Deviation: the user means are sequential sums in training order
+(eccknn.row_moments), where numpy's mean adds pairwise above 8 elements.
+
+The model has no hyper-parameter, no random state and no sequential update, so it follows surprise's own order of the
+ratings.  The fit is the co-rated pair pass of the similarity kernels with a lighter accumulator, in the same two forms
+with the same bytes: sim_options["form"] = "auto" (dense inside n_items * n_users <= 2^31, sparse past it), "dense" or
+"sparse".  The table is n_items x n_items (fp64 dev, int32 freq), n_items^2 <= 2^31.  The top-N lists read it densely:
+for a user and 64 neighbouring candidates every rated item contributes one contiguous piece of its row.
+
+Everything is fp64.  There is no CPU fallback.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .eccknn import (PredictionImpossible, TopN, _require_gpu, _topn_buffers, _topn_inputs, choose_form, csr_by_x, csr_check,
+                     densify, predict, row_moments, topn_options, yr_check, FORMS)
+
+MAX_TABLE = 1 << 31              # elements of dev: n_items * n_items
+
+
+def check_items(n_items):
+    """n_items as the table allows it; host arithmetic only, before anything is allocated."""
+    n_items = int(n_items)
+    if n_items < 1 or n_items * n_items > MAX_TABLE:
+        raise ValueError("slopeone: n_items^2 = %d^2 exceeds the table limit of %d elements (16 GiB of dev, 8 GiB of freq)"
+                         % (n_items, MAX_TABLE))
+    return n_items
+
+
+# ---- C-ABI wrappers (device tensors in, device tensors out) -----------------------------------------------------------
+
+def _table(n_items, dev_, accumulators):
+    return (torch.empty((n_items, n_items), dtype=torch.float64, device=dev_),
+            torch.empty((n_items, n_items), dtype=torch.int32, device=dev_),
+            torch.empty((n_items, n_items), dtype=torch.float64, device=dev_) if accumulators else None)
+
+
+def deviations(dense, mask, accumulators=False):
+    """(dev fp64, freq int32) [n_items][n_items] from eccknn.densify(items, users, r, n_items, n_users)
+    (n2v_slopeone_dev); with accumulators also acc, the raw sums."""
+    n_users, n_items = dense.shape
+    check_items(n_items)
+    _require_gpu()
+    d = dense.device
+    with torch.cuda.device(d):
+        dev, freq, acc = _table(n_items, d, accumulators)
+        _lib.check(_lib.load().n2v_slopeone_dev(_lib.ptr(dense), _lib.ptr(mask), n_items, n_users, _lib.ptr(dev), _lib.ptr(freq),
+                                                _lib.ptr(acc), _lib.stream_ptr(d)))
+    return (dev, freq, acc) if accumulators else (dev, freq)
+
+
+def deviations_sparse(xr, n_users, accumulators=False):
+    """deviations() from the item-major CSR xr = eccknn.csr_by_x(items, users, r, n_items, n_users): the same bytes, no
+    n_items * n_users limit (n2v_slopeone_dev_sparse).  The CSR is checked first; a malformed one is a ValueError."""
+    if len(xr) != 3 or xr[0].dtype != torch.int64 or xr[1].dtype != torch.int32 or xr[2].dtype != torch.float64:
+        raise ValueError("deviations_sparse: xr must be (int64 ptr, int32 user, fp64 r)")
+    n_items, n = xr[0].numel() - 1, xr[1].numel()
+    check_items(n_items)
+    if xr[2].numel() != n:
+        raise ValueError("deviations_sparse: %d rows, %d users, %d r" % (n_items, n, xr[2].numel()))
+    _require_gpu()
+    csr_check(xr, n_users)
+    d = xr[2].device
+    with torch.cuda.device(d):
+        dev, freq, acc = _table(n_items, d, accumulators)
+        _lib.check(_lib.load().n2v_slopeone_dev_sparse(_lib.ptr(xr[0]), _lib.ptr(xr[1]) if n else None,
+                                                       _lib.ptr(xr[2]) if n else None, n_items, int(n_users), n, _lib.ptr(dev),
+                                                       _lib.ptr(freq), _lib.ptr(acc), _lib.stream_ptr(d)))
+    return (dev, freq, acc) if accumulators else (dev, freq)
+
+
+def _model_args(dev, freq, ur, user_mean, check):
+    """The model's part of the two calls below after the host checks; ur = (ptr int64[n_users + 1], item int32, r fp64) in
+    training order.  check: eccknn.yr_check on ur (integers only): a malformed list is a ValueError, not a launch."""
+    n_items, n_users = dev.shape[0], ur[0].numel() - 1
+    check_items(n_items)
+    if tuple(dev.shape) != (n_items, n_items) or tuple(freq.shape) != (n_items, n_items) or dev.dtype != torch.float64 \
+            or freq.dtype != torch.int32 or user_mean.dtype != torch.float64 or user_mean.numel() != n_users:
+        raise ValueError("slopeone: dev fp64 and freq int32 must be [n_items][n_items], user_mean fp64[n_users = %d]" % n_users)
+    if check:
+        yr_check(ur, n_items)
+    n = ur[1].numel()
+    return [_lib.ptr(dev), _lib.ptr(freq), n_items, _lib.ptr(ur[0]), _lib.ptr(ur[1]) if n else None, n_users, n,
+            _lib.ptr(user_mean)]
+
+
+def estimate_batch(dev, freq, ur, user_mean, qu, qi, check=True):
+    """(est fp64, n_deviations int32, impossible uint8) device tensors for int32 device queries, -1 = unknown
+    (n2v_slopeone_estimate)."""
+    _require_gpu()
+    n_q = qu.numel()
+    if n_q == 0 or qi.numel() != n_q:
+        raise ValueError("estimate: %d user and %d item queries: nothing to estimate" % (n_q, qi.numel()))
+    model = _model_args(dev, freq, ur, user_mean, check)
+    d = dev.device
+    with torch.cuda.device(d):
+        est = torch.empty(n_q, dtype=torch.float64, device=d)
+        n_dev = torch.empty(n_q, dtype=torch.int32, device=d)
+        imp = torch.empty(n_q, dtype=torch.uint8, device=d)
+        _lib.check(_lib.load().n2v_slopeone_estimate(*model, _lib.ptr(qu), _lib.ptr(qi), n_q, _lib.ptr(est), _lib.ptr(n_dev),
+                                                     _lib.ptr(imp), _lib.stream_ptr(d)))
+    return est, n_dev, imp
+
+
+def top_n(dev, freq, ur, user_mean, seen, global_mean, rating_scale, n, owners=None, segments=None, check=True):
+    """eccknn.top_n for the deviation table (n2v_slopeone_topn): per owner the n unseen inner items with the best
+    predictions, each the bits of estimate_batch + eccknn.predict for that pair."""
+    n, segments = topn_options(n, segments)
+    _require_gpu()
+    model = _model_args(dev, freq, ur, user_mean, check)
+    n_items, n_users = model[2], model[5]
+    d = dev.device
+    owners = _topn_inputs(seen, n_users, n_items, owners, d)
+    lib = _lib.load()
+    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
+    with torch.cuda.device(d):
+        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, d)
+        n_seen = seen[1].numel()
+        _lib.check(lib.n2v_slopeone_topn(*model, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None, n_seen,
+                                         _lib.ptr(owners), owners.numel(), float(global_mean), float(rating_scale[0]),
+                                         float(rating_scale[1]), n, S, _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items),
+                                         _lib.ptr(score), _lib.stream_ptr(d)))
+    return items, score
+
+
+# ---- the algorithm ----------------------------------------------------------------------------------------------------
+
+class SlopeOne(TopN):
+    """surprise's SlopeOne, plus sim_options["form"] and device.  fit(trainset) takes an eccknn.Trainset; afterwards dev
+    (fp64), freq (int32) [n_items][n_items] and user_mean (fp64[n_users]) are device tensors."""
+
+    def __init__(self, sim_options=None, device="cuda:0"):
+        self.sim_options = dict(sim_options or {})
+        unknown = sorted(set(self.sim_options) - {"form"})
+        if unknown:
+            raise ValueError("slopeone: sim_options key %s: SlopeOne has no similarity, the one key is form" % ", ".join(unknown))
+        self.form = self.sim_options.get("form", "auto")
+        if self.form not in FORMS:
+            raise ValueError("slopeone: form %r, allowed values are %s" % (self.form, ", ".join(FORMS)))
+        self.device = device
+
+    def fit(self, trainset):
+        ts = trainset
+        check_items(ts.n_items)
+        form = choose_form(ts.n_items, ts.n_users, self.form)
+        _require_gpu()
+        d = torch.device(self.device)
+        self.trainset = ts
+        to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=d, dtype=dt)
+        di, du, dr = to(ts.i, torch.int32), to(ts.u, torch.int32), to(ts.r, torch.float64)
+        if form == "dense":
+            self.dev, self.freq = deviations(*densify(di, du, dr, ts.n_items, ts.n_users))
+        else:
+            self.dev, self.freq = deviations_sparse(csr_by_x(di, du, dr, ts.n_items, ts.n_users), ts.n_users)
+        self.ur = (to(ts.ur[0], torch.int64), to(ts.ur[1], torch.int32), to(ts.ur[2], torch.float64))
+        yr_check(self.ur, ts.n_items)
+        self.user_mean = row_moments(self.ur[0], self.ur[2])[0]
+        return self
+
+    def _queries(self, u, i):
+        to = lambda a: torch.as_tensor(np.asarray(a)).to(device=self.dev.device, dtype=torch.int32).contiguous()
+        return to(u), to(i)
+
+    def estimate(self, u, i):
+        """(est, {'n_deviations': n}) for inner ids u, i; PredictionImpossible for an unknown one, as surprise raises it."""
+        if not (self.trainset.knows_user(u) and self.trainset.knows_item(i)):
+            raise PredictionImpossible("User and/or item is unkown.")
+        est, n_dev, _ = estimate_batch(self.dev, self.freq, self.ur, self.user_mean, *self._queries([u], [i]), check=False)
+        return float(est.item()), {"n_deviations": int(n_dev.item())}
+
+    def _test(self, testset):
+        """testset: (raw user, raw item, true rating) triples."""
+        testset = list(testset)
+        if not testset:
+            raise ValueError("test: empty testset")
+        ts = self.trainset
+        qu, qi = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
+        est, n_dev, imp = estimate_batch(self.dev, self.freq, self.ur, self.user_mean, qu, qi, check=False)
+        r_true = torch.as_tensor(np.array([t[2] for t in testset], dtype=np.float64)).to(self.dev.device)
+        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
+        return pred, n_dev, imp, err
+
+    def test(self, testset):
+        """Arrays (est, n_deviations, was_impossible): est after the global-mean fallback and clipping."""
+        pred, n_dev, imp, _ = self._test(testset)
+        return pred.cpu().numpy(), n_dev.cpu().numpy(), imp.cpu().numpy().astype(bool)
+
+    def rmse(self, testset):
+        return self._test(testset)[3]
+
+    def _device(self):
+        return self.dev.device
+
+    def _top_n(self, owners, n, segments):
+        ts = self.trainset
+        return top_n(self.dev, self.freq, self.ur, self.user_mean, self._seen(), ts.global_mean, ts.rating_scale, n, owners,
+                     segments, check=False)
