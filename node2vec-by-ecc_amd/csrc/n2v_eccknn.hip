@@ -16,8 +16,8 @@
 //                    from its own cursor.  A round's bound is the smallest last-staged y among the rows that have entries
 //                    beyond their staged ones: up to it every row's staged segment is complete, so every thread merges
 //                    its 16 pairs of segments two-pointer fashion in y order, and the cursors advance by what was ready.
-//                    The row that set the bound consumes its whole chunk, so every round makes progress.  finish_tile is
-//                    shared with sim_kernel.  csr_check_kernel (integers only) names a malformed CSR; the similarity
+//                    The row that set the bound consumes its whole chunk, so every round makes progress.  pair_step
+//                    and finish_tile are shared with sim_kernel.  csr_check_kernel (integers only) names a malformed CSR; the similarity
 //                    kernel itself clamps every row range to [0, n] and never indexes w with a y outside [0, n_y).
 //                    The two Pearson similarities of surprise's KNNBasic (n2v_eccknn_pearson, n2v_eccknn_pearson_sparse)
 //                    are two more METHODs of the same two kernels: pearson carries prods, sqi, sqj, si, sj; the
@@ -43,6 +43,8 @@
 //                    the same knn_estimate and predict_value as the two kernels above, folded into a best-N list in LDS;
 //                    nothing of size owners x items is stored.  The S segment lists of an owner are merged under the
 //                    same order (n2v_topn.h), so the result does not depend on S.
+#include <type_traits>
+
 #include "n2v_common.h"
 #include "n2v_sim.h"
 #include "n2v_rank.h"
@@ -151,6 +153,32 @@ __device__ __forceinline__ void finish_tile(const SimOut& o, int64_t i0, int64_t
     }
 }
 
+// One co-rated y of one pair, the one copy behind the dense and the sparse kernel: a and b are the two ratings (under
+// pearson_baseline their deviations), qa and qb their squares, wy the weight of y.  co is a select, never a multiply: a
+// y that one side did not rate leaves every accumulator untouched, whatever the staged values are; the sparse kernel
+// meets only co-rated y and passes true.  Every product and sum is rounded on its own, left to right as the reference
+// writes them (`ri * rj * i_dict[y]`).  finish_tile names p0 .. p4 per method.
+template <int METHOD>
+__device__ __forceinline__ void pair_step(bool co, double a, double b, double qa, double qb, double wy, int32_t& fr,
+                                          double& p0, double& p1, double& p2, double& p3, double& p4) {
+    fr += co ? 1 : 0;
+    if (METHOD == N2V_ECCKNN_COSINE || METHOD == M_PEARSON || METHOD == M_PBASE) {
+        const double pr = (a * b) * wy;
+        p0 = co ? p0 + pr : p0;
+        p1 = co ? p1 + qa : p1;
+        p2 = co ? p2 + qb : p2;
+        if (METHOD == M_PEARSON) {
+            p3 = co ? p3 + a : p3;
+            p4 = co ? p4 + b : p4;
+        }
+    } else if (METHOD == M_SLOPE) {
+        p0 = co ? p0 + (a - b) : p0;
+    } else {
+        const double d = (a - b) * wy;
+        p0 = co ? p0 + d * d : p0;
+    }
+}
+
 // SlopeOne's finishing step: o.sim is dev, o.prods the optional raw sums.  The pair i < j writes both of its entries:
 // dev[i][j] = p0 / fr (no rater in common: 0.0 / 0 = NaN) and dev[j][i] = -dev[i][j], the negation of the stored value,
 // so two items every co-rater rated alike get +0.0 above the diagonal and -0.0 below it.  A pair i > j of a diagonal tile
@@ -237,77 +265,21 @@ __global__ void __launch_bounds__(256) sim_kernel(SimArgs a) {
             double ri[4], rj[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) { ri[u] = ra[yy][4 * ty + u]; rj[u] = rb[yy][4 * tx + u]; }
-            if (METHOD == N2V_ECCKNN_COSINE) {
-                double si[4], sj[4];
+            const double pb = METHOD == M_PBASE ? pbl[yy] : 0.0;
+            double si[4], sj[4];                                  // the 4 + 4 squares, once for the 16 pairs
 #pragma unroll
-                for (int u = 0; u < 4; ++u) { si[u] = ri[u] * ri[u]; sj[u] = rj[u] * rj[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
-                        const double pr = (ri[u] * rj[v]) * wy;   // `ri * rj * i_dict[y]`: left to right
-                        fr[u][v] += co ? 1 : 0;
-                        p0[u][v] = co ? p0[u][v] + pr : p0[u][v];
-                        p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
-                        p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
-                    }
-            } else if (METHOD == M_PEARSON) {
-                double si[4], sj[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { si[u] = ri[u] * ri[u]; sj[u] = rj[u] * rj[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
-                        const double pr = (ri[u] * rj[v]) * wy;
-                        fr[u][v] += co ? 1 : 0;
-                        p0[u][v] = co ? p0[u][v] + pr : p0[u][v];
-                        p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
-                        p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
-                        p3[u][v] = co ? p3[u][v] + ri[u] : p3[u][v];
-                        p4[u][v] = co ? p4[u][v] + rj[v] : p4[u][v];
-                    }
-            } else if (METHOD == M_PBASE) {
-                const double pb = pbl[yy];
-                double di[4], dj[4], si[4], sj[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    di[u] = ri[u] - (pb + bxi[u]); dj[u] = rj[u] - (pb + bxj[u]);
-                    si[u] = di[u] * di[u]; sj[u] = dj[u] * dj[u];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
-                        const double pr = (di[u] * dj[v]) * wy;
-                        fr[u][v] += co ? 1 : 0;
-                        p0[u][v] = co ? p0[u][v] + pr : p0[u][v];
-                        p1[u][v] = co ? p1[u][v] + si[u] : p1[u][v];
-                        p2[u][v] = co ? p2[u][v] + sj[v] : p2[u][v];
-                    }
-            } else if (METHOD == M_SLOPE) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
-                        fr[u][v] += co ? 1 : 0;
-                        p0[u][v] = co ? p0[u][v] + (ri[u] - rj[v]) : p0[u][v];
-                    }
-            } else {
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
-                        const double d = (ri[u] - rj[v]) * wy;
-                        fr[u][v] += co ? 1 : 0;
-                        p0[u][v] = co ? p0[u][v] + d * d : p0[u][v];
-                    }
+            for (int u = 0; u < 4; ++u) {
+                if (METHOD == M_PBASE) { ri[u] = ri[u] - (pb + bxi[u]); rj[u] = rj[u] - (pb + bxj[u]); }   // the deviations
+                si[u] = ri[u] * ri[u]; sj[u] = rj[u] * rj[u];
             }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const bool co = ((mi >> (8 * u)) & 0xff) && ((mj >> (8 * v)) & 0xff);
+                    pair_step<METHOD>(co, ri[u], rj[v], si[u], sj[v], wy, fr[u][v], p0[u][v], p1[u][v], p2[u][v], p3[u][v],
+                                      p4[u][v]);
+                }
         }
     }
 
@@ -422,30 +394,14 @@ __global__ void __launch_bounds__(256) sim_sparse_kernel(SparseArgs a) {
                 int32_t ya = sy[ra][0], yb = sy[rb][0];
                 for (;;) {                                        // y ascending: the order of every accumulator
                     if (ya == yb) {
-                        const double ri = sr[ra][ka], rj = sr[rb][kb], wy = METHOD == M_SLOPE ? 1.0 : sw[ra][ka];
-                        fr[u][v] += 1;
-                        if (METHOD == N2V_ECCKNN_COSINE) {
-                            p0[u][v] = p0[u][v] + (ri * rj) * wy; // `ri * rj * i_dict[y]`: left to right
-                            p1[u][v] = p1[u][v] + ri * ri;
-                            p2[u][v] = p2[u][v] + rj * rj;
-                        } else if (METHOD == M_PEARSON) {
-                            p0[u][v] = p0[u][v] + (ri * rj) * wy;
-                            p1[u][v] = p1[u][v] + ri * ri;
-                            p2[u][v] = p2[u][v] + rj * rj;
-                            p3[u][v] = p3[u][v] + ri;
-                            p4[u][v] = p4[u][v] + rj;
-                        } else if (METHOD == M_PBASE) {
+                        double ri = sr[ra][ka], rj = sr[rb][kb];
+                        const double wy = METHOD == M_SLOPE ? 1.0 : sw[ra][ka];
+                        if (METHOD == M_PBASE) {
                             const double pb = sp[ra][ka];
-                            const double di = ri - (pb + bxi[u]), dj = rj - (pb + bxj[v]);
-                            p0[u][v] = p0[u][v] + (di * dj) * wy;
-                            p1[u][v] = p1[u][v] + di * di;
-                            p2[u][v] = p2[u][v] + dj * dj;
-                        } else if (METHOD == M_SLOPE) {
-                            p0[u][v] = p0[u][v] + (ri - rj);
-                        } else {
-                            const double d = (ri - rj) * wy;
-                            p0[u][v] = p0[u][v] + d * d;
+                            ri = ri - (pb + bxi[u]); rj = rj - (pb + bxj[v]);
                         }
+                        pair_step<METHOD>(true, ri, rj, ri * ri, rj * rj, wy, fr[u][v], p0[u][v], p1[u][v], p2[u][v], p3[u][v],
+                                          p4[u][v]);
                         if (++ka >= na[u] || ++kb >= nb[v]) break;
                         ya = sy[ra][ka]; yb = sy[rb][kb];
                     } else if (ya < yb) {
@@ -766,6 +722,180 @@ __global__ void __launch_bounds__(256) predict_kernel(const double* __restrict__
 
 }  // namespace
 
+// ---- the six tile calls: a frame check, the family's own checks, an args struct, a launch -----------------------------
+
+// The checks every dense tile call makes, in the order its callers always made them: the shape, the dense limit, the
+// family's own checks (extra: a callable, 0 or the error; SlopeOne's come before the dense limit, extra_first), the
+// pointers every method reads, the tile count.  xs / ys name the two sides in the messages.  T, the tiles a side, or the
+// (negative) error.
+template <class Extra>
+static int64_t dense_frame(const char* who, const char* xs, const char* ys, int64_t n_x, int64_t n_y, const double* dense,
+                           const uint8_t* mask, const double* sim, bool extra_first, Extra extra) {
+    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "%s: %s=%lld %s=%lld", who, xs, (long long)n_x, ys, (long long)n_y);
+    if (extra_first) if (const int rc = extra()) return rc;
+    if (n_x > MAX_DENSE || n_y > MAX_DENSE || n_x * n_y > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "%s: %s * %s = %lld x %lld exceeds the dense limit of %lld elements", who, xs, ys,
+                         (long long)n_x, (long long)n_y, (long long)MAX_DENSE);
+    if (!extra_first) if (const int rc = extra()) return rc;
+    if (!dense || !mask || !sim) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    const int64_t T = (n_x + TB - 1) / TB;
+    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "%s: %s %lld needs more than 65535 tiles a side", who, xs, (long long)n_x);
+    return T;
+}
+
+// The same for the sparse form, where every family's checks sit between the shape and the pointers.
+template <class Extra>
+static int64_t sparse_frame(const char* who, const char* xs, const char* ys, int64_t n_x, int64_t n_y, int64_t n,
+                            const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, const double* sim, Extra extra) {
+    if (n_x < 1 || n_y < 1 || n_y > Y_MAX || n < 0)
+        return n2v::fail(N2V_ERR_INVALID, "%s: %s=%lld %s=%lld n=%lld", who, xs, (long long)n_x, ys, (long long)n_y, (long long)n);
+    if (const int rc = extra()) return rc;
+    if (!xr_ptr || !sim || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    const int64_t T = (n_x + TB - 1) / TB;
+    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "%s: %s %lld needs more than 65535 tiles a side", who, xs, (long long)n_x);
+    return T;
+}
+
+// One workgroup per tile of the T x T grid (the lower triangle returns at once); method is one of the five METHODs.
+static int launch_sim(const char* who, int method, int64_t T, const SimArgs& a, void* stream) {
+    const dim3 grid((unsigned)T, (unsigned)T);
+    hipStream_t s = (hipStream_t)stream;
+    switch (method) {
+        case N2V_ECCKNN_COSINE: sim_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, s>>>(a); break;
+        case N2V_ECCKNN_MSD: sim_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, s>>>(a); break;
+        case M_PEARSON: sim_kernel<M_PEARSON><<<grid, 256, 0, s>>>(a); break;
+        case M_PBASE: sim_kernel<M_PBASE><<<grid, 256, 0, s>>>(a); break;
+        case M_SLOPE: sim_kernel<M_SLOPE><<<grid, 256, 0, s>>>(a); break;
+        default: return n2v::fail(N2V_ERR_INVALID, "%s: no tile kernel for method %d", who, method);
+    }
+    return n2v::check_launch(who);
+}
+
+// One workgroup per tile of the upper triangle, a.tiles a side.
+static int launch_sim_sparse(const char* who, int method, const SparseArgs& a, void* stream) {
+    const unsigned grid = (unsigned)(a.tiles * (a.tiles + 1) / 2);   // < 2^31 for T <= 65535
+    hipStream_t s = (hipStream_t)stream;
+    switch (method) {
+        case N2V_ECCKNN_COSINE: sim_sparse_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, s>>>(a); break;
+        case N2V_ECCKNN_MSD: sim_sparse_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, s>>>(a); break;
+        case M_PEARSON: sim_sparse_kernel<M_PEARSON><<<grid, 256, 0, s>>>(a); break;
+        case M_PBASE: sim_sparse_kernel<M_PBASE><<<grid, 256, 0, s>>>(a); break;
+        case M_SLOPE: sim_sparse_kernel<M_SLOPE><<<grid, 256, 0, s>>>(a); break;
+        default: return n2v::fail(N2V_ERR_INVALID, "%s: no tile kernel for method %d", who, method);
+    }
+    return n2v::check_launch(who);
+}
+
+// What cosine and msd check beside the frame: the method, and the weights they cannot do without; 0 or the error.
+static int method_args(const char* who, int32_t method, const double* w) {
+    if (method != N2V_ECCKNN_COSINE && method != N2V_ECCKNN_MSD) return n2v::fail(N2V_ERR_INVALID, "%s: method %d", who, method);
+    if (!w) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    return N2V_OK;
+}
+
+// What the two Pearson calls check beside the frame; 0 or the error.
+static int pearson_args(const char* who, int32_t kind, const double* bx, const double* by) {
+    if (kind != N2V_ECCKNN_PEARSON && kind != N2V_ECCKNN_PEARSON_BASELINE) return n2v::fail(N2V_ERR_INVALID, "%s: kind %d", who, kind);
+    if (kind == N2V_ECCKNN_PEARSON_BASELINE && (!bx || !by)) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (bx / by, required by kind 1)", who);
+    return N2V_OK;
+}
+
+// kind 0: a1 .. a4 are sqi, sqj, si, sj; kind 1: a1, a2 are sq_diff_i, sq_diff_j and min_support is raised to 2.
+static SimOut pearson_out(int32_t kind, int64_t n_x, int32_t min_support, double shrinkage, double* sim, int32_t* freq,
+                          double* prods, double* a1, double* a2, double* a3, double* a4) {
+    const bool base = kind == N2V_ECCKNN_PEARSON_BASELINE;
+    return SimOut{n_x, base && min_support < 2 ? 2 : min_support, sim, freq, prods, a1, a2, nullptr,
+                  base ? nullptr : a3, base ? nullptr : a4, shrinkage};
+}
+
+// What the two SlopeOne table calls check of their outputs; 0 or the error.
+static int slope_args(const char* who, int64_t n_items, const double* dev, const int32_t* freq) {
+    if (n_items > 65535 || n_items * n_items > MAX_DENSE)
+        return n2v::fail(N2V_ERR_INVALID, "%s: n_items^2 = %lld^2 exceeds the table limit of %lld elements", who,
+                         (long long)n_items, (long long)MAX_DENSE);
+    if (!dev || !freq) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    return N2V_OK;
+}
+
+static SimOut slope_out(int64_t n_items, double* dev, int32_t* freq, double* acc) {
+    return SimOut{n_items, 0, dev, freq, acc, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0};
+}
+
+// ---- the plain and the centred k-NN calls: one body each for the estimate and for the top-N lists ---------------------
+
+// What a centred call adds to the plain one: the caller's centring code as it came, and the tables.  The plain calls pass
+// none (NULL): mode C_NONE, which reads no table.
+struct Centred {
+    int32_t code; Centering tables;
+};
+
+// The checks the two centred calls make of their own; 0 or the error.  A table the mode reads may not be NULL.
+static int centering_args(const char* who, const Centred& c) {
+    if (c.code != N2V_ECCKNN_CENTER_MEANS && c.code != N2V_ECCKNN_CENTER_ZSCORE && c.code != N2V_ECCKNN_CENTER_BASELINE)
+        return n2v::fail(N2V_ERR_INVALID, "%s: centering %d (1 means, 2 z-score, 3 baseline)", who, c.code);
+    if (!c.tables.tx) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (tx, the mu or bx table over x)", who);
+    if (c.code == N2V_ECCKNN_CENTER_ZSCORE && !c.tables.sd) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (sd, required by centering 2)", who);
+    if (c.code == N2V_ECCKNN_CENTER_BASELINE && !c.tables.by) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (by, required by centering 3)", who);
+    return N2V_OK;
+}
+
+static int knn_options(const char* who, int32_t k, int32_t min_k) {
+    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "%s: k %d outside [1, %d]", who, k, N2V_ECCKNN_MAX_K);
+    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "%s: min_k %d < 1 (an empty neighbourhood has no mean)", who, min_k);
+    return N2V_OK;
+}
+
+// f(mode, tables) with the centring mode as a compile-time constant: what picks the instantiation of estimate_kernel and
+// of eccknn_topn_kernel.  c NULL: C_NONE; otherwise a code centering_args let through.
+template <class F>
+static void with_centering(const Centred* c, F f) {
+    if (!c) return f(std::integral_constant<int, C_NONE>{}, Centering{0.0, 1, nullptr, nullptr, nullptr});
+    switch (c->code) {
+        case N2V_ECCKNN_CENTER_MEANS: return f(std::integral_constant<int, N2V_ECCKNN_CENTER_MEANS>{}, c->tables);
+        case N2V_ECCKNN_CENTER_ZSCORE: return f(std::integral_constant<int, N2V_ECCKNN_CENTER_ZSCORE>{}, c->tables);
+        default: return f(std::integral_constant<int, N2V_ECCKNN_CENTER_BASELINE>{}, c->tables);
+    }
+}
+
+// n2v_eccknn_estimate (c NULL) and n2v_eccknn_estimate_centered.
+static int estimate_call(const char* who, const KnnModel& m, const int32_t* qx, const int32_t* qy, int64_t n_q,
+                         const Centred* c, double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
+    if (const int rc = knn_options(who, m.k, m.min_k)) return rc;
+    if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "%s: n_q %lld outside [1, 2^31)", who, (long long)n_q);
+    if (m.n_x < 1 || m.n_y < 1) return n2v::fail(N2V_ERR_INVALID, "%s: n_x=%lld n_y=%lld", who, (long long)m.n_x, (long long)m.n_y);
+    if (c) if (const int rc = centering_args(who, *c)) return rc;
+    if (!m.sim || !m.yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    const EstArgs a{m, qx, qy, n_q, est, actual_k, impossible};
+    with_centering(c, [&](auto mode, const Centering& t) {
+        estimate_kernel<decltype(mode)::value><<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a, t);
+    });
+    return n2v::check_launch(who);
+}
+
+// n2v_eccknn_topn (c NULL) and n2v_eccknn_topn_centered; merge_who names the merge launch in an error.
+static int topn_call(const char* who, const char* merge_who, const KnnModel& m, int32_t user_based, const int64_t* seen_ptr,
+                     const int32_t* seen_i, int64_t n_seen, const int32_t* owners, int64_t n_owners, double global_mean,
+                     double lo, double hi, int32_t top_n, int32_t segments, const Centred* c,
+                     double* part_score, int32_t* part_pos, int32_t* items, double* score, void* stream) {
+    if (const int rc = knn_options(who, m.k, m.min_k)) return rc;
+    if (m.n_x < 1 || m.n_y < 1) return n2v::fail(N2V_ERR_INVALID, "%s: n_x=%lld n_y=%lld", who, (long long)m.n_x, (long long)m.n_y);
+    if (c) if (const int rc = centering_args(who, *c)) return rc;
+    const int64_t n_users = user_based ? m.n_x : m.n_y, n_items = user_based ? m.n_y : m.n_x;
+    if (const int rc = n2v::topn_args(who, n_owners, n_items, top_n, segments, seen_ptr, seen_i, n_seen, owners, part_score,
+                                      part_pos, items, score))
+        return rc;
+    if (!m.sim || !m.yr_ptr) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
+    const TopnArgs a{m, user_based ? 1 : 0, Seen{seen_ptr, seen_i, n_users, n_seen}, n_items, owners, top_n, S, global_mean,
+                     lo, hi, part_score, part_pos};
+    hipStream_t s = (hipStream_t)stream;
+    with_centering(c, [&](auto mode, const Centering& t) {
+        eccknn_topn_kernel<decltype(mode)::value><<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, s>>>(a, t);
+    });
+    if (const int rc = n2v::check_launch(who)) return rc;
+    return n2v::topn_merge(merge_who, part_score, part_pos, n_owners, S, top_n, items, score, s);
+}
+
 extern "C" {
 
 int32_t n2v_eccknn_max_k(void) { return N2V_ECCKNN_MAX_K; }
@@ -791,20 +921,12 @@ int n2v_eccknn_densify(const int32_t* x, const int32_t* y, const double* r, int6
 int n2v_eccknn_sim(const double* dense, const uint8_t* mask, int64_t n_x, int64_t n_y, const double* w, int32_t method,
                    int32_t min_support, double* sim, int32_t* freq, double* prods, double* sqi, double* sqj,
                    double* sq_diff, void* stream) {
-    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
-    if (n_x > MAX_DENSE || n_y > MAX_DENSE || n_x * n_y > MAX_DENSE)
-        return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x * n_y = %lld x %lld exceeds the dense limit of %lld elements",
-                         (long long)n_x, (long long)n_y, (long long)MAX_DENSE);
-    if (method != N2V_ECCKNN_COSINE && method != N2V_ECCKNN_MSD) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: method %d", method);
-    if (!dense || !mask || !w || !sim) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: null pointer");
-    const int64_t T = (n_x + TB - 1) / TB;
-    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SimArgs a{dense, mask, n_y, w, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff, nullptr, nullptr, 0.0},
-              Baselines{nullptr, nullptr, 0.0}};
-    const dim3 grid((unsigned)T, (unsigned)T);
-    if (method == N2V_ECCKNN_COSINE) sim_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    else sim_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    return n2v::check_launch("eccknn_sim");
+    const char* who = "eccknn_sim";
+    const int64_t T = dense_frame(who, "n_x", "n_y", n_x, n_y, dense, mask, sim, false, [&] { return method_args(who, method, w); });
+    if (T < 0) return (int)T;
+    const SimArgs a{dense, mask, n_y, w, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff, nullptr, nullptr, 0.0},
+                    Baselines{nullptr, nullptr, 0.0}};
+    return launch_sim(who, method, T, a, stream);
 }
 
 int32_t n2v_eccknn_sparse_chunk(void) { return SC; }
@@ -822,108 +944,59 @@ int n2v_eccknn_csr_check(const int64_t* xr_ptr, const int32_t* xr_y, int64_t n_x
 int n2v_eccknn_sim_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_x, int64_t n_y,
                           int64_t n, const double* w, int32_t method, int32_t min_support, double* sim, int32_t* freq,
                           double* prods, double* sqi, double* sqj, double* sq_diff, void* stream) {
-    if (n_x < 1 || n_y < 1 || n_y > Y_MAX || n < 0)
-        return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: n_x=%lld n_y=%lld n=%lld", (long long)n_x, (long long)n_y, (long long)n);
-    if (method != N2V_ECCKNN_COSINE && method != N2V_ECCKNN_MSD) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: method %d", method);
-    if (!xr_ptr || !w || !sim || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: null pointer");
-    const int64_t T = (n_x + TB - 1) / TB;
-    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_sim_sparse: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T, SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff, nullptr, nullptr, 0.0},
-                 Baselines{nullptr, nullptr, 0.0}};
-    const unsigned grid = (unsigned)(T * (T + 1) / 2);            // < 2^31 for T <= 65535
-    if (method == N2V_ECCKNN_COSINE) sim_sparse_kernel<N2V_ECCKNN_COSINE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    else sim_sparse_kernel<N2V_ECCKNN_MSD><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    return n2v::check_launch("eccknn_sim_sparse");
-}
-
-// The checks n2v_eccknn_pearson and n2v_eccknn_pearson_sparse share; 0 or the error.
-static int pearson_args(const char* who, int32_t kind, const double* bx, const double* by) {
-    if (kind != N2V_ECCKNN_PEARSON && kind != N2V_ECCKNN_PEARSON_BASELINE) return n2v::fail(N2V_ERR_INVALID, "%s: kind %d", who, kind);
-    if (kind == N2V_ECCKNN_PEARSON_BASELINE && (!bx || !by)) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (bx / by, required by kind 1)", who);
-    return N2V_OK;
-}
-
-// kind 0: a1 .. a4 are sqi, sqj, si, sj; kind 1: a1, a2 are sq_diff_i, sq_diff_j and min_support is raised to 2.
-static SimOut pearson_out(int32_t kind, int64_t n_x, int32_t min_support, double shrinkage, double* sim, int32_t* freq,
-                          double* prods, double* a1, double* a2, double* a3, double* a4) {
-    const bool base = kind == N2V_ECCKNN_PEARSON_BASELINE;
-    return SimOut{n_x, base && min_support < 2 ? 2 : min_support, sim, freq, prods, a1, a2, nullptr,
-                  base ? nullptr : a3, base ? nullptr : a4, shrinkage};
+    const char* who = "eccknn_sim_sparse";
+    const int64_t T = sparse_frame(who, "n_x", "n_y", n_x, n_y, n, xr_ptr, xr_y, xr_r, sim, [&] { return method_args(who, method, w); });
+    if (T < 0) return (int)T;
+    const SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T,
+                       SimOut{n_x, min_support, sim, freq, prods, sqi, sqj, sq_diff, nullptr, nullptr, 0.0},
+                       Baselines{nullptr, nullptr, 0.0}};
+    return launch_sim_sparse(who, method, a, stream);
 }
 
 int n2v_eccknn_pearson(const double* dense, const uint8_t* mask, int64_t n_x, int64_t n_y, const double* w, int32_t kind,
                        int32_t min_support, double global_mean, const double* bx, const double* by, double shrinkage,
                        double* sim, int32_t* freq, double* prods, double* a1, double* a2, double* a3, double* a4,
                        void* stream) {
-    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
-    if (n_x > MAX_DENSE || n_y > MAX_DENSE || n_x * n_y > MAX_DENSE)
-        return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: n_x * n_y = %lld x %lld exceeds the dense limit of %lld elements",
-                         (long long)n_x, (long long)n_y, (long long)MAX_DENSE);
-    if (const int rc = pearson_args("eccknn_pearson", kind, bx, by)) return rc;
-    if (!dense || !mask || !sim) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: null pointer");
-    const int64_t T = (n_x + TB - 1) / TB;
-    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SimArgs a{dense, mask, n_y, w, pearson_out(kind, n_x, min_support, shrinkage, sim, freq, prods, a1, a2, a3, a4),
-              Baselines{bx, by, global_mean}};
-    const dim3 grid((unsigned)T, (unsigned)T);
-    if (kind == N2V_ECCKNN_PEARSON) sim_kernel<M_PEARSON><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    else sim_kernel<M_PBASE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    return n2v::check_launch("eccknn_pearson");
+    const char* who = "eccknn_pearson";
+    const int64_t T = dense_frame(who, "n_x", "n_y", n_x, n_y, dense, mask, sim, false, [&] { return pearson_args(who, kind, bx, by); });
+    if (T < 0) return (int)T;
+    const SimArgs a{dense, mask, n_y, w, pearson_out(kind, n_x, min_support, shrinkage, sim, freq, prods, a1, a2, a3, a4),
+                    Baselines{bx, by, global_mean}};
+    return launch_sim(who, kind == N2V_ECCKNN_PEARSON ? M_PEARSON : M_PBASE, T, a, stream);
 }
 
 int n2v_eccknn_pearson_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_x, int64_t n_y,
                               int64_t n, const double* w, int32_t kind, int32_t min_support, double global_mean,
                               const double* bx, const double* by, double shrinkage, double* sim, int32_t* freq,
                               double* prods, double* a1, double* a2, double* a3, double* a4, void* stream) {
-    if (n_x < 1 || n_y < 1 || n_y > Y_MAX || n < 0)
-        return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson_sparse: n_x=%lld n_y=%lld n=%lld", (long long)n_x, (long long)n_y, (long long)n);
-    if (const int rc = pearson_args("eccknn_pearson_sparse", kind, bx, by)) return rc;
-    if (!xr_ptr || !sim || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson_sparse: null pointer");
-    const int64_t T = (n_x + TB - 1) / TB;
-    if (T > 65535) return n2v::fail(N2V_ERR_INVALID, "eccknn_pearson_sparse: n_x %lld needs more than 65535 tiles a side", (long long)n_x);
-    SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T, pearson_out(kind, n_x, min_support, shrinkage, sim, freq, prods, a1, a2, a3, a4),
-                 Baselines{bx, by, global_mean}};
-    const unsigned grid = (unsigned)(T * (T + 1) / 2);            // < 2^31 for T <= 65535
-    if (kind == N2V_ECCKNN_PEARSON) sim_sparse_kernel<M_PEARSON><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    else sim_sparse_kernel<M_PBASE><<<grid, 256, 0, (hipStream_t)stream>>>(a);
-    return n2v::check_launch("eccknn_pearson_sparse");
-}
-
-// What the two SlopeOne table calls check of their outputs; 0 or the error.
-static int slope_args(const char* who, int64_t n_items, const double* dev, const int32_t* freq) {
-    if (n_items > 65535 || n_items * n_items > MAX_DENSE)
-        return n2v::fail(N2V_ERR_INVALID, "%s: n_items^2 = %lld^2 exceeds the table limit of %lld elements", who,
-                         (long long)n_items, (long long)MAX_DENSE);
-    if (!dev || !freq) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
-    return N2V_OK;
+    const char* who = "eccknn_pearson_sparse";
+    const int64_t T = sparse_frame(who, "n_x", "n_y", n_x, n_y, n, xr_ptr, xr_y, xr_r, sim, [&] { return pearson_args(who, kind, bx, by); });
+    if (T < 0) return (int)T;
+    const SparseArgs a{xr_ptr, xr_y, xr_r, n_y, n, w, T,
+                       pearson_out(kind, n_x, min_support, shrinkage, sim, freq, prods, a1, a2, a3, a4),
+                       Baselines{bx, by, global_mean}};
+    return launch_sim_sparse(who, kind == N2V_ECCKNN_PEARSON ? M_PEARSON : M_PBASE, a, stream);
 }
 
 int n2v_slopeone_dev(const double* dense, const uint8_t* mask, int64_t n_items, int64_t n_users, double* dev, int32_t* freq,
                      double* acc, void* stream) {
-    if (n_items < 1 || n_users < 1) return n2v::fail(N2V_ERR_INVALID, "slopeone_dev: n_items=%lld n_users=%lld", (long long)n_items, (long long)n_users);
-    if (const int rc = slope_args("slopeone_dev", n_items, dev, freq)) return rc;
-    if (n_users > MAX_DENSE || n_items * n_users > MAX_DENSE)
-        return n2v::fail(N2V_ERR_INVALID, "slopeone_dev: n_items * n_users = %lld x %lld exceeds the dense limit of %lld elements",
-                         (long long)n_items, (long long)n_users, (long long)MAX_DENSE);
-    if (!dense || !mask) return n2v::fail(N2V_ERR_INVALID, "slopeone_dev: null pointer");
-    const int64_t T = (n_items + TB - 1) / TB;
-    SimArgs a{dense, mask, n_users, nullptr, SimOut{n_items, 0, dev, freq, acc, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0},
-              Baselines{nullptr, nullptr, 0.0}};
-    sim_kernel<M_SLOPE><<<dim3((unsigned)T, (unsigned)T), 256, 0, (hipStream_t)stream>>>(a);
-    return n2v::check_launch("slopeone_dev");
+    const char* who = "slopeone_dev";
+    const int64_t T = dense_frame(who, "n_items", "n_users", n_items, n_users, dense, mask, dev, true,
+                                  [&] { return slope_args(who, n_items, dev, freq); });
+    if (T < 0) return (int)T;
+    const SimArgs a{dense, mask, n_users, nullptr, slope_out(n_items, dev, freq, acc), Baselines{nullptr, nullptr, 0.0}};
+    return launch_sim(who, M_SLOPE, T, a, stream);
 }
 
 int n2v_slopeone_dev_sparse(const int64_t* xr_ptr, const int32_t* xr_y, const double* xr_r, int64_t n_items, int64_t n_users,
                             int64_t n, double* dev, int32_t* freq, double* acc, void* stream) {
-    if (n_items < 1 || n_users < 1 || n_users > Y_MAX || n < 0)
-        return n2v::fail(N2V_ERR_INVALID, "slopeone_dev_sparse: n_items=%lld n_users=%lld n=%lld", (long long)n_items, (long long)n_users, (long long)n);
-    if (const int rc = slope_args("slopeone_dev_sparse", n_items, dev, freq)) return rc;
-    if (!xr_ptr || (n > 0 && (!xr_y || !xr_r))) return n2v::fail(N2V_ERR_INVALID, "slopeone_dev_sparse: null pointer");
-    const int64_t T = (n_items + TB - 1) / TB;
-    SparseArgs a{xr_ptr, xr_y, xr_r, n_users, n, nullptr, T,
-                 SimOut{n_items, 0, dev, freq, acc, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0}, Baselines{nullptr, nullptr, 0.0}};
-    sim_sparse_kernel<M_SLOPE><<<(unsigned)(T * (T + 1) / 2), 256, 0, (hipStream_t)stream>>>(a);
-    return n2v::check_launch("slopeone_dev_sparse");
+    const char* who = "slopeone_dev_sparse";
+    const int64_t T = sparse_frame(who, "n_items", "n_users", n_items, n_users, n, xr_ptr, xr_y, xr_r, dev,
+                                   [&] { return slope_args(who, n_items, dev, freq); });
+    if (T < 0) return (int)T;
+    const SparseArgs a{xr_ptr, xr_y, xr_r, n_users, n, nullptr, T, slope_out(n_items, dev, freq, acc),
+                       Baselines{nullptr, nullptr, 0.0}};
+    return launch_sim_sparse(who, M_SLOPE, a, stream);
 }
 
 int n2v_eccknn_baselines(const int64_t* ur_ptr, const int32_t* ur_i, const double* ur_r, int64_t n_users,
@@ -949,43 +1022,17 @@ int n2v_eccknn_baselines(const int64_t* ur_ptr, const int32_t* ur_i, const doubl
 int n2v_eccknn_estimate(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
                         int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
                         double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
-    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
-    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: min_k %d < 1 (an empty neighbourhood has no mean)", min_k);
-    if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_q %lld outside [1, 2^31)", (long long)n_q);
-    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
-    if (!sim || !yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate: null pointer");
-    EstArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, est, actual_k, impossible};
-    estimate_kernel<C_NONE><<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a, Centering{0.0, 1, nullptr, nullptr, nullptr});
-    return n2v::check_launch("eccknn_estimate");
-}
-
-// The checks the two centred calls share; 0 or the error.  A table the mode reads may not be NULL.
-static int centering_args(const char* who, int32_t centering, const double* tx, const double* sd, const double* by) {
-    if (centering != N2V_ECCKNN_CENTER_MEANS && centering != N2V_ECCKNN_CENTER_ZSCORE && centering != N2V_ECCKNN_CENTER_BASELINE)
-        return n2v::fail(N2V_ERR_INVALID, "%s: centering %d (1 means, 2 z-score, 3 baseline)", who, centering);
-    if (!tx) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (tx, the mu or bx table over x)", who);
-    if (centering == N2V_ECCKNN_CENTER_ZSCORE && !sd) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (sd, required by centering 2)", who);
-    if (centering == N2V_ECCKNN_CENTER_BASELINE && !by) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (by, required by centering 3)", who);
-    return N2V_OK;
+    return estimate_call("eccknn_estimate", KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, nullptr, est,
+                         actual_k, impossible, stream);
 }
 
 int n2v_eccknn_estimate_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
                                  int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, int32_t k, int32_t min_k,
                                  int32_t centering, int32_t user_based, double global_mean, const double* tx, const double* sd,
                                  const double* by, double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
-    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
-    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: min_k %d < 1", min_k);
-    if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: n_q %lld outside [1, 2^31)", (long long)n_q);
-    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
-    if (const int rc = centering_args("eccknn_estimate_centered", centering, tx, sd, by)) return rc;
-    if (!sim || !yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "eccknn_estimate_centered: null pointer");
-    EstArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, est, actual_k, impossible};
-    const Centering c{global_mean, user_based ? 1 : 0, tx, sd, by};
-    hipStream_t s = (hipStream_t)stream;
-    if (centering == N2V_ECCKNN_CENTER_MEANS) estimate_kernel<N2V_ECCKNN_CENTER_MEANS><<<(unsigned)n_q, 64, 0, s>>>(a, c);
-    else if (centering == N2V_ECCKNN_CENTER_ZSCORE) estimate_kernel<N2V_ECCKNN_CENTER_ZSCORE><<<(unsigned)n_q, 64, 0, s>>>(a, c);
-    else estimate_kernel<N2V_ECCKNN_CENTER_BASELINE><<<(unsigned)n_q, 64, 0, s>>>(a, c);
-    return n2v::check_launch("eccknn_estimate_centered");
+    const Centred c{centering, Centering{global_mean, user_based ? 1 : 0, tx, sd, by}};
+    return estimate_call("eccknn_estimate_centered", KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, qx, qy, n_q, &c,
+                         est, actual_k, impossible, stream);
 }
 
 int n2v_eccknn_row_moments(const int64_t* ptr, const double* r, int64_t n_rows, int64_t n, double zero_sigma, double* mu,
@@ -1011,21 +1058,9 @@ int n2v_eccknn_topn(const double* sim, int64_t n_x, const int64_t* yr_ptr, const
                     const int32_t* owners, int64_t n_owners, int32_t k, int32_t min_k, double global_mean, double lo,
                     double hi, int32_t top_n, int32_t segments, double* part_score, int32_t* part_pos, int32_t* items,
                     double* score, void* stream) {
-    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
-    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: min_k %d < 1 (an empty neighbourhood has no mean)", min_k);
-    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
-    const int64_t n_users = user_based ? n_x : n_y, n_items = user_based ? n_y : n_x;
-    if (const int rc = n2v::topn_args("eccknn_topn", n_owners, n_items, top_n, segments, seen_ptr, seen_i, n_seen, owners,
-                                      part_score, part_pos, items, score))
-        return rc;
-    if (!sim || !yr_ptr) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn: null pointer");
-    const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
-    TopnArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, user_based ? 1 : 0, Seen{seen_ptr, seen_i, n_users, n_seen},
-               n_items, owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
-    eccknn_topn_kernel<C_NONE><<<dim3((unsigned)n_owners, (unsigned)S), 64, 0, (hipStream_t)stream>>>(
-        a, Centering{0.0, 1, nullptr, nullptr, nullptr});
-    if (const int rc = n2v::check_launch("eccknn_topn")) return rc;
-    return n2v::topn_merge("eccknn_topn (merge)", part_score, part_pos, n_owners, S, top_n, items, score, (hipStream_t)stream);
+    return topn_call("eccknn_topn", "eccknn_topn (merge)", KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, user_based,
+                     seen_ptr, seen_i, n_seen, owners, n_owners, global_mean, lo, hi, top_n, segments, nullptr,
+                     part_score, part_pos, items, score, stream);
 }
 
 int n2v_eccknn_topn_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
@@ -1034,26 +1069,10 @@ int n2v_eccknn_topn_centered(const double* sim, int64_t n_x, const int64_t* yr_p
                              double hi, int32_t top_n, int32_t segments, int32_t centering, const double* tx, const double* sd,
                              const double* by, double* part_score, int32_t* part_pos, int32_t* items, double* score,
                              void* stream) {
-    if (k < 1 || k > N2V_ECCKNN_MAX_K) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: k %d outside [1, %d]", k, N2V_ECCKNN_MAX_K);
-    if (min_k < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: min_k %d < 1", min_k);
-    if (n_x < 1 || n_y < 1) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: n_x=%lld n_y=%lld", (long long)n_x, (long long)n_y);
-    if (const int rc = centering_args("eccknn_topn_centered", centering, tx, sd, by)) return rc;
-    const int64_t n_users = user_based ? n_x : n_y, n_items = user_based ? n_y : n_x;
-    if (const int rc = n2v::topn_args("eccknn_topn_centered", n_owners, n_items, top_n, segments, seen_ptr, seen_i, n_seen, owners,
-                                      part_score, part_pos, items, score))
-        return rc;
-    if (!sim || !yr_ptr) return n2v::fail(N2V_ERR_INVALID, "eccknn_topn_centered: null pointer");
-    const int S = segments > 0 ? segments : n2v_topn_segments(n_owners, n_items);
-    TopnArgs a{KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k}, user_based ? 1 : 0, Seen{seen_ptr, seen_i, n_users, n_seen},
-               n_items, owners, top_n, S, global_mean, lo, hi, part_score, part_pos};
-    const Centering c{global_mean, user_based ? 1 : 0, tx, sd, by};
-    const dim3 grid((unsigned)n_owners, (unsigned)S);
-    hipStream_t s = (hipStream_t)stream;
-    if (centering == N2V_ECCKNN_CENTER_MEANS) eccknn_topn_kernel<N2V_ECCKNN_CENTER_MEANS><<<grid, 64, 0, s>>>(a, c);
-    else if (centering == N2V_ECCKNN_CENTER_ZSCORE) eccknn_topn_kernel<N2V_ECCKNN_CENTER_ZSCORE><<<grid, 64, 0, s>>>(a, c);
-    else eccknn_topn_kernel<N2V_ECCKNN_CENTER_BASELINE><<<grid, 64, 0, s>>>(a, c);
-    if (const int rc = n2v::check_launch("eccknn_topn_centered")) return rc;
-    return n2v::topn_merge("eccknn_topn_centered (merge)", part_score, part_pos, n_owners, S, top_n, items, score, s);
+    const Centred c{centering, Centering{global_mean, user_based ? 1 : 0, tx, sd, by}};
+    return topn_call("eccknn_topn_centered", "eccknn_topn_centered (merge)", KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, k, min_k},
+                     user_based, seen_ptr, seen_i, n_seen, owners, n_owners, global_mean, lo, hi, top_n, segments, &c,
+                     part_score, part_pos, items, score, stream);
 }
 
 int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,

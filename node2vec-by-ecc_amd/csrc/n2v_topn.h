@@ -1,6 +1,8 @@
-// Top-N lists of the rating predictors (n2v_eccknn.hip, n2v_svd.hip) — gfx950 (MI355X).  C-ABI: include/n2v_sim.h.
+// Top-N lists of the rating predictors (n2v_eccknn.hip, n2v_svd.hip, n2v_slopeone.hip) — gfx950 (MI355X).  C-ABI:
+// include/n2v_sim.h.
 //
-// What the two top-N kernels share: the fallback-and-clip of a prediction (also predict_kernel's), the cursor over the
+// What the top-N kernels share (eccknn_topn_kernel in its four centring modes, svd_topn_kernel, which NMF uses too, and
+// slope_topn_kernel): the fallback-and-clip of a prediction (also predict_kernel's), the cursor over the
 // items an owner has rated, the owner's best-N list in LDS under the one order of n2v_rank.h with the item id as the
 // position, and the merge of the S segment lists of an owner.  One wavefront (a 64-thread workgroup) per
 // (owner, segment of candidates); every value that steers control flow is the same in all 64 lanes.
@@ -88,7 +90,7 @@ topn_merge_kernel(const double* __restrict__ part_score, const int32_t* __restri
     merge_lists(part_score + o * S * N, part_pos + o * S * N, S, N, lane, items + o * N, score + o * N, -1);
 }
 
-// The argument checks the two top-N calls share; 0 or the error.
+// The argument checks every top-N call shares; 0 or the error.
 inline int topn_args(const char* who, int64_t n_owners, int64_t n_items, int32_t top_n, int32_t segments,
                      const void* seen_ptr, const void* seen_i, int64_t n_seen, const void* owners, const void* part_score,
                      const void* part_pos, const void* items, const void* score) {

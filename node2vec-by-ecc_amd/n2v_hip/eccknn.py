@@ -76,7 +76,13 @@ def _require_gpu():
         raise RuntimeError("n2v_hip.eccknn: no GPU visible (torch.cuda.is_available() is False); no CPU fallback")
 
 
+_PLAIN = object()                # in place of a Centering: the call that centres nothing
+
+
 def _first_appearance(raw):
+    """(inner id of every entry, {raw id: inner id}) in order of first appearance, for raw ids of any hashable kind, as
+    surprise takes them.  eccstats.first_appearance numbers the columns of a ratings file the same way through np.unique,
+    which is the faster of the two and holds for ids of one sortable type only; so there are two."""
     table, inner = {}, np.empty(len(raw), dtype=np.int64)
     for n, v in enumerate(raw):
         i = table.get(v)
@@ -84,6 +90,34 @@ def _first_appearance(raw):
             i = table[v] = len(table)
         inner[n] = i
     return inner, table
+
+
+def _to_device(a, dtype, dev):
+    """A host array (or list) as a contiguous tensor of `dtype` on `dev`."""
+    return torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
+
+
+def _csr_to_device(triple, dev):
+    """A host CSR triple (ptr, ids, r) as (int64, int32, fp64) tensors on `dev`."""
+    return tuple(_to_device(a, dt, dev) for a, dt in zip(triple, (torch.int64, torch.int32, torch.float64)))
+
+
+def _knn_options(k, min_k):
+    """(k, min_k) as every k-NN call takes them; host only."""
+    k, min_k = int(k), int(min_k)
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
+    if min_k < 1:
+        raise ValueError("min_k %d < 1" % min_k)
+    return k, min_k
+
+
+def _query_count(qx, qy, sides=("x", "y")):
+    """The number of queries of an estimate call: at least one, and as many on one side as on the other."""
+    n_q = qx.numel()
+    if n_q == 0 or qy.numel() != n_q:
+        raise ValueError("estimate: %d %s and %d %s queries: nothing to estimate" % (n_q, sides[0], qy.numel(), sides[1]))
+    return n_q
 
 
 def _csr(major, minor, r, n_major):
@@ -273,11 +307,9 @@ def baselines(trainset, bsl_options=None, device="cuda:0"):
     _require_gpu()
     dev = torch.device(device)
     lib = _lib.load()
-    to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
     ts = trainset
     with torch.cuda.device(dev):
-        ur = (to(ts.ur[0], torch.int64), to(ts.ur[1], torch.int32), to(ts.ur[2], torch.float64))
-        ir = (to(ts.ir[0], torch.int64), to(ts.ir[1], torch.int32), to(ts.ir[2], torch.float64))
+        ur, ir = _csr_to_device(ts.ur, dev), _csr_to_device(ts.ir, dev)
         bu = torch.empty(ts.n_users, dtype=torch.float64, device=dev)
         bi = torch.empty(ts.n_items, dtype=torch.float64, device=dev)
         _lib.check(lib.n2v_eccknn_baselines(_lib.ptr(ur[0]), _lib.ptr(ur[1]), _lib.ptr(ur[2]), ts.n_users, _lib.ptr(ir[0]),
@@ -350,25 +382,7 @@ def similarity_pearson_sparse(xr, n_y, name, w=None, min_support=1, global_mean=
 def estimate_batch(sim, yr, qx, qy, k, min_k):
     """(est fp64, actual_k int32, impossible uint8) device tensors.  yr: device CSR triple (ptr int64, x int32, r fp64);
     qx / qy: int32 device tensors, -1 = unknown."""
-    _require_gpu()
-    k, min_k = int(k), int(min_k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
-    if min_k < 1:
-        raise ValueError("min_k %d < 1" % min_k)
-    n_q = qx.numel()
-    if n_q == 0 or qy.numel() != n_q:
-        raise ValueError("estimate: %d x and %d y queries: nothing to estimate" % (n_q, qy.numel()))
-    dev = sim.device
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        est = torch.empty(n_q, dtype=torch.float64, device=dev)
-        actual_k = torch.empty(n_q, dtype=torch.int32, device=dev)
-        imp = torch.empty(n_q, dtype=torch.uint8, device=dev)
-        _lib.check(lib.n2v_eccknn_estimate(_lib.ptr(sim), sim.shape[0], _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]),
-                                           yr[0].numel() - 1, _lib.ptr(qx), _lib.ptr(qy), n_q, k, min_k, _lib.ptr(est),
-                                           _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
-    return est, actual_k, imp
+    return _estimate_batch(sim, yr, qx, qy, k, min_k, _PLAIN, False)
 
 
 # ---- centred k-NN: KNNWithMeans, KNNWithZScore, KNNBaseline -------------------------------------------------------------
@@ -430,34 +444,35 @@ def yr_check(yr, n_x):
         raise ValueError("yr: malformed lists: an x outside [0, %d)" % n_x)
 
 
-def estimate_batch_centered(sim, yr, qx, qy, k, min_k, centering, check=True):
-    """estimate_batch under a Centering (n2v_eccknn_estimate_centered): the same neighbours, centred sums.  Too few
-    neighbours is not impossible here (the estimate is the base alone); under "baseline" nothing is.  yr is checked first
-    (yr_check): a malformed list is a ValueError, not a launch.  check False: the caller has run yr_check on these lists."""
+def _estimate_batch(sim, yr, qx, qy, k, min_k, centering, check):
+    """The one body of estimate_batch (centering _PLAIN: n2v_eccknn_estimate) and estimate_batch_centered."""
     _require_gpu()
-    k, min_k = int(k), int(min_k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
-    if min_k < 1:
-        raise ValueError("min_k %d < 1" % min_k)
-    n_q = qx.numel()
-    if n_q == 0 or qy.numel() != n_q:
-        raise ValueError("estimate: %d x and %d y queries: nothing to estimate" % (n_q, qy.numel()))
+    k, min_k = _knn_options(k, min_k)
+    n_q = _query_count(qx, qy)
     n_x, n_y = sim.shape[0], yr[0].numel() - 1
-    code, tx, sd, by = _centering_args(centering, n_x, n_y)
-    if check:
-        yr_check(yr, n_x)
+    model = [_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y, _lib.ptr(qx), _lib.ptr(qy), n_q, k,
+             min_k]
+    if centering is not _PLAIN:
+        code, tx, sd, by = _centering_args(centering, n_x, n_y)
+        if check:
+            yr_check(yr, n_x)
+        model += [code, 1 if centering.user_based else 0, float(centering.global_mean), tx, sd, by]
     dev = sim.device
     lib = _lib.load()
     with torch.cuda.device(dev):
         est = torch.empty(n_q, dtype=torch.float64, device=dev)
         actual_k = torch.empty(n_q, dtype=torch.int32, device=dev)
         imp = torch.empty(n_q, dtype=torch.uint8, device=dev)
-        _lib.check(lib.n2v_eccknn_estimate_centered(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y,
-                                                    _lib.ptr(qx), _lib.ptr(qy), n_q, k, min_k, code,
-                                                    1 if centering.user_based else 0, float(centering.global_mean), tx, sd, by,
-                                                    _lib.ptr(est), _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
+        fn = lib.n2v_eccknn_estimate if centering is _PLAIN else lib.n2v_eccknn_estimate_centered
+        _lib.check(fn(*model, _lib.ptr(est), _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
     return est, actual_k, imp
+
+
+def estimate_batch_centered(sim, yr, qx, qy, k, min_k, centering, check=True):
+    """estimate_batch under a Centering (n2v_eccknn_estimate_centered): the same neighbours, centred sums.  Too few
+    neighbours is not impossible here (the estimate is the base alone); under "baseline" nothing is.  yr is checked first
+    (yr_check): a malformed list is a ValueError, not a launch.  check False: the caller has run yr_check on these lists."""
+    return _estimate_batch(sim, yr, qx, qy, k, min_k, centering, check)
 
 
 def predict(est, impossible, global_mean, rating_scale, r_true=None):
@@ -516,11 +531,42 @@ def _topn_inputs(seen, n_users, n_items, owners, dev):
     return owners
 
 
-def _topn_buffers(n_owners, S, n, dev):
-    return (torch.empty((n_owners, S, n), dtype=torch.float64, device=dev),
-            torch.empty((n_owners, S, n), dtype=torch.int32, device=dev),
-            torch.empty((n_owners, n), dtype=torch.int32, device=dev),
-            torch.empty((n_owners, n), dtype=torch.float64, device=dev))
+def _topn_call(fn, head, mid, tail, seen, n_users, n_items, owners, global_mean, rating_scale, n, segments, dev):
+    """What the top_n of every predictor does after its own checks: the checked seen CSR and owners, the segment count,
+    the buffers, and the one C call fn(*head, seen, owners, *mid, fallback, scale, n, S, *tail, buffers, stream),
+    where fn is the library's function and head, mid and tail are the model's own arguments.  n and segments are topn_options'."""
+    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
+    lib = _lib.load()
+    n_owners, n_seen = owners.numel(), seen[1].numel()
+    S = segments or int(lib.n2v_topn_segments(n_owners, n_items))
+    with torch.cuda.device(dev):
+        part_score = torch.empty((n_owners, S, n), dtype=torch.float64, device=dev)
+        part_pos = torch.empty((n_owners, S, n), dtype=torch.int32, device=dev)
+        items = torch.empty((n_owners, n), dtype=torch.int32, device=dev)
+        score = torch.empty((n_owners, n), dtype=torch.float64, device=dev)
+        _lib.check(fn(*head, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None, n_seen, _lib.ptr(owners), n_owners,
+                      *mid, float(global_mean), float(rating_scale[0]), float(rating_scale[1]), n, S, *tail,
+                      _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score), _lib.stream_ptr(dev)))
+    return items, score
+
+
+def _top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, owners, segments, centering, check):
+    """The one body of top_n (centering _PLAIN: n2v_eccknn_topn) and top_n_centered."""
+    n, segments = topn_options(n, segments)
+    _require_gpu()
+    k, min_k = _knn_options(k, min_k)
+    n_x, n_y = sim.shape[0], yr[0].numel() - 1
+    tail = []
+    if centering is not _PLAIN:
+        tail = list(_centering_args(centering, n_x, n_y))
+        user_based, global_mean = bool(centering.user_based), centering.global_mean
+        if check:
+            yr_check(yr, n_x)
+    n_users, n_items = (n_x, n_y) if user_based else (n_y, n_x)
+    head = [_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y, 1 if user_based else 0]
+    fn = _lib.load().n2v_eccknn_topn if centering is _PLAIN else _lib.load().n2v_eccknn_topn_centered
+    return _topn_call(fn, head, [k, min_k], tail, seen, n_users, n_items, owners, global_mean, rating_scale, n, segments,
+                      sim.device)
 
 
 def top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, owners=None, segments=None):
@@ -530,76 +576,27 @@ def top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, own
     seen: the owner-major CSR csr_by_x(u, i, r, n_users, n_items) of the training ratings; it is checked first and a
     malformed one is a ValueError.  owners None: every user.  segments None: the library's choice; the result does not
     depend on it."""
-    n, segments = topn_options(n, segments)
-    _require_gpu()
-    k, min_k = int(k), int(min_k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
-    if min_k < 1:
-        raise ValueError("min_k %d < 1" % min_k)
-    n_x, n_y = sim.shape[0], yr[0].numel() - 1
-    n_users, n_items = (n_x, n_y) if user_based else (n_y, n_x)
-    dev = sim.device
-    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
-    lib = _lib.load()
-    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
-    with torch.cuda.device(dev):
-        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, dev)
-        n_seen = seen[1].numel()
-        _lib.check(lib.n2v_eccknn_topn(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y,
-                                       1 if user_based else 0, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None,
-                                       n_seen, _lib.ptr(owners), owners.numel(), k, min_k, float(global_mean),
-                                       float(rating_scale[0]), float(rating_scale[1]), n, S, _lib.ptr(part_score),
-                                       _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score), _lib.stream_ptr(dev)))
-    return items, score
+    return _top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, owners, segments, _PLAIN, False)
 
 
 def top_n_centered(sim, yr, seen, k, min_k, rating_scale, n, centering, owners=None, segments=None, check=True):
     """top_n under a Centering (n2v_eccknn_topn_centered): every prediction the bits of estimate_batch_centered + predict.
     user_based and global_mean are the centering's.  Under "baseline" an unknown owner's items score global_mean + bi[i],
     clipped, and so are ranked by it.  yr is checked first as estimate_batch_centered checks it."""
-    n, segments = topn_options(n, segments)
-    _require_gpu()
-    k, min_k = int(k), int(min_k)
-    if not 1 <= k <= MAX_K:
-        raise ValueError("k %d outside [1, %d]" % (k, MAX_K))
-    if min_k < 1:
-        raise ValueError("min_k %d < 1" % min_k)
-    n_x, n_y = sim.shape[0], yr[0].numel() - 1
-    code, tx, sd, by = _centering_args(centering, n_x, n_y)
-    user_based = bool(centering.user_based)
-    n_users, n_items = (n_x, n_y) if user_based else (n_y, n_x)
-    if check:
-        yr_check(yr, n_x)
-    dev = sim.device
-    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
-    lib = _lib.load()
-    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
-    with torch.cuda.device(dev):
-        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, dev)
-        n_seen = seen[1].numel()
-        _lib.check(lib.n2v_eccknn_topn_centered(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y,
-                                                1 if user_based else 0, _lib.ptr(seen[0]),
-                                                _lib.ptr(seen[1]) if n_seen else None, n_seen, _lib.ptr(owners),
-                                                owners.numel(), k, min_k, float(centering.global_mean),
-                                                float(rating_scale[0]), float(rating_scale[1]), n, S, code, tx, sd, by,
-                                                _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score),
-                                                _lib.stream_ptr(dev)))
-    return items, score
+    return _top_n(sim, yr, seen, None, k, min_k, None, rating_scale, n, owners, segments, centering, check)
 
 
 class TopN:
     """What the fitted rating predictors share above their top-N kernel: raw ids in, lists or metrics out.  A subclass
-    has self.trainset after fit and implements _top_n(owners, n, segments) and _device()."""
+    has self.trainset after fit and implements _top_n(owners, n, segments) and _device() (Predictor's, below)."""
 
     def _seen(self):
         """The owner-major CSR of the training ratings on the device, built once per fit."""
         ts = self.trainset
         if getattr(self, "_seen_of", None) is not ts:
             dev = self._device()
-            to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
-            self._seen_csr = csr_by_x(to(ts.u, torch.int32), to(ts.i, torch.int32), to(ts.r, torch.float64), ts.n_users,
-                                      ts.n_items)
+            self._seen_csr = csr_by_x(_to_device(ts.u, torch.int32, dev), _to_device(ts.i, torch.int32, dev),
+                                      _to_device(ts.r, torch.float64, dev), ts.n_users, ts.n_items)
             self._seen_of = ts
         return self._seen_csr
 
@@ -642,11 +639,51 @@ class TopN:
         return rec.averages(per_user) + (per_user,)
 
 
+class Predictor(TopN):
+    """What the fitted rating predictors share around their estimate kernel: raw test triples in, predictions out.  A
+    subclass implements _estimate_batch(qx, qy) -> (est, *extras, impossible) device tensors and names in _MODEL a tensor
+    of the fitted model (the predictor lives on its device); an item-based k-NN says _swapped(): its x are the items."""
+    _MODEL = None
+
+    def _swapped(self):
+        return False
+
+    def _device(self):
+        return getattr(self, self._MODEL).device
+
+    def _queries(self, u, i):
+        """Inner user and item ids (-1 = unknown) as the int32 device pair _estimate_batch takes."""
+        u, i = _to_device(u, torch.int32, self._device()), _to_device(i, torch.int32, self._device())
+        return (i, u) if self._swapped() else (u, i)
+
+    def _test(self, testset):
+        """testset: (raw user, raw item, true rating) triples -> (pred, *extras, impossible, rmse)."""
+        testset = list(testset)
+        if not testset:
+            raise ValueError("test: empty testset")
+        ts = self.trainset
+        qx, qy = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
+        est, *extras, imp = self._estimate_batch(qx, qy)
+        r_true = _to_device(np.array([t[2] for t in testset], dtype=np.float64), torch.float64, self._device())
+        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
+        return (pred, *extras, imp, err)
+
+    def test(self, testset):
+        """Arrays (est, *extras, was_impossible): est after the global-mean fallback and clipping; the extras are
+        actual_k for a k-NN, n_deviations for SlopeOne, none for the factor models."""
+        pred, *extras, imp, _ = self._test(testset)
+        return (pred.cpu().numpy(), *[e.cpu().numpy() for e in extras], imp.cpu().numpy().astype(bool))
+
+    def rmse(self, testset):
+        return self._test(testset)[-1]
+
+
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
 
-class _SymmetricKNN(TopN):
+class _SymmetricKNN(Predictor):
     """What EccenKNN and KNNBasic share: the options, the weights, the device fit and estimate / test / rmse.  A subclass
     names its similarities (_check_name) and may add to them (_similarity)."""
+    _MODEL = "sim"
 
     def __init__(self, k=40, min_k=1, sim_options=None, device="cuda:0"):
         self.k, self.min_k = int(k), int(min_k)
@@ -655,10 +692,7 @@ class _SymmetricKNN(TopN):
         self.device = device
         name = self.sim_options.get("name", "msd").lower()
         self._check_name(name)
-        if not 1 <= self.k <= MAX_K:
-            raise ValueError("k %d outside [1, %d]" % (self.k, MAX_K))
-        if self.min_k < 1:
-            raise ValueError("min_k %d < 1" % self.min_k)
+        _knn_options(self.k, self.min_k)
         self.name = name
         self.form = self.sim_options.get("form", "auto")
         if self.form not in FORMS:
@@ -694,21 +728,18 @@ class _SymmetricKNN(TopN):
         x, y, yr = (ts.u, ts.i, ts.ir) if user_based else (ts.i, ts.u, ts.ur)
         self.n_x, self.n_y = (ts.n_users, ts.n_items) if user_based else (ts.n_items, ts.n_users)
         self.trainset = ts
-        to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
         form = choose_form(self.n_x, self.n_y, self.form, int(_lib.load().n2v_eccknn_max_dense()))
-        dx, dy, dr = to(x, torch.int32), to(y, torch.int32), to(ts.r, torch.float64)
-        dw = None if w is None else to(w, torch.float64)
+        dx, dy, dr = _to_device(x, torch.int32, dev), _to_device(y, torch.int32, dev), _to_device(ts.r, torch.float64, dev)
+        dw = None if w is None else _to_device(w, torch.float64, dev)
         if form == "dense":
             self.sim = self._similarity(densify(dx, dy, dr, self.n_x, self.n_y), None, dw)
         else:
             self.sim = self._similarity(None, csr_by_x(dx, dy, dr, self.n_x, self.n_y), dw)
-        self.yr = (to(yr[0], torch.int64), to(yr[1], torch.int32), to(yr[2], torch.float64))
+        self.yr = _csr_to_device(yr, dev)
         return self
 
-    def _queries(self, u, i):
-        u = torch.as_tensor(np.asarray(u)).to(device=self.sim.device, dtype=torch.int32).contiguous()
-        i = torch.as_tensor(np.asarray(i)).to(device=self.sim.device, dtype=torch.int32).contiguous()
-        return (u, i) if self.sim_options["user_based"] else (i, u)
+    def _swapped(self):
+        return not self.sim_options["user_based"]
 
     def _estimate_batch(self, qx, qy):
         return estimate_batch(self.sim, self.yr, qx, qy, self.k, self.min_k)
@@ -721,29 +752,6 @@ class _SymmetricKNN(TopN):
         if int(imp.item()):
             raise PredictionImpossible("Not enough neighbors.")
         return float(est.item()), {"actual_k": int(ak.item())}
-
-    def _test(self, testset):
-        """testset: (raw user, raw item, true rating) triples."""
-        testset = list(testset)
-        if not testset:
-            raise ValueError("test: empty testset")
-        ts = self.trainset
-        qx, qy = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
-        est, ak, imp = self._estimate_batch(qx, qy)
-        r_true = torch.as_tensor(np.array([t[2] for t in testset], dtype=np.float64)).to(self.sim.device)
-        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
-        return pred, ak, imp, err
-
-    def test(self, testset):
-        """Arrays (est, actual_k, was_impossible): est after the global-mean fallback and clipping."""
-        pred, ak, imp, _ = self._test(testset)
-        return pred.cpu().numpy(), ak.cpu().numpy(), imp.cpu().numpy().astype(bool)
-
-    def rmse(self, testset):
-        return self._test(testset)[3]
-
-    def _device(self):
-        return self.sim.device
 
     def _top_n(self, owners, n, segments):
         ts = self.trainset
@@ -825,8 +833,7 @@ class _CenteredKNN(KNNBasic):
         ts = self.trainset
         xr = ts.ur if self.sim_options["user_based"] else ts.ir
         dev = torch.device(self.device)
-        return (torch.as_tensor(np.ascontiguousarray(xr[0])).to(device=dev, dtype=torch.int64),
-                torch.as_tensor(np.ascontiguousarray(xr[2])).to(device=dev, dtype=torch.float64))
+        return _to_device(xr[0], torch.int64, dev), _to_device(xr[2], torch.float64, dev)
 
     def _estimate_batch(self, qx, qy):
         return estimate_batch_centered(self.sim, self.yr, qx, qy, self.k, self.min_k, self.centering, check=False)
@@ -863,7 +870,7 @@ class KNNWithZScore(_CenteredKNN):
     def _tables(self):
         ptr_, r = self._x_rows()
         dev = r.device
-        all_r = torch.as_tensor(np.ascontiguousarray(self.trainset.r)).to(device=dev, dtype=torch.float64)
+        all_r = _to_device(self.trainset.r, torch.float64, dev)
         one_row = torch.tensor([0, all_r.numel()], dtype=torch.int64, device=dev)
         self.overall_sigma = float(row_moments(one_row, all_r)[1].item())
         self.means, self.sigmas = row_moments(ptr_, r, zero_sigma=self.overall_sigma)

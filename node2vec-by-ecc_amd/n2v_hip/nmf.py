@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eccknn import PredictionImpossible, _require_gpu  # noqa: F401  (PredictionImpossible: what estimate raises)
+from .eccknn import PredictionImpossible  # noqa: F401  (what estimate raises)
+from .eccknn import _csr_to_device, _require_gpu, _to_device
 from .svd import MAX_FACTORS, SVD
 
 LISTS_BAD = ((1, "a ptr does not start at 0, is not monotone or leaves [0, n]"), (2, "a ptr does not end at n"),
@@ -166,14 +167,12 @@ class NMF(SVD):
         _require_gpu()
         dev = torch.device(self.device)
         ts = self.trainset = trainset
-        to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
         rng = np.random.RandomState(self.random_state)
         pu = rng.uniform(self.init_low, self.init_high, (ts.n_users, self.n_factors))
         qi = rng.uniform(self.init_low, self.init_high, (ts.n_items, self.n_factors))
         with torch.cuda.device(dev):
-            ur = to(ts.ur[0], torch.int64), to(ts.ur[1], torch.int32), to(ts.ur[2], torch.float64)
-            self.lists = lists(ur, ts.n_users, ts.n_items)
-            self.pu, self.qi = to(pu, torch.float64), to(qi, torch.float64)
+            self.lists = lists(_csr_to_device(ts.ur, dev), ts.n_users, ts.n_items)
+            self.pu, self.qi = _to_device(pu, torch.float64, dev), _to_device(qi, torch.float64, dev)
             pu_out, qi_out = torch.empty_like(self.pu), torch.empty_like(self.qi)
             for _ in range(self.n_epochs):
                 epoch(self.lists, self.reg_pu, self.reg_qi, self.pu, self.qi, pu_out, qi_out)

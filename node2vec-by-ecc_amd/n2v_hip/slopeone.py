@@ -15,12 +15,11 @@ for a user and 64 neighbouring candidates every rated item contributes one conti
 
 Everything is fp64.  There is no CPU fallback.
 """
-import numpy as np
 import torch
 
 from . import _lib
-from .eccknn import (PredictionImpossible, TopN, _require_gpu, _topn_buffers, _topn_inputs, choose_form, csr_by_x, csr_check,
-                     densify, predict, row_moments, topn_options, yr_check, FORMS)
+from .eccknn import (PredictionImpossible, Predictor, _csr_to_device, _query_count, _require_gpu, _to_device, _topn_call,
+                     choose_form, csr_by_x, csr_check, densify, row_moments, topn_options, yr_check, FORMS)
 
 MAX_TABLE = 1 << 31              # elements of dev: n_items * n_items
 
@@ -95,9 +94,7 @@ def estimate_batch(dev, freq, ur, user_mean, qu, qi, check=True):
     """(est fp64, n_deviations int32, impossible uint8) device tensors for int32 device queries, -1 = unknown
     (n2v_slopeone_estimate)."""
     _require_gpu()
-    n_q = qu.numel()
-    if n_q == 0 or qi.numel() != n_q:
-        raise ValueError("estimate: %d user and %d item queries: nothing to estimate" % (n_q, qi.numel()))
+    n_q = _query_count(qu, qi, ("user", "item"))
     model = _model_args(dev, freq, ur, user_mean, check)
     d = dev.device
     with torch.cuda.device(d):
@@ -115,26 +112,16 @@ def top_n(dev, freq, ur, user_mean, seen, global_mean, rating_scale, n, owners=N
     n, segments = topn_options(n, segments)
     _require_gpu()
     model = _model_args(dev, freq, ur, user_mean, check)
-    n_items, n_users = model[2], model[5]
-    d = dev.device
-    owners = _topn_inputs(seen, n_users, n_items, owners, d)
-    lib = _lib.load()
-    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
-    with torch.cuda.device(d):
-        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, d)
-        n_seen = seen[1].numel()
-        _lib.check(lib.n2v_slopeone_topn(*model, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None, n_seen,
-                                         _lib.ptr(owners), owners.numel(), float(global_mean), float(rating_scale[0]),
-                                         float(rating_scale[1]), n, S, _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items),
-                                         _lib.ptr(score), _lib.stream_ptr(d)))
-    return items, score
+    return _topn_call(_lib.load().n2v_slopeone_topn, model, [], [], seen, model[5], model[2], owners, global_mean, rating_scale, n,
+                      segments, dev.device)
 
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
 
-class SlopeOne(TopN):
+class SlopeOne(Predictor):
     """surprise's SlopeOne, plus sim_options["form"] and device.  fit(trainset) takes an eccknn.Trainset; afterwards dev
     (fp64), freq (int32) [n_items][n_items] and user_mean (fp64[n_users]) are device tensors."""
+    _MODEL = "dev"
 
     def __init__(self, sim_options=None, device="cuda:0"):
         self.sim_options = dict(sim_options or {})
@@ -153,50 +140,25 @@ class SlopeOne(TopN):
         _require_gpu()
         d = torch.device(self.device)
         self.trainset = ts
-        to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=d, dtype=dt)
-        di, du, dr = to(ts.i, torch.int32), to(ts.u, torch.int32), to(ts.r, torch.float64)
+        di, du, dr = _to_device(ts.i, torch.int32, d), _to_device(ts.u, torch.int32, d), _to_device(ts.r, torch.float64, d)
         if form == "dense":
             self.dev, self.freq = deviations(*densify(di, du, dr, ts.n_items, ts.n_users))
         else:
             self.dev, self.freq = deviations_sparse(csr_by_x(di, du, dr, ts.n_items, ts.n_users), ts.n_users)
-        self.ur = (to(ts.ur[0], torch.int64), to(ts.ur[1], torch.int32), to(ts.ur[2], torch.float64))
+        self.ur = _csr_to_device(ts.ur, d)
         yr_check(self.ur, ts.n_items)
         self.user_mean = row_moments(self.ur[0], self.ur[2])[0]
         return self
 
-    def _queries(self, u, i):
-        to = lambda a: torch.as_tensor(np.asarray(a)).to(device=self.dev.device, dtype=torch.int32).contiguous()
-        return to(u), to(i)
+    def _estimate_batch(self, qu, qi):
+        return estimate_batch(self.dev, self.freq, self.ur, self.user_mean, qu, qi, check=False)
 
     def estimate(self, u, i):
         """(est, {'n_deviations': n}) for inner ids u, i; PredictionImpossible for an unknown one, as surprise raises it."""
         if not (self.trainset.knows_user(u) and self.trainset.knows_item(i)):
             raise PredictionImpossible("User and/or item is unkown.")
-        est, n_dev, _ = estimate_batch(self.dev, self.freq, self.ur, self.user_mean, *self._queries([u], [i]), check=False)
+        est, n_dev, _ = self._estimate_batch(*self._queries([u], [i]))
         return float(est.item()), {"n_deviations": int(n_dev.item())}
-
-    def _test(self, testset):
-        """testset: (raw user, raw item, true rating) triples."""
-        testset = list(testset)
-        if not testset:
-            raise ValueError("test: empty testset")
-        ts = self.trainset
-        qu, qi = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
-        est, n_dev, imp = estimate_batch(self.dev, self.freq, self.ur, self.user_mean, qu, qi, check=False)
-        r_true = torch.as_tensor(np.array([t[2] for t in testset], dtype=np.float64)).to(self.dev.device)
-        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
-        return pred, n_dev, imp, err
-
-    def test(self, testset):
-        """Arrays (est, n_deviations, was_impossible): est after the global-mean fallback and clipping."""
-        pred, n_dev, imp, _ = self._test(testset)
-        return pred.cpu().numpy(), n_dev.cpu().numpy(), imp.cpu().numpy().astype(bool)
-
-    def rmse(self, testset):
-        return self._test(testset)[3]
-
-    def _device(self):
-        return self.dev.device
 
     def _top_n(self, owners, n, segments):
         ts = self.trainset

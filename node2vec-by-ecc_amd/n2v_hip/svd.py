@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eccknn import PredictionImpossible, TopN, _require_gpu, _topn_buffers, _topn_inputs, predict, topn_options
+from .eccknn import PredictionImpossible, Predictor, _query_count, _require_gpu, _to_device, _topn_call, topn_options
 
 MAX_FACTORS = 256                # n2v_svd_max_factors()
 MAX_STRATA = 32768               # n2v_svd_max_strata()
@@ -128,9 +128,7 @@ def epoch(blocks, mu, biased, rates, bu, bi, pu, qi):
 def estimate_batch(mu, biased, bu, bi, pu, qi, qu, qi_ids):
     """(est fp64, impossible uint8) device tensors for int32 device queries, -1 = unknown (n2v_svd_estimate)."""
     _require_gpu()
-    n_q = qu.numel()
-    if n_q == 0 or qi_ids.numel() != n_q:
-        raise ValueError("estimate: %d user and %d item queries: nothing to estimate" % (n_q, qi_ids.numel()))
+    n_q = _query_count(qu, qi_ids, ("user", "item"))
     dev = pu.device
     lib = _lib.load()
     with torch.cuda.device(dev):
@@ -149,26 +147,18 @@ def top_n(mu, biased, bu, bi, pu, qi, seen, global_mean, rating_scale, n, owners
     n, segments = topn_options(n, segments)
     _require_gpu()
     n_users, n_items = pu.shape[0], qi.shape[0]
-    dev = pu.device
-    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
-    lib = _lib.load()
-    S = segments or int(lib.n2v_topn_segments(owners.numel(), n_items))
-    with torch.cuda.device(dev):
-        part_score, part_pos, items, score = _topn_buffers(owners.numel(), S, n, dev)
-        n_seen = seen[1].numel()
-        _lib.check(lib.n2v_svd_topn(_lib.ptr(bu), _lib.ptr(bi), _lib.ptr(pu), _lib.ptr(qi), n_users, n_items, pu.shape[1],
-                                    float(mu), 1 if biased else 0, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None,
-                                    n_seen, _lib.ptr(owners), owners.numel(), float(global_mean), float(rating_scale[0]),
-                                    float(rating_scale[1]), n, S, _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items),
-                                    _lib.ptr(score), _lib.stream_ptr(dev)))
-    return items, score
+    head = [_lib.ptr(bu), _lib.ptr(bi), _lib.ptr(pu), _lib.ptr(qi), n_users, n_items, pu.shape[1], float(mu),
+            1 if biased else 0]
+    return _topn_call(_lib.load().n2v_svd_topn, head, [], [], seen, n_users, n_items, owners, global_mean, rating_scale, n, segments,
+                      pu.device)
 
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
 
-class SVD(TopN):
+class SVD(Predictor):
     """surprise's SVD with its options and defaults, plus n_strata (an integer, or "auto": auto_strata) and device.
     fit(trainset) takes an eccknn.Trainset; afterwards bu, bi, pu, qi are device fp64 tensors."""
+    _MODEL = "pu"
 
     def __init__(self, n_factors=100, n_epochs=20, biased=True, init_mean=0, init_std_dev=0.1, lr_all=0.005, reg_all=0.02,
                  lr_bu=None, lr_bi=None, lr_pu=None, lr_qi=None, reg_bu=None, reg_bi=None, reg_pu=None, reg_qi=None,
@@ -204,56 +194,31 @@ class SVD(TopN):
         self.mu = float(ts.global_mean) if self.biased else 0.0
         # all_ratings(): the users ascending, each one's ratings in training order; that is the ur lists, concatenated
         u = np.repeat(np.arange(ts.n_users, dtype=np.int64), np.diff(ts.ur[0]))
-        to = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=dev, dtype=dt)
         rng = np.random.RandomState(self.random_state)
         pu = rng.normal(self.init_mean, self.init_std_dev, (ts.n_users, self.n_factors))
         qi = rng.normal(self.init_mean, self.init_std_dev, (ts.n_items, self.n_factors))
         with torch.cuda.device(dev):
-            lists = build_blocks(to(u, torch.int64), to(ts.ur[1], torch.int64), to(ts.ur[2], torch.float64), ts.n_users,
-                                 ts.n_items, P)
+            lists = build_blocks(_to_device(u, torch.int64, dev), _to_device(ts.ur[1], torch.int64, dev),
+                                 _to_device(ts.ur[2], torch.float64, dev), ts.n_users, ts.n_items, P)
             self.blocks = Blocks(lists, ts.n_users, ts.n_items, P)
             self.bu = torch.zeros(ts.n_users, dtype=torch.float64, device=dev)
             self.bi = torch.zeros(ts.n_items, dtype=torch.float64, device=dev)
-            self.pu, self.qi = to(pu, torch.float64), to(qi, torch.float64)
+            self.pu, self.qi = _to_device(pu, torch.float64, dev), _to_device(qi, torch.float64, dev)
             for _ in range(self.n_epochs):
                 epoch(self.blocks, self.mu, self.biased, self.rates, self.bu, self.bi, self.pu, self.qi)
         return self
 
-    def _queries(self, u, i):
-        to = lambda a: torch.as_tensor(np.asarray(a)).to(device=self.pu.device, dtype=torch.int32).contiguous()
-        return to(u), to(i)
+    def _estimate_batch(self, qu, qi_ids):
+        return estimate_batch(self.mu, self.biased, self.bu, self.bi, self.pu, self.qi, qu, qi_ids)
 
     def estimate(self, u, i):
         """est for inner ids u, i (anything else is unknown); PredictionImpossible as surprise raises it."""
         ts = self.trainset
         qu, qi_ids = self._queries([u if ts.knows_user(u) else -1], [i if ts.knows_item(i) else -1])
-        est, imp = estimate_batch(self.mu, self.biased, self.bu, self.bi, self.pu, self.qi, qu, qi_ids)
+        est, imp = self._estimate_batch(qu, qi_ids)
         if int(imp.item()):
             raise PredictionImpossible("User and item are unknown.")
         return float(est.item())
-
-    def _test(self, testset):
-        """testset: (raw user, raw item, true rating) triples."""
-        testset = list(testset)
-        if not testset:
-            raise ValueError("test: empty testset")
-        ts = self.trainset
-        qu, qi_ids = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
-        est, imp = estimate_batch(self.mu, self.biased, self.bu, self.bi, self.pu, self.qi, qu, qi_ids)
-        r_true = torch.as_tensor(np.array([t[2] for t in testset], dtype=np.float64)).to(self.pu.device)
-        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
-        return pred, imp, err
-
-    def test(self, testset):
-        """Arrays (est, was_impossible): est after the global-mean fallback and clipping."""
-        pred, imp, _ = self._test(testset)
-        return pred.cpu().numpy(), imp.cpu().numpy().astype(bool)
-
-    def rmse(self, testset):
-        return self._test(testset)[2]
-
-    def _device(self):
-        return self.pu.device
 
     def _top_n(self, owners, n, segments):
         ts = self.trainset

@@ -254,9 +254,7 @@ def test_symbols_are_declared_and_bound():
     hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     new = {"n2v_cbow_max_sentence", "n2v_cbow_corpus_check", "n2v_cbow_train"}
     assert new <= set(re.findall(r"\b(n2v_[a-z0-9_]+)\s*\(", hdr)) and new <= set(_lib.SIGNATURES)
-    for name in new:
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr).group(1).strip()
-        assert len(_lib.SIGNATURES[name][1]) == (0 if params == "void" else params.count(",") + 1), name
+    # (that each binding has the header's parameters, type by type: tests/test_host_logic.py)
     lib = _lib.load()
     assert all(hasattr(lib, name) for name in new)
     assert lib.n2v_cbow_max_sentence() == 4096 == corpus.MAX_SENTENCE

@@ -110,6 +110,19 @@ def test_trainset_ids_and_order():
     assert ts2.global_mean == E.global_mean(big)
 
 
+def test_trainset_takes_any_hashable_raw_id():
+    """Raw ids are dictionary keys, as surprise's are: numbers, strings, tuples and None may share a column, 1 and "1" are
+    two users, and nothing is coerced to a common type."""
+    from n2v_hip import eccknn
+    users = [1, "a", 2, (1, 2), None, "1", 1]
+    items = ["x", "x", 7, (7,), 7, "7", 7]
+    ts = eccknn.Trainset.from_ratings(users, items, [1.0, 2.0, 3.0, 4.0, 5.0, 1.5, 2.5])
+    assert ts.u.tolist() == [0, 1, 2, 3, 4, 5, 0] and ts.i.tolist() == [0, 0, 1, 2, 1, 3, 1]
+    assert (ts.n_users, ts.n_items) == (6, 4)
+    assert ts.inner_uids([1, 2, (1, 2), None, "1", "2"]).tolist() == [0, 2, 3, 4, 5, -1]
+    assert ts.to_inner_iid((7,)) == 2 and ts.to_inner_iid("7") == 3 and ts.to_inner_iid(7) == 1
+
+
 def test_error_paths():
     from n2v_hip import eccknn
     with pytest.raises(NameError, match=r"Wrong sim name jaccard\. Allowed values are cosine, msd, pearson, pearson_baseline\."):

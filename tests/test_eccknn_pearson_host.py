@@ -152,9 +152,7 @@ def test_symbols_are_declared_and_bound():
     declared = set(re.findall(r"\b(n2v_[a-z0-9_]+)\s*\(", hdr))
     new = {"n2v_eccknn_baselines", "n2v_eccknn_pearson", "n2v_eccknn_pearson_sparse"}
     assert new <= declared and new <= set(_lib.SIGNATURES)
-    for name in new:
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr).group(1)
-        assert len(_lib.SIGNATURES[name][1]) == params.count(",") + 1, name
+    # (that each binding has the header's parameters, type by type: tests/test_host_logic.py)
     lib = _lib.load()
     assert all(hasattr(lib, name) for name in new)
     from n2v_hip import eccknn

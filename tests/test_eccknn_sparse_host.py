@@ -59,11 +59,7 @@ def test_sparse_symbols_are_declared_and_bound():
     declared = set(re.findall(r"\b(n2v_[a-z0-9_]+)\s*\(", hdr))
     new = {"n2v_eccknn_sparse_chunk", "n2v_eccknn_csr_check", "n2v_eccknn_sim_sparse"}
     assert new <= declared and new <= set(_lib.SIGNATURES)
-    # one ctypes argument per declared parameter
-    for name in new:
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr).group(1)
-        n_params = 0 if params.strip() == "void" else params.count(",") + 1
-        assert len(_lib.SIGNATURES[name][1]) == n_params, name
+    # (that each binding has the header's parameters, type by type: tests/test_host_logic.py)
     for bit, macro in ((1, "N2V_ECCKNN_CSR_BAD_PTR"), (2, "N2V_ECCKNN_CSR_BAD_Y"), (4, "N2V_ECCKNN_CSR_UNSORTED")):
         assert re.search(r"#define %s %d\b" % (macro, bit), hdr)
     from n2v_hip import eccknn

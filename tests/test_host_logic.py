@@ -104,6 +104,33 @@ def test_abi_exports_every_declared_symbol():
     assert _lib.load().n2v_abi_version() == int(re.search(r"#define N2V_ABI_VERSION (\d+)", hdr).group(1))
 
 
+def test_abi_signatures_match_the_declared_types():
+    """Every declaration of the three headers, type by type: the return type and each parameter's C type map to the
+    ctypes type the binding gives them (any pointer -> c_void_p, except a returned `const char*` -> c_char_p), so a
+    parameter that changes its width or its place fails here and not in a call."""
+    from n2v_hip import _lib
+    hdr = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("n2v_hip.h", "n2v_bine.h", "n2v_sim.h"))
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    scalars = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double,
+               "float": ctypes.c_float, "int": ctypes.c_int}
+
+    def ctype(decl, returned=False):
+        words = decl.replace("*", " * ").split()
+        if "*" in words:
+            return ctypes.c_char_p if returned and words == ["const", "char", "*"] else ctypes.c_void_p
+        return scalars[[w for w in words if w != "const"][0]]   # a parameter's name, if it has one, follows its type
+
+    protos = re.findall(r"^([A-Za-z_][\w \*]*?)\b(n2v_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr, flags=re.M)
+    assert len(protos) == len({name for _, name, _ in protos}) and {name for _, name, _ in protos} == set(_lib.SIGNATURES)
+    for ret, name, params in protos:
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is ctype(ret, returned=True), name
+        assert len(argtypes) == len(params), name
+        for at, (got, p) in enumerate(zip(argtypes, params)):
+            assert got is ctype(p), "%s: parameter %d, `%s`" % (name, at, " ".join(p.split()))
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

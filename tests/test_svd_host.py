@@ -280,9 +280,7 @@ def test_symbols_are_declared_and_bound():
     declared = set(re.findall(r"\b(n2v_[a-z0-9_]+)\s*\(", hdr))
     new = {"n2v_svd_max_factors", "n2v_svd_max_strata", "n2v_svd_blocks_check", "n2v_svd_epoch", "n2v_svd_estimate"}
     assert new <= declared and new <= set(_lib.SIGNATURES)
-    for name in new:
-        params = re.search(r"\b%s\s*\(([^)]*)\)" % name, hdr).group(1).strip()
-        assert len(_lib.SIGNATURES[name][1]) == (0 if params == "void" else params.count(",") + 1), name
+    # (that each binding has the header's parameters, type by type: tests/test_host_logic.py)
     lib = _lib.load()
     assert all(hasattr(lib, name) for name in new)
     from n2v_hip import svd
