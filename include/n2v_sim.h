@@ -397,6 +397,66 @@ int n2v_slopeone_topn(const double* dev, const int32_t* freq, int64_t n_items, c
                       int32_t top_n, int32_t segments, double* part_score, int32_t* part_pos, int32_t* items, double* score,
                       void* stream);
 
+/* ---- Co-clustering: surprise's CoClustering in surprise's own order (csrc/n2v_cocl.hip) ---------------------------------
+ * surprise 1.0.6's CoClustering (George and Merugu 2005).  surprise is not a dependency: the algorithm below is restated
+ * from memory, parity with surprise itself is UNPINNED, and tests/coclustering_reference.py is the definition the kernels
+ * equal bit for bit.  Everything is fp64 without fused multiply-add, as written, left to right.  (A NaN's sign and payload
+ * are not part of the contract.)  Every user is in one of n_cltr_u clusters (cltr_u int32[n_users]), every item in one of
+ * n_cltr_i (cltr_i int32[n_items]), 1 <= n_cltr_u, n_cltr_i <= n2v_cocl_max_clusters() = 64: one lane holds one cluster.
+ * A list is (ptr int64[n_rows + 1], other int32[n], r fp64[n]), row k being [ptr[k], ptr[k + 1]), in training order
+ * (Trainset.ur / Trainset.ir).  user_mean fp64[n_users] / item_mean fp64[n_items]: n2v_eccknn_row_moments over them.
+ * The averages: int64 counts and fp64 sums per user cluster, item cluster and co-cluster; an empty one's average is
+ * global_mean, any other sum / (double)count.  DEVIATION from surprise, deliberate: surprise adds each sum as one chain
+ * over all ratings; here the sums are grouped by user row.  For user u over ur[u] in list order, from +0.0:
+ *   t_u = t_u + r;  s_u[ic] = s_u[ic] + r  with ic = cltr_i[i]
+ * then over the users in ascending inner id, for every ic (an s_u[ic] nothing was added to is +0.0):
+ *   sum_cltr_u[cltr_u[u]] += t_u;  sum_cltr_i[ic] += s_u[ic];  sum_cocltr[cltr_u[u]][ic] += s_u[ic]
+ * so a chain is n_users long, not n long; where every sum is exact (ratings that are multiples of 1/2) the two orders
+ * give the same bytes.  One assignment pass, for every row of one side and every candidate cluster c of that side, over
+ * the row's list in list order from +0.0 (user side: row u, c = uc, ic = cltr_i[i]; item side: row i, c = ic,
+ * uc = cltr_u[u]):
+ *   est = (((avg_cocltr[uc][ic] + user_mean[u]) - avg_cltr_u[uc]) + item_mean[i]) - avg_cltr_i[ic]
+ *   d = r - est;  errors[c] = errors[c] + d * d
+ * and the row takes numpy's argmin of errors: the first index holding a NaN if there is one, else the first index of the
+ * minimum; an empty list leaves cluster 0.  An epoch is the averages, the user pass, then the item pass over the
+ * assignment the user pass wrote and the SAME averages.
+ * No kernel indexes with a value it has not checked: a row range is clamped to [0, n]; an entry whose id is outside its
+ * range, or whose cluster (its own, or in n2v_cocl_averages its user's) is outside [0, n_cltr), adds nothing, so a
+ * malformed list or assignment is no out-of-bounds access.                                                              */
+int32_t n2v_cocl_max_clusters(void);
+/* The three average tables of an assignment, a clear and two launches: one wavefront per user writes part (the caller's scratch,
+ * fp64[n_users][n_cltr_i + 1]: s_u, then t_u) and adds its counts to count_cocltr (int64[n_cltr_u][n_cltr_i], cleared by
+ * the call; integer atomics); then one wavefront per table row runs the chains over the users and writes its averages:
+ * avg_cltr_u fp64[n_cltr_u], avg_cltr_i fp64[n_cltr_i], avg_cocltr fp64[n_cltr_u][n_cltr_i].  n >= 0.                  */
+int n2v_cocl_averages(const int64_t* ur_ptr, const int32_t* ur_i, const double* ur_r, int64_t n_users, int64_t n_items, int64_t n,
+                      const int32_t* cltr_u, const int32_t* cltr_i, int32_t n_cltr_u, int32_t n_cltr_i, double global_mean,
+                      double* part, double* avg_cltr_u, double* avg_cltr_i, double* avg_cocltr, int64_t* count_cocltr,
+                      void* stream);
+/* One assignment pass of one side, one launch, one wavefront per row.  user_side != 0: the list is the user-major one
+ * (other = items), cltr_i is read and cltr_u written; user_side == 0: the item-major one, cltr_u read and cltr_i written.
+ * order int32[n_rows]: the row the k-th wavefront takes (a permutation; longest lists first is the fast one; NULL: the
+ * identity); it changes no bit.  cltr_u and cltr_i must not overlap, else N2V_ERR_INVALID before any launch.  n >= 0.  */
+int n2v_cocl_assign(const int64_t* ptr, const int32_t* other, const double* r, const int32_t* order, int64_t n_users,
+                    int64_t n_items, int64_t n, int32_t user_side, int32_t n_cltr_u, int32_t n_cltr_i, const double* user_mean,
+                    const double* item_mean, const double* avg_cltr_u, const double* avg_cltr_i, const double* avg_cocltr,
+                    int32_t* cltr_u, int32_t* cltr_i, void* stream);
+/* One query per lane (q_u[q], q_i[q]); an id outside its range (-1) is unknown.  Both known: the expression above with the
+ * fitted clusters; only the user: user_mean[u]; only the item: item_mean[i]; neither: global_mean.  impossible = 0 always.
+ * Before any clipping: n2v_eccknn_predict does that.  n_q >= 1.                                                        */
+int n2v_cocl_estimate(const int32_t* cltr_u, const int32_t* cltr_i, const double* avg_cltr_u, const double* avg_cltr_i,
+                      const double* avg_cocltr, const double* user_mean, const double* item_mean, int64_t n_users,
+                      int64_t n_items, int32_t n_cltr_u, int32_t n_cltr_i, double global_mean, const int32_t* q_u,
+                      const int32_t* q_i, int64_t n_q, double* est, uint8_t* impossible, void* stream);
+/* The top-N lists of the section above with n2v_cocl_estimate's value as the score, by the same device function and so by
+ * the same bits: one wavefront per (owner, segment), 64 neighbouring candidates at a time, one a lane.  An unknown owner
+ * scores every item at its clipped item_mean.  Owners, seen_*, top_n, segments, the scratch and the outputs as
+ * n2v_eccknn_topn.                                                                                                      */
+int n2v_cocl_topn(const int32_t* cltr_u, const int32_t* cltr_i, const double* avg_cltr_u, const double* avg_cltr_i,
+                  const double* avg_cocltr, const double* user_mean, const double* item_mean, int64_t n_users, int64_t n_items,
+                  int32_t n_cltr_u, int32_t n_cltr_i, const int64_t* seen_ptr, const int32_t* seen_i, int64_t n_seen,
+                  const int32_t* owners, int64_t n_owners, double global_mean, double lo, double hi, int32_t top_n,
+                  int32_t segments, double* part_score, int32_t* part_pos, int32_t* items, double* score, void* stream);
+
 /* ---- Eccentricity statistics: the ir / ie / ire / ier item weights and the per-user ue (csrc/n2v_eccstats.hip) -----
  * Replaces src/utils.py:53-153 (pandas group-bys and merges).  Rows are (user, item, feedback, timewindow) with inner
  * ids; a group is a distinct (item, timewindow) pair, numbered in ascending (item, timewindow) order.  Everything is

@@ -9,6 +9,8 @@ plain k-NN (surprise's KNNBasic) it is compared against.
                        [-unbiased] [-test-ratio 0.2] [-seed 0] [-cv N]
     python main_rec.py -input ratings.csv -algo nmf [-factors 15] [-epochs 50] [-reg 0.06] [-test-ratio 0.2] [-seed 0] [-cv N]
     python main_rec.py -input ratings.csv -algo slopeone [-form auto|dense|sparse] [-test-ratio 0.2] [-seed 0] [-cv N]
+    python main_rec.py -input ratings.csv -algo coclustering [-clusters-u 3] [-clusters-i 3] [-epochs 20] [-test-ratio 0.2]
+                       [-seed 0] [-cv N]
     every form:        [-topn N [-threshold T] [-save-recs FILE]]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
@@ -34,6 +36,12 @@ plain k-NN (surprise's KNNBasic) it is compared against.
           the similarities (n2v_hip.slopeone), and a prediction is the user's mean plus the mean difference to the items
           they rated.  It has no hyper-parameter and no random state: beside the split, -topn and -device flags it takes
           -form alone, and none of -k, -mink, -sim, -shrinkage, -weights, -mode, -item-based and the factor flags.
+          coclustering: surprise's CoClustering (restated; parity with surprise is unpinned): users and items are each
+          put into clusters, and a prediction is the co-cluster's average plus what the user's and the item's mean differ
+          from their clusters' averages; trained on the device in surprise's own order of the ratings, every user and then
+          every item reassigned in parallel (n2v_hip.coclustering).  -clusters-u, -clusters-i and -epochs are surprise's
+          n_cltr_u, n_cltr_i (1 .. 64 each) and n_epochs, and -seed also seeds the first assignment.  It takes none of
+          the k-NN flags, -form, -shrinkage, -factors, -lr, -reg, -strata and -unbiased.
           svd itself is not built: surprise's order of the ratings is sequential, and -algo mf follows it only with -strata 1.
 -weights  `id,weight` lines for the y side (items, or users with -item-based); absent = all ones, which is plain k-NN.
 -mode     derive the item weights on the device instead (n2v_hip.eccstats; the reference's src/utils.py:95-153): item
@@ -88,6 +96,8 @@ def parse_args(argv=None):
     p.add_argument("-reg", type=float, default=None)
     p.add_argument("-strata", default=None)
     p.add_argument("-unbiased", action="store_true")
+    p.add_argument("-clusters-u", dest="clusters_u", type=int, default=None)
+    p.add_argument("-clusters-i", dest="clusters_i", type=int, default=None)
     p.add_argument("-device", default="cuda:0")
     p.add_argument("-topn", type=int, default=None)
     p.add_argument("-threshold", type=float, default=None)
@@ -107,17 +117,27 @@ def parse_args(argv=None):
     if a.algo == "svd":
         p.error("-algo svd is not built: surprise's SVD applies the ratings in one sequential order.  -algo mf is the same "
                 "model and update under a deterministic stratified order (equal to surprise's only with -strata 1)")
-    if a.algo not in ("eccen", "mf", "nmf", "slopeone") + KNN_ALGOS:
-        p.error("-algo %s: eccen, %s, mf, nmf or slopeone" % (a.algo, ", ".join(KNN_ALGOS)))
+    if a.algo not in ("eccen", "mf", "nmf", "slopeone", "coclustering") + KNN_ALGOS:
+        p.error("-algo %s: eccen, %s, mf, nmf, slopeone or coclustering" % (a.algo, ", ".join(KNN_ALGOS)))
     knn_flags = (("-sim", a.sim), ("-k", a.k), ("-mink", a.mink), ("-weights", a.weights), ("-mode", a.mode),
                  ("-item-based", a.item_based or None), ("-form", a.form))
     mf_flags = (("-factors", a.factors), ("-epochs", a.epochs), ("-lr", a.lr), ("-reg", a.reg), ("-strata", a.strata),
                 ("-unbiased", a.unbiased or None))
     sgd_flags = tuple(f for f in mf_flags if f[0] in ("-lr", "-strata", "-unbiased"))     # what mf has and nmf has not
     slope_flags = tuple(f for f in knn_flags if f[0] != "-form") + (("-shrinkage", a.shrinkage),) + mf_flags   # all but -form
-    for flag, v in {"mf": knn_flags, "nmf": knn_flags + sgd_flags, "slopeone": slope_flags}.get(a.algo, mf_flags):
+    cocl_flags = tuple(f for f in knn_flags + (("-shrinkage", a.shrinkage),) + mf_flags if f[0] != "-epochs")   # all but -epochs
+    cluster_flags = (("-clusters-u", a.clusters_u), ("-clusters-i", a.clusters_i))
+    refused = {"mf": knn_flags, "nmf": knn_flags + sgd_flags, "slopeone": slope_flags, "coclustering": cocl_flags}
+    for flag, v in refused.get(a.algo, mf_flags) + (() if a.algo == "coclustering" else cluster_flags):
         if v is not None:
             p.error("%s does not go with -algo %s" % (flag, a.algo))
+    if a.algo == "coclustering":
+        from n2v_hip import coclustering
+        a.clusters_u, a.clusters_i = (3 if v is None else v for v in (a.clusters_u, a.clusters_i))
+        try:
+            coclustering.CoClustering(n_cltr_u=a.clusters_u, n_cltr_i=a.clusters_i, n_epochs=20 if a.epochs is None else a.epochs)
+        except ValueError as e:
+            p.error(str(e))
     factor_defaults = (("factors", 15), ("epochs", 50), ("reg", 0.06)) if a.algo == "nmf" else ()
     for name, v in factor_defaults + (("shrinkage", 100), ("k", 40), ("mink", 1), ("sim", "cosine"), ("form", "auto"),
                                       ("factors", 100), ("epochs", 20), ("lr", 0.005), ("reg", 0.02), ("strata", "auto")):
@@ -259,6 +279,11 @@ def fit_split(args, users, items, ratings, weights, train):
     if args.algo == "slopeone":
         from n2v_hip import slopeone
         return slopeone.SlopeOne(sim_options={"form": args.form}, device=args.device).fit(ts)
+    if args.algo == "coclustering":
+        from n2v_hip import coclustering
+        algo = coclustering.CoClustering(n_cltr_u=args.clusters_u, n_cltr_i=args.clusters_i, n_epochs=args.epochs,
+                                         random_state=args.seed, device=args.device)
+        return algo.fit(ts)
     sim_options = {"name": args.sim, "user_based": not args.item_based, "min_support": args.min_support, "form": args.form}
     if args.algo in KNN_ALGOS:
         sim_options["shrinkage"] = args.shrinkage

@@ -153,6 +153,15 @@ SIGNATURES = {
                                         _ptr]),
     "n2v_slopeone_topn": (C.c_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _f64, _f64,
                                     _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_cocl_max_clusters": (C.c_int32, []),
+    "n2v_cocl_averages": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _i32, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                    _ptr]),
+    "n2v_cocl_assign": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                  _ptr, _ptr]),
+    "n2v_cocl_estimate": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _i32, _f64, _ptr, _ptr, _i64, _ptr,
+                                    _ptr, _ptr]),
+    "n2v_cocl_topn": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _i32, _ptr, _ptr, _i64, _ptr, _i64,
+                                _f64, _f64, _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_eccstats_log_table":(C.c_int, [_i64, _ptr]),
     "n2v_eccstats_groups_scratch": (C.c_int64, [_i64]),
     "n2v_eccstats_groups": (C.c_int, [_ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
