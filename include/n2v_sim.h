@@ -235,6 +235,38 @@ int n2v_eccknn_estimate_centered(const double* sim, int64_t n_x, const int64_t* 
 int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const double* r_true, int64_t n_q, double global_mean,
                        double lo, double hi, double* pred, double* rmse, void* stream);
 
+/* ---- k-NN sweep: every (k, min_k) of a grid from one neighbour selection (csrc/n2v_eccknn.hip) --------------------------
+ * The reference's experiment varies -k and -mink over the same similarities and the same queries.  The prefix argument:
+ * the selection list is kept in a total order (sim descending, list position ascending, NaN last), so the selection for k
+ * is the first k entries of the selection for any larger k; the sums that follow are sequential in rank order, so the sums
+ * for k are a prefix of the sums for the largest k, the same adds in the same order; and min_k enters only in the finish.
+ * Hence one selection at ks[n_k - 1] and one walk down it give every cell, and cell (j, m) holds exactly what
+ * n2v_eccknn_estimate (n2v_eccknn_estimate_centered) gives for k = ks[j], min_k = min_ks[m], bit for bit.
+ * ks: int32[n_k], min_ks: int32[n_m]: HOST arrays, read during the call and passed to the kernel by value; both strictly
+ * ascending, 1 <= n_k, n_m <= N2V_ECCKNN_MAX_SWEEP, 1 <= ks[j] <= N2V_ECCKNN_MAX_K, min_ks[m] >= 1.  The outputs are
+ * cell-major, a cell being a contiguous column over the queries:
+ *   est: fp64[n_k][n_m][n_q], impossible: uint8[n_k][n_m][n_q], actual_k: int32[n_k][n_q] (it does not depend on min_k).
+ * One wavefront per query; everything else as the single-cell calls, whose argument rules hold.  A bad grid, a NULL
+ * output or a bad table of the centred call is N2V_ERR_INVALID before any launch.                                      */
+#define N2V_ECCKNN_MAX_SWEEP 16   /* values a side of the grid                                                           */
+int n2v_eccknn_estimate_sweep(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                              int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, const int32_t* ks, int32_t n_k,
+                              const int32_t* min_ks, int32_t n_m, double* est, int32_t* actual_k, uint8_t* impossible,
+                              void* stream);
+int n2v_eccknn_estimate_sweep_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x,
+                                       const double* yr_r, int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q,
+                                       const int32_t* ks, int32_t n_k, const int32_t* min_ks, int32_t n_m, int32_t centering,
+                                       int32_t user_based, double global_mean, const double* tx, const double* sd,
+                                       const double* by, double* est, int32_t* actual_k, uint8_t* impossible, void* stream);
+
+/* The two error measures of surprise's cross_validate over the columns of pred: fp64[n_cols][n_q] against r_true: fp64[n_q],
+ * one workgroup per column, both sums taken in query order by one thread:
+ *   rmse[c] = sqrt(sum((r_true - pred)^2) / n_q), the bits n2v_eccknn_predict gives for that column;
+ *   mae[c]  = sum(|r_true - pred|) / n_q.
+ * rmse, mae: fp64[n_cols]; either may be NULL, not both.  n_q >= 1, 1 <= n_cols < 2^31.                                   */
+int n2v_eccknn_errors(const double* pred, const double* r_true, int64_t n_q, int64_t n_cols, double* rmse, double* mae,
+                      void* stream);
+
 /* ---- Matrix factorisation: surprise's SVD under a deterministic stratified schedule (csrc/n2v_svd.hip) --------------
  * The third algorithm of src/main_rec.py:341-348 (`-algo svd`, surprise 1.0.6's SVD).  surprise is not a dependency: the
  * model and the update below are its arithmetic restated from memory, parity with surprise itself is UNPINNED, and

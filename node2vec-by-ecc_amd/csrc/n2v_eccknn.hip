@@ -36,9 +36,15 @@
 //                    knn_estimate: none (EccenKNN, KNNBasic: n2v_eccknn_estimate), or the row mean, the z-score or the
 //                    baseline of surprise's KNNWithMeans / KNNWithZScore / KNNBaseline (n2v_eccknn_estimate_centered):
 //                    the same selection, three more fp64 gathers per kept neighbour, no more LDS.
+//   estimate_sweep_kernel one wavefront per query: every (k, min_k) cell of a grid from one selection at the largest k.
+//                    The list's order is total, so the selection for k is its first k entries and the rank-order sums for
+//                    k are a prefix of the sums for the largest k; knn_estimate is split into knn_unknown, knn_select,
+//                    knn_sums and knn_finish, and the sweep runs the selection once, the sums from one k of the grid to
+//                    the next, and the finish per min_k.  The grid travels in the kernel's arguments.
 //   row_moments_kernel one wavefront per row: the mean and the population sigma of a row's ratings, each sum in list order.
 //   predict_kernel   one workgroup: global-mean fallback, clip to the rating scale, and the squared errors added one
 //                    after the other in query order (rmse).
+//   errors_kernel    one workgroup per column of predictions: rmse and mae, both sums in query order as predict_kernel's.
 //   eccknn_topn_kernel one wavefront per (owner, segment of the items): the owner's unseen items ascending, each through
 //                    the same knn_estimate and predict_value as the two kernels above, folded into a best-N list in LDS;
 //                    nothing of size owners x items is stored.  The S segment lists of an owner are merged under the
@@ -541,28 +547,37 @@ struct Centering {
 // s * (r - mu[x2]), s * ((r - mu[x2]) / sd[x2]) or s * (r - ((gm + bx[x2]) + by[y])); fewer than min_k of them zero
 // sum_ratings instead of making the estimate impossible; est = base [+ sum_ratings / sum_sim [* sd[x]]] with base mu[x] or
 // (gm + bu[u]) + bi[i].  Under the baseline mode nothing is impossible: an unknown user or item drops its bias.
+// The four steps of an estimate, each in one copy: knn_unknown, knn_select, knn_sums, knn_finish.  knn_estimate is the four
+// in a row; knn_estimate_sweep runs the selection once at the largest k of a grid and the other steps per cell.
+
+// True when x or y is unknown, which settles the estimate without a neighbour: est and imp are it.
 template <int MODE>
-__device__ __forceinline__ bool knn_estimate(const KnnModel& a, const Centering& c, int64_t x, int64_t y, double* ls,
-                                             int32_t* lp, int lane, double& est, int& n_pos) {
-    est = 0.0; n_pos = 0;
-    if (MODE == N2V_ECCKNN_CENTER_BASELINE) {
-        const bool kx = x >= 0 && x < a.n_x, ky = y >= 0 && y < a.n_y;
-        if (!(kx && ky)) {                                        // the user's bias first, whichever side x is
-            double e = c.gm;
-            if (c.user_based) { if (kx) e = e + c.tx[x]; if (ky) e = e + c.by[y]; }
-            else { if (ky) e = e + c.by[y]; if (kx) e = e + c.tx[x]; }
-            est = e;
-            return false;
-        }
+__device__ __forceinline__ bool knn_unknown(const KnnModel& a, const Centering& c, int64_t x, int64_t y, double& est,
+                                            bool& imp) {
+    est = 0.0; imp = false;
+    const bool kx = x >= 0 && x < a.n_x, ky = y >= 0 && y < a.n_y;
+    if (kx && ky) return false;
+    if (MODE == N2V_ECCKNN_CENTER_BASELINE) {                         // the user's bias first, whichever side x is
+        double e = c.gm;
+        if (c.user_based) { if (kx) e = e + c.tx[x]; if (ky) e = e + c.by[y]; }
+        else { if (ky) e = e + c.by[y]; if (kx) e = e + c.tx[x]; }
+        est = e;
     } else {
-        if (x < 0 || x >= a.n_x || y < 0 || y >= a.n_y) return true; // 'User and/or item is unkown.'
+        imp = true;                                               // 'User and/or item is unkown.'
     }
-    const int k = a.k;
+    return true;
+}
+
+// The selection: the best k of the raters of y under the order of n2v_rank.h, in ls / lp in rank order.  Returns L, the
+// length of y's list (beg: where it starts); the first min(L, k) entries of the list are real, the others fillers.  The
+// order is total, so the first k2 < k entries are what a selection with k2 would have kept.
+__device__ __forceinline__ int knn_select(const KnnModel& a, int k, int64_t x, int64_t y, double* ls, int32_t* lp, int lane,
+                                          int64_t& beg) {
     __syncthreads();                                              // the previous estimate's list has been read
     // the list starts as k entries (NaN, POS_NONE): below any real entry, so it is always "full"
     for (int i = lane; i < k; i += 64) { ls[i] = __builtin_nan(""); lp[i] = POS_NONE; }
     __syncthreads();
-    const int64_t beg = a.yr_ptr[y];
+    beg = a.yr_ptr[y];
     const int64_t len64 = a.yr_ptr[y + 1] - beg;
     const int L = (int)(len64 < POS_NONE ? len64 : POS_NONE - 1);
     const double* srow = a.sim + x * a.n_x;
@@ -585,15 +600,20 @@ __device__ __forceinline__ bool knn_estimate(const KnnModel& a, const Centering&
             if (beats(ck, cp, tk, tp)) list_insert(ls, lp, k, cs, cp, ck, lane, tk, tp);
         }
     }
-    // rank order: `for (sim, r) in k_neighbors: if sim > 0: ...`; every lane runs the same sums
-    double sum_sim = 0.0, sum_ratings = 0.0;
-    int actual_k = 0;
-    const int n_sel = L < k ? L : k;
-    const double pby = MODE == N2V_ECCKNN_CENTER_BASELINE ? c.by[y] : 0.0;
-    for (int base = 0; base < n_sel; base += 64) {
+    return L;
+}
+
+// Ranks [from, to) of the selection added to the sums, to <= min(L, k): `for (sim, r) in k_neighbors: if sim > 0: ...`.
+// Every lane runs the same sums, one add after the other in rank order, so the sums over [0, to) are the same bits in
+// however many calls the range is walked.  pby: by[y] under the baseline mode.
+template <int MODE>
+__device__ __forceinline__ void knn_sums(const KnnModel& a, const Centering& c, int64_t beg, int L, double pby,
+                                         const double* ls, const int32_t* lp, int lane, int from, int to, double& sum_sim,
+                                         double& sum_ratings, int& actual_k) {
+    for (int base = from; base < to; base += 64) {
         const int i = base + lane;
         double s = 0.0, sr = 0.0;
-        if (i < n_sel) {
+        if (i < to) {
             const int p = lp[i];
             if (p < L) {                                          // always: a filler is below every real entry
                 if (MODE == C_NONE) {
@@ -615,19 +635,24 @@ __device__ __forceinline__ bool knn_estimate(const KnnModel& a, const Centering&
                 }
             }
         }
-        const int cnt = n_sel - base < 64 ? n_sel - base : 64;
+        const int cnt = to - base < 64 ? to - base : 64;
         for (int j = 0; j < cnt; ++j) {
             const double sj = __shfl(s, j, 64), tj = __shfl(sr, j, 64);
             if (sj > 0) { sum_sim = sum_sim + sj; sum_ratings = sum_ratings + tj; ++actual_k; }
         }
     }
-    n_pos = actual_k;
+}
+
+// The finish of the mode for one min_k; true: the estimate is impossible (est = 0).
+template <int MODE>
+__device__ __forceinline__ bool knn_finish(const Centering& c, int64_t x, double pby, int min_k, double sum_sim,
+                                           double sum_ratings, int actual_k, double& est) {
     if (MODE == C_NONE) {
-        const bool imp = actual_k < a.min_k;                      // 'Not enough neighbors.'
+        const bool imp = actual_k < min_k;                        // 'Not enough neighbors.'
         est = imp ? 0.0 : sum_ratings / sum_sim;
         return imp;
     }
-    if (actual_k < a.min_k) sum_ratings = 0.0;                    // too few neighbours: the base alone, not impossible
+    if (actual_k < min_k) sum_ratings = 0.0;                      // too few neighbours: the base alone, not impossible
     double b;
     if (MODE == N2V_ECCKNN_CENTER_BASELINE) b = c.user_based ? (c.gm + c.tx[x]) + pby : (c.gm + pby) + c.tx[x];
     else b = c.tx[x];
@@ -635,6 +660,22 @@ __device__ __forceinline__ bool knn_estimate(const KnnModel& a, const Centering&
     else if (MODE == N2V_ECCKNN_CENTER_ZSCORE) est = b + (sum_ratings / sum_sim) * c.sd[x];
     else est = b + sum_ratings / sum_sim;
     return false;
+}
+
+template <int MODE>
+__device__ __forceinline__ bool knn_estimate(const KnnModel& a, const Centering& c, int64_t x, int64_t y, double* ls,
+                                             int32_t* lp, int lane, double& est, int& n_pos) {
+    n_pos = 0;
+    bool imp;
+    if (knn_unknown<MODE>(a, c, x, y, est, imp)) return imp;
+    int64_t beg;
+    const int L = knn_select(a, a.k, x, y, ls, lp, lane, beg);
+    double sum_sim = 0.0, sum_ratings = 0.0;
+    int actual_k = 0;
+    const double pby = MODE == N2V_ECCKNN_CENTER_BASELINE ? c.by[y] : 0.0;
+    knn_sums<MODE>(a, c, beg, L, pby, ls, lp, lane, 0, L < a.k ? L : a.k, sum_sim, sum_ratings, actual_k);
+    n_pos = actual_k;
+    return knn_finish<MODE>(c, x, pby, a.min_k, sum_sim, sum_ratings, actual_k, est);
 }
 
 struct EstArgs {
@@ -652,6 +693,61 @@ __global__ void __launch_bounds__(64) estimate_kernel(EstArgs a, Centering c) {
     int actual_k;
     const bool imp = knn_estimate<MODE>(a.m, c, a.qx[q], a.qy[q], ls, lp, lane, est, actual_k);
     if (lane == 0) { a.est[q] = est; a.actual_k[q] = actual_k; a.impossible[q] = imp ? 1 : 0; }
+}
+
+// The grid of a sweep travels by value: ks and min_ks strictly ascending, m.k = ks[n_k - 1], m.min_k unused.
+struct SweepArgs {
+    KnnModel m; const int32_t* qx; const int32_t* qy; int64_t n_q;
+    int n_k, n_m; int ks[N2V_ECCKNN_MAX_SWEEP], min_ks[N2V_ECCKNN_MAX_SWEEP];
+    double* est; int32_t* actual_k; uint8_t* impossible;         // [n_k][n_m][n_q], [n_k][n_q], [n_k][n_m][n_q]
+};
+
+// Every (ks[j], min_ks[m]) cell of query q from one selection at the largest k: the list is walked once, rank
+// min(L, ks[j - 1]) to min(L, ks[j]) for j = 0, 1, ..., and where the walk stands at min(L, ks[j]) the sums are those of
+// knn_estimate with k = ks[j] (knn_select, knn_sums), so every min_k is finished from them and written; nothing is kept.
+template <int MODE>
+__device__ __forceinline__ void knn_estimate_sweep(const SweepArgs& a, const Centering& c, int64_t q, double* ls,
+                                                   int32_t* lp, int lane) {
+    const int64_t x = a.qx[q], y = a.qy[q];
+    double est;
+    bool imp;
+    if (knn_unknown<MODE>(a.m, c, x, y, est, imp)) {
+        if (lane == 0) {
+            for (int j = 0; j < a.n_k; ++j) {
+                a.actual_k[j * a.n_q + q] = 0;
+                for (int m = 0; m < a.n_m; ++m) {
+                    const int64_t o = ((int64_t)j * a.n_m + m) * a.n_q + q;
+                    a.est[o] = est; a.impossible[o] = imp ? 1 : 0;
+                }
+            }
+        }
+        return;
+    }
+    int64_t beg;
+    const int L = knn_select(a.m, a.m.k, x, y, ls, lp, lane, beg);
+    double sum_sim = 0.0, sum_ratings = 0.0;
+    int actual_k = 0, from = 0;
+    const double pby = MODE == N2V_ECCKNN_CENTER_BASELINE ? c.by[y] : 0.0;
+    for (int j = 0; j < a.n_k; ++j) {
+        const int to = L < a.ks[j] ? L : a.ks[j];
+        knn_sums<MODE>(a.m, c, beg, L, pby, ls, lp, lane, from, to, sum_sim, sum_ratings, actual_k);
+        from = to;
+        if (lane == 0) a.actual_k[j * a.n_q + q] = actual_k;
+        for (int m = 0; m < a.n_m; ++m) {
+            imp = knn_finish<MODE>(c, x, pby, a.min_ks[m], sum_sim, sum_ratings, actual_k, est);
+            if (lane == 0) {
+                const int64_t o = ((int64_t)j * a.n_m + m) * a.n_q + q;
+                a.est[o] = est; a.impossible[o] = imp ? 1 : 0;
+            }
+        }
+    }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(64) estimate_sweep_kernel(SweepArgs a, Centering c) {
+    __shared__ double ls[N2V_ECCKNN_MAX_K];
+    __shared__ int32_t lp[N2V_ECCKNN_MAX_K];
+    knn_estimate_sweep<MODE>(a, c, blockIdx.x, ls, lp, threadIdx.x);
 }
 
 // ---- top-N ------------------------------------------------------------------------------------------------------------
@@ -718,6 +814,31 @@ __global__ void __launch_bounds__(256) predict_kernel(const double* __restrict__
         }
     }
     if (r_true && threadIdx.x == 0) rmse[0] = sqrt(acc / (double)n);
+}
+
+// ---- rmse and mae of columns ------------------------------------------------------------------------------------------
+
+// One workgroup per column of pred[n_cols][n]; the sums as predict_kernel takes its own, so rmse[c] is its value.
+__global__ void __launch_bounds__(256) errors_kernel(const double* __restrict__ pred, const double* __restrict__ r_true,
+                                                     int64_t n, double* __restrict__ rmse, double* __restrict__ mae) {
+    __shared__ double sq[256];
+    __shared__ double ab[256];
+    const double* col = pred + (int64_t)blockIdx.x * n;
+    double acc = 0.0, aab = 0.0;                                  // thread 0's; test order
+    for (int64_t base = 0; base < n; base += 256) {
+        const int64_t i = base + threadIdx.x;
+        if (i < n) { const double d = r_true[i] - col[i]; sq[threadIdx.x] = d * d; ab[threadIdx.x] = fabs(d); }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int cnt = n - base < 256 ? (int)(n - base) : 256;
+            for (int j = 0; j < cnt; ++j) { acc = acc + sq[j]; aab = aab + ab[j]; }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (rmse) rmse[blockIdx.x] = sqrt(acc / (double)n);
+        if (mae) mae[blockIdx.x] = aab / (double)n;
+    }
 }
 
 }  // namespace
@@ -857,17 +978,53 @@ static void with_centering(const Centred* c, F f) {
     }
 }
 
-// n2v_eccknn_estimate (c NULL) and n2v_eccknn_estimate_centered.
-static int estimate_call(const char* who, const KnnModel& m, const int32_t* qx, const int32_t* qy, int64_t n_q,
-                         const Centred* c, double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
-    if (const int rc = knn_options(who, m.k, m.min_k)) return rc;
+// What the single-cell and the sweep estimate calls check after their k and min_k; 0 or the error.
+static int estimate_args(const char* who, const KnnModel& m, const int32_t* qx, const int32_t* qy, int64_t n_q,
+                         const Centred* c, const double* est, const int32_t* actual_k, const uint8_t* impossible) {
     if (n_q < 1 || n_q > 0x7fffffff) return n2v::fail(N2V_ERR_INVALID, "%s: n_q %lld outside [1, 2^31)", who, (long long)n_q);
     if (m.n_x < 1 || m.n_y < 1) return n2v::fail(N2V_ERR_INVALID, "%s: n_x=%lld n_y=%lld", who, (long long)m.n_x, (long long)m.n_y);
     if (c) if (const int rc = centering_args(who, *c)) return rc;
     if (!m.sim || !m.yr_ptr || !qx || !qy || !est || !actual_k || !impossible) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer", who);
+    return N2V_OK;
+}
+
+// n2v_eccknn_estimate (c NULL) and n2v_eccknn_estimate_centered.
+static int estimate_call(const char* who, const KnnModel& m, const int32_t* qx, const int32_t* qy, int64_t n_q,
+                         const Centred* c, double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
+    if (const int rc = knn_options(who, m.k, m.min_k)) return rc;
+    if (const int rc = estimate_args(who, m, qx, qy, n_q, c, est, actual_k, impossible)) return rc;
     const EstArgs a{m, qx, qy, n_q, est, actual_k, impossible};
     with_centering(c, [&](auto mode, const Centering& t) {
         estimate_kernel<decltype(mode)::value><<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a, t);
+    });
+    return n2v::check_launch(who);
+}
+
+// n2v_eccknn_estimate_sweep (c NULL) and n2v_eccknn_estimate_sweep_centered.  ks and min_ks are host arrays.
+static int sweep_call(const char* who, KnnModel m, const int32_t* qx, const int32_t* qy, int64_t n_q, const int32_t* ks,
+                      int32_t n_k, const int32_t* min_ks, int32_t n_m, const Centred* c, double* est, int32_t* actual_k,
+                      uint8_t* impossible, void* stream) {
+    if (n_k < 1 || n_k > N2V_ECCKNN_MAX_SWEEP || n_m < 1 || n_m > N2V_ECCKNN_MAX_SWEEP)
+        return n2v::fail(N2V_ERR_INVALID, "%s: n_k %d or n_m %d outside [1, %d]", who, n_k, n_m, N2V_ECCKNN_MAX_SWEEP);
+    if (!ks || !min_ks) return n2v::fail(N2V_ERR_INVALID, "%s: null pointer (ks, min_ks: host arrays)", who);
+    SweepArgs a{};
+    for (int j = 0; j < n_k; ++j) {
+        if (const int rc = knn_options(who, ks[j], 1)) return rc;
+        if (j && ks[j] <= ks[j - 1]) return n2v::fail(N2V_ERR_INVALID, "%s: ks not strictly ascending (%d after %d)", who, ks[j], ks[j - 1]);
+        a.ks[j] = ks[j];
+    }
+    for (int j = 0; j < n_m; ++j) {
+        if (const int rc = knn_options(who, 1, min_ks[j])) return rc;
+        if (j && min_ks[j] <= min_ks[j - 1])
+            return n2v::fail(N2V_ERR_INVALID, "%s: min_ks not strictly ascending (%d after %d)", who, min_ks[j], min_ks[j - 1]);
+        a.min_ks[j] = min_ks[j];
+    }
+    if (const int rc = estimate_args(who, m, qx, qy, n_q, c, est, actual_k, impossible)) return rc;
+    m.k = ks[n_k - 1]; m.min_k = min_ks[0];
+    a.m = m; a.qx = qx; a.qy = qy; a.n_q = n_q; a.n_k = n_k; a.n_m = n_m;
+    a.est = est; a.actual_k = actual_k; a.impossible = impossible;
+    with_centering(c, [&](auto mode, const Centering& t) {
+        estimate_sweep_kernel<decltype(mode)::value><<<(unsigned)n_q, 64, 0, (hipStream_t)stream>>>(a, t);
     });
     return n2v::check_launch(who);
 }
@@ -1035,6 +1192,24 @@ int n2v_eccknn_estimate_centered(const double* sim, int64_t n_x, const int64_t* 
                          est, actual_k, impossible, stream);
 }
 
+int n2v_eccknn_estimate_sweep(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x, const double* yr_r,
+                              int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q, const int32_t* ks, int32_t n_k,
+                              const int32_t* min_ks, int32_t n_m, double* est, int32_t* actual_k, uint8_t* impossible,
+                              void* stream) {
+    return sweep_call("eccknn_estimate_sweep", KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, 0, 0}, qx, qy, n_q, ks, n_k, min_ks,
+                      n_m, nullptr, est, actual_k, impossible, stream);
+}
+
+int n2v_eccknn_estimate_sweep_centered(const double* sim, int64_t n_x, const int64_t* yr_ptr, const int32_t* yr_x,
+                                       const double* yr_r, int64_t n_y, const int32_t* qx, const int32_t* qy, int64_t n_q,
+                                       const int32_t* ks, int32_t n_k, const int32_t* min_ks, int32_t n_m, int32_t centering,
+                                       int32_t user_based, double global_mean, const double* tx, const double* sd,
+                                       const double* by, double* est, int32_t* actual_k, uint8_t* impossible, void* stream) {
+    const Centred c{centering, Centering{global_mean, user_based ? 1 : 0, tx, sd, by}};
+    return sweep_call("eccknn_estimate_sweep_centered", KnnModel{sim, n_x, yr_ptr, yr_x, yr_r, n_y, 0, 0}, qx, qy, n_q, ks, n_k,
+                      min_ks, n_m, &c, est, actual_k, impossible, stream);
+}
+
 int n2v_eccknn_row_moments(const int64_t* ptr, const double* r, int64_t n_rows, int64_t n, double zero_sigma, double* mu,
                            double* sd, void* stream) {
     if (n_rows < 1 || n_rows > 0x7fffffff || n < 0)
@@ -1081,6 +1256,15 @@ int n2v_eccknn_predict(const double* est, const uint8_t* impossible, const doubl
     if (!est || !impossible || !pred || (r_true && !rmse)) return n2v::fail(N2V_ERR_INVALID, "eccknn_predict: null pointer");
     predict_kernel<<<1, 256, 0, (hipStream_t)stream>>>(est, impossible, r_true, n_q, global_mean, lo, hi, pred, rmse);
     return n2v::check_launch("eccknn_predict");
+}
+
+int n2v_eccknn_errors(const double* pred, const double* r_true, int64_t n_q, int64_t n_cols, double* rmse, double* mae,
+                      void* stream) {
+    if (n_q < 1 || n_cols < 1 || n_cols > 0x7fffffff)
+        return n2v::fail(N2V_ERR_INVALID, "eccknn_errors: n_q %lld < 1 or n_cols %lld outside [1, 2^31)", (long long)n_q, (long long)n_cols);
+    if (!pred || !r_true || (!rmse && !mae)) return n2v::fail(N2V_ERR_INVALID, "eccknn_errors: null pointer");
+    errors_kernel<<<(unsigned)n_cols, 256, 0, (hipStream_t)stream>>>(pred, r_true, n_q, rmse, mae);
+    return n2v::check_launch("eccknn_errors");
 }
 
 }  // extern "C"

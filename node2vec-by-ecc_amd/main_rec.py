@@ -5,13 +5,14 @@ plain k-NN (surprise's KNNBasic) it is compared against.
                        [-shrinkage 100] [-item-based] [-weights FILE]
                        [-mode ir|ie|ire|ier] [-window-col timestamp|timewindow] [-save-weights FILE]
                        [-test-ratio 0.2] [-seed 0] [-cv N] [-form auto|dense|sparse]
+                       [-sweep-k 5,10,20,40,80 [-sweep-mink 1,5]]
     python main_rec.py -input ratings.csv -algo mf [-factors 100] [-epochs 20] [-lr 0.005] [-reg 0.02] [-strata N|auto]
                        [-unbiased] [-test-ratio 0.2] [-seed 0] [-cv N]
     python main_rec.py -input ratings.csv -algo nmf [-factors 15] [-epochs 50] [-reg 0.06] [-test-ratio 0.2] [-seed 0] [-cv N]
     python main_rec.py -input ratings.csv -algo slopeone [-form auto|dense|sparse] [-test-ratio 0.2] [-seed 0] [-cv N]
     python main_rec.py -input ratings.csv -algo coclustering [-clusters-u 3] [-clusters-i 3] [-epochs 20] [-test-ratio 0.2]
                        [-seed 0] [-cv N]
-    every form:        [-topn N [-threshold T] [-save-recs FILE]]
+    every form:        [-topn N [-threshold T] [-save-recs FILE]] [-mae]
 
 -input    csv `user,item,rating[,timestamp]`, an optional header line is skipped
 -algo     eccen (the default) or knn: KNNBasic, which also takes -sim pearson and pearson_baseline (surprise's functions,
@@ -62,6 +63,17 @@ Prints `RMSE: <repr>` per split (and their mean for -cv).
           are not counted.
 -save-recs  write `user,item,score` lines, every training user's list best first; under -cv one file per fold, FILE.0,
           FILE.1, ...
+-mae      with every -algo: one more line `MAE: <repr>` after each split's `RMSE:` line (and `mean MAE:` for -cv), the mean
+          absolute error of the same predictions, the second measure of surprise's cross_validate.  What main() returns
+          does not change.
+-sweep-k  with -algo eccen and the four k-NN algos: the reference's experiment, every neighbourhood size of the list
+          (1 to 16 values, strictly ascending, each at most 256) against every -sweep-mink (the same rules; absent: the
+          run's -mink alone) on each split.  A split is fitted once and all cells come from one neighbour selection at the
+          largest k (n2v_hip.eccknn.estimate_sweep), each with the numbers a run with that -k and -mink prints.  Prints
+          `k K mink M RMSE: <repr> MAE: <repr>` per cell in grid order; with -cv, after the folds, `k K mink M mean RMSE:
+          <repr> mean MAE: <repr>` per cell; then `best: k K mink M mean RMSE <repr>`, the smallest mean RMSE, ties to
+          the smaller k and then the smaller min_k.  main() then returns {(k, min_k): {"rmse", "mae"}} per split.  -k
+          plays no part.  It does not go with -topn.
 """
 import argparse
 import sys
@@ -102,6 +114,9 @@ def parse_args(argv=None):
     p.add_argument("-topn", type=int, default=None)
     p.add_argument("-threshold", type=float, default=None)
     p.add_argument("-save-recs", dest="save_recs", default=None)
+    p.add_argument("-sweep-k", dest="sweep_k", default=None)
+    p.add_argument("-sweep-mink", dest="sweep_mink", default=None)
+    p.add_argument("-mae", action="store_true")
     a = p.parse_args(argv)
     if a.topn is None:
         for flag, v in (("-threshold", a.threshold), ("-save-recs", a.save_recs)):
@@ -160,6 +175,20 @@ def parse_args(argv=None):
             nmf.NMF(n_factors=a.factors, n_epochs=a.epochs, reg_pu=a.reg, reg_qi=a.reg)
         except ValueError as e:
             p.error(str(e))
+    if a.sweep_k is None:
+        if a.sweep_mink is not None:
+            p.error("-sweep-mink needs -sweep-k")
+    else:
+        if a.algo != "eccen" and a.algo not in KNN_ALGOS:
+            p.error("-sweep-k does not go with -algo %s" % a.algo)
+        if a.topn is not None:
+            p.error("-sweep-k does not go with -topn")
+        from n2v_hip import eccknn
+        try:
+            grid = [[int(v) for v in text.split(",")] for text in (a.sweep_k, a.sweep_mink or str(a.mink))]
+            a.sweep_k, a.sweep_mink = eccknn.sweep_options(*grid)
+        except ValueError as e:
+            p.error("-sweep-k / -sweep-mink: %s" % e)
     if a.sim in ("pearson", "pearson_baseline") and a.algo not in KNN_ALGOS:
         p.error("-sim %s is surprise's own similarity: it needs -algo knn (or knnmeans, knnzscore, knnbaseline)" % a.sim)
     if not 0.0 < a.test_ratio < 1.0:
@@ -307,25 +336,45 @@ def write_recs(path, recs):
 
 
 def run_split(args, users, items, ratings, weights, train, test, recs_path=None):
-    """The split's rmse; with -topn, (rmse, (f1, map, mrr, ndcg)), and the lists written to recs_path when it is given."""
+    """(result, mae) of one split.  result: the rmse; with -topn, (rmse, (f1, map, mrr, ndcg)), and the lists written to
+    recs_path when it is given; with -sweep-k, {(k, min_k): {"rmse", "mae"}} over the grid.  mae: None without -mae."""
     algo = fit_split(args, users, items, ratings, weights, train)
     testset = [(users[i], items[i], ratings[i]) for i in test]
+    if args.sweep_k is not None:
+        return algo.accuracy_sweep(testset, args.sweep_k, args.sweep_mink), None
     err = algo.rmse(testset)
+    mae = algo.mae(testset) if args.mae else None
     if args.topn is None:
-        return err
+        return err, mae
     metrics = algo.ranking_metrics(testset, args.topn, args.threshold)[:4]
     if recs_path:
         write_recs(recs_path, algo.recommend(args.topn))
-    return err, metrics
+    return (err, metrics), mae
 
 
-def report(args, result):
+def report(args, result, mae=None):
     """Prints one split's lines."""
-    if args.topn is None:
-        print("RMSE: %r" % result)
+    if args.sweep_k is not None:
+        for (k, min_k), cell in result.items():
+            print("k %d mink %d RMSE: %r MAE: %r" % (k, min_k, cell["rmse"], cell["mae"]))
         return
-    print("RMSE: %r" % result[0])
-    print("F1 / MAP / MRR / NDCG @%d: %r / %r / %r / %r" % ((args.topn,) + tuple(result[1])))
+    print("RMSE: %r" % (result if args.topn is None else result[0]))
+    if mae is not None:
+        print("MAE: %r" % mae)
+    if args.topn is not None:
+        print("F1 / MAP / MRR / NDCG @%d: %r / %r / %r / %r" % ((args.topn,) + tuple(result[1])))
+
+
+def report_sweep(args, results):
+    """After the splits of a sweep: the per-cell means when there are folds, then the best cell by mean RMSE, ties to the
+    smaller k and then the smaller min_k (the grid's order)."""
+    cells = [(k, min_k) for k in args.sweep_k for min_k in args.sweep_mink]
+    mean = {c: tuple(float(np.mean([r[c][m] for r in results])) for m in ("rmse", "mae")) for c in cells}
+    if args.cv:
+        for c in cells:
+            print("k %d mink %d mean RMSE: %r mean MAE: %r" % (c + mean[c]))
+    best = min(cells, key=lambda c: (np.isnan(mean[c][0]), mean[c][0]))   # min() keeps the first of equal keys
+    print("best: k %d mink %d mean RMSE %r" % (best + (mean[best][0],)))
 
 
 def main(argv=None):
@@ -338,16 +387,25 @@ def main(argv=None):
     if args.save_weights:
         write_weights(args.save_weights, weights)
     if args.cv:
-        results = []
+        results, maes = [], []
         for fold, (train, test) in enumerate(folds(len(ratings), args.cv, args.seed)):
             recs_path = "%s.%d" % (args.save_recs, fold) if args.save_recs else None
-            results.append(run_split(args, users, items, ratings, weights, train, test, recs_path))
-            report(args, results[-1])
+            result, mae = run_split(args, users, items, ratings, weights, train, test, recs_path)
+            results.append(result)
+            maes.append(mae)
+            report(args, result, mae)
+        if args.sweep_k is not None:
+            report_sweep(args, results)
+            return results
         print("mean RMSE: %r" % float(np.mean([r if args.topn is None else r[0] for r in results])))
+        if args.mae:
+            print("mean MAE: %r" % float(np.mean(maes)))
         return results
     train, test = split(len(ratings), args.test_ratio, args.seed)
-    result = run_split(args, users, items, ratings, weights, train, test, args.save_recs)
-    report(args, result)
+    result, mae = run_split(args, users, items, ratings, weights, train, test, args.save_recs)
+    report(args, result, mae)
+    if args.sweep_k is not None:
+        report_sweep(args, [result])
     return result
 
 

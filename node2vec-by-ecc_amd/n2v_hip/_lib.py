@@ -132,6 +132,11 @@ SIGNATURES = {
                                            _f64, _f64, _f64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                            _ptr]),
     "n2v_eccknn_predict": (C.c_int, [_ptr, _ptr, _ptr, _i64, _f64, _f64, _f64, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_estimate_sweep": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i32, _ptr, _i32, _ptr,
+                                            _ptr, _ptr, _ptr]),
+    "n2v_eccknn_estimate_sweep_centered": (C.c_int, [_ptr, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i32, _ptr, _i32,
+                                                     _i32, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_eccknn_errors": (C.c_int, [_ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr]),
     "n2v_svd_max_factors": (C.c_int32, []),
     "n2v_svd_max_strata": (C.c_int32, []),
     "n2v_svd_blocks_check": (C.c_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr]),

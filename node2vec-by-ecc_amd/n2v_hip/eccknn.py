@@ -43,9 +43,17 @@ unrated items, by the same device functions as estimate_batch + predict and so b
 the n_users x n_items predictions are never stored.  Equal predictions rank by inner item id.  The definition is
 tests/topn_reference.py; parity with surprise is unpinned as above.
 
+The k-NN sweep (`estimate_sweep`, `test_sweep` / `accuracy_sweep` on every k-NN class, main_rec.py -sweep-k) is the step
+the reference's experiment is made of: every (k, min_k) of a grid over one fit.  The selection list is in a total order, so
+the neighbours for k are the head of the neighbours for any larger k and the rank-order sums for k a prefix of the sums for
+the largest; one selection and one walk down it give every cell with the bits of the single-cell call
+(tests/knn_sweep_reference.py is the definition: the single-cell restatement, cell by cell).  `errors` / `Predictor.mae`
+add the second measure of surprise's cross_validate, the mean absolute error, to every predictor.
+
 There is no CPU fallback.
 """
 import collections
+import collections.abc
 
 import numpy as np
 import torch
@@ -53,6 +61,7 @@ import torch
 from . import _lib
 
 MAX_K = 256                      # N2V_ECCKNN_MAX_K
+MAX_SWEEP = 16                   # N2V_ECCKNN_MAX_SWEEP: values a side of a (k, min_k) grid
 MAX_TOP_N = 256                  # N2V_TOPN_MAX_N
 MAX_SEGMENTS = 64                # segments of the candidate range per owner in the top-N kernels
 SIM_NAMES = ("cosine", "msd", "pearson", "pearson_baseline")   # the reference's construction_func keys
@@ -489,6 +498,82 @@ def predict(est, impossible, global_mean, rating_scale, r_true=None):
     return (pred, float(out.item())) if r_true is not None else pred
 
 
+# ---- k-NN sweep: every (k, min_k) of a grid from one neighbour selection ------------------------------------------------
+
+def sweep_options(ks, min_ks):
+    """(ks, min_ks) as lists of ints, the grid every sweep call takes; host only.  Each side has 1 to MAX_SWEEP values,
+    strictly ascending; every k in [1, MAX_K], every min_k >= 1."""
+    out = []
+    for name, values in (("ks", ks), ("min_ks", min_ks)):
+        if isinstance(values, (str, bytes)) or not isinstance(values, (collections.abc.Sequence, np.ndarray)):
+            raise ValueError("%s %r: a list of 1 to %d integers" % (name, values, MAX_SWEEP))
+        values = list(values)
+        if not 1 <= len(values) <= MAX_SWEEP:
+            raise ValueError("%s: %d values, outside [1, %d]" % (name, len(values), MAX_SWEEP))
+        for v in values:
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError("%s: %r is not an integer" % (name, v))
+        values = [int(v) for v in values]
+        for v in values:                                         # the rules and the messages of a single k or min_k
+            _knn_options(*((v, 1) if name == "ks" else (1, v)))
+        if any(b <= a for a, b in zip(values, values[1:])):
+            raise ValueError("%s %r: not strictly ascending" % (name, values))
+        out.append(values)
+    return out[0], out[1]
+
+
+def estimate_sweep(sim, yr, qx, qy, ks, min_ks, centering=None, check=True):
+    """(est fp64 [n_k][n_m][n_q], actual_k int32 [n_k][n_q], impossible uint8 [n_k][n_m][n_q]) device tensors: cell (j, m)
+    is estimate_batch(sim, yr, qx, qy, ks[j], min_ks[m]) bit for bit, all of them from one selection at the largest k and one
+    walk down it (n2v_eccknn_estimate_sweep).  The selection list is in a total order, so the list for k is the head of
+    the list for any larger k, the rank-order sums for k are a prefix of the sums for the largest k, and min_k enters in
+    the finish alone.  With a Centering the cells are estimate_batch_centered's (n2v_eccknn_estimate_sweep_centered), and yr
+    is checked first as there; check False: the caller has run yr_check on these lists."""
+    ks, min_ks = sweep_options(ks, min_ks)
+    _require_gpu()
+    n_q = _query_count(qx, qy)
+    n_x, n_y = sim.shape[0], yr[0].numel() - 1
+    n_k, n_m = len(ks), len(min_ks)
+    tail = []
+    if centering is not None:
+        code, tx, sd, by = _centering_args(centering, n_x, n_y)
+        if check:
+            yr_check(yr, n_x)
+        tail = [code, 1 if centering.user_based else 0, float(centering.global_mean), tx, sd, by]
+    dev = sim.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        est = torch.empty((n_k, n_m, n_q), dtype=torch.float64, device=dev)
+        actual_k = torch.empty((n_k, n_q), dtype=torch.int32, device=dev)
+        imp = torch.empty((n_k, n_m, n_q), dtype=torch.uint8, device=dev)
+        fn = lib.n2v_eccknn_estimate_sweep if centering is None else lib.n2v_eccknn_estimate_sweep_centered
+        _lib.check(fn(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y, _lib.ptr(qx), _lib.ptr(qy), n_q,
+                      (_lib.C.c_int32 * n_k)(*ks), n_k, (_lib.C.c_int32 * n_m)(*min_ks), n_m, *tail, _lib.ptr(est),
+                      _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
+    return est, actual_k, imp
+
+
+def errors(pred, r_true):
+    """(rmse, mae) host fp64 arrays over the columns of pred, a device fp64 tensor [n_cols][n_q] (or [n_q]: one column),
+    against r_true, device fp64 [n_q] (n2v_eccknn_errors): both sums in query order, the rmse of a column the bits
+    predict() gives for it."""
+    _require_gpu()
+    if pred.dim() == 1:
+        pred = pred.view(1, -1)
+    if pred.dim() != 2 or pred.dtype != torch.float64 or r_true.dtype != torch.float64 or pred.numel() == 0 \
+            or r_true.dim() != 1 or r_true.numel() != pred.shape[1]:
+        raise ValueError("errors: pred must be fp64 [n_cols][n_q] or [n_q] and r_true fp64 [n_q], n_q >= 1")
+    dev = pred.device
+    lib = _lib.load()
+    n_cols, n_q = pred.shape
+    with torch.cuda.device(dev):
+        out = torch.empty((2, n_cols), dtype=torch.float64, device=dev)
+        _lib.check(lib.n2v_eccknn_errors(_lib.ptr(pred), _lib.ptr(r_true), n_q, n_cols, _lib.ptr(out[0]), _lib.ptr(out[1]),
+                                         _lib.stream_ptr(dev)))
+        out = out.cpu().numpy()
+    return out[0].copy(), out[1].copy()
+
+
 # ---- top-N lists ------------------------------------------------------------------------------------------------------
 
 def topn_options(n, segments):
@@ -656,16 +741,20 @@ class Predictor(TopN):
         u, i = _to_device(u, torch.int32, self._device()), _to_device(i, torch.int32, self._device())
         return (i, u) if self._swapped() else (u, i)
 
-    def _test(self, testset):
-        """testset: (raw user, raw item, true rating) triples -> (pred, *extras, impossible, rmse)."""
+    def _test_inputs(self, testset):
+        """testset: (raw user, raw item, true rating) triples -> the query pair of _queries and the true ratings on the device."""
         testset = list(testset)
         if not testset:
             raise ValueError("test: empty testset")
         ts = self.trainset
         qx, qy = self._queries(ts.inner_uids([t[0] for t in testset]), ts.inner_iids([t[1] for t in testset]))
+        return qx, qy, _to_device(np.array([t[2] for t in testset], dtype=np.float64), torch.float64, self._device())
+
+    def _test(self, testset):
+        """testset: (raw user, raw item, true rating) triples -> (pred, *extras, impossible, rmse)."""
+        qx, qy, r_true = self._test_inputs(testset)
         est, *extras, imp = self._estimate_batch(qx, qy)
-        r_true = _to_device(np.array([t[2] for t in testset], dtype=np.float64), torch.float64, self._device())
-        pred, err = predict(est, imp, ts.global_mean, ts.rating_scale, r_true)
+        pred, err = predict(est, imp, self.trainset.global_mean, self.trainset.rating_scale, r_true)
         return (pred, *extras, imp, err)
 
     def test(self, testset):
@@ -676,6 +765,14 @@ class Predictor(TopN):
 
     def rmse(self, testset):
         return self._test(testset)[-1]
+
+    def mae(self, testset):
+        """The mean absolute error of test()'s predictions, the second measure of surprise's cross_validate: the sum in
+        test order (errors)."""
+        qx, qy, r_true = self._test_inputs(testset)
+        est, *_, imp = self._estimate_batch(qx, qy)
+        pred = predict(est, imp, self.trainset.global_mean, self.trainset.rating_scale)
+        return float(errors(pred, r_true)[1][0])
 
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
@@ -757,6 +854,35 @@ class _SymmetricKNN(Predictor):
         ts = self.trainset
         return top_n(self.sim, self.yr, self._seen(), self.sim_options["user_based"], self.k, self.min_k, ts.global_mean,
                      ts.rating_scale, n, owners, segments)
+
+    def _sweep_centering(self):
+        """What estimate_sweep takes as its centering: None here, the fit's Centering in the centred classes."""
+        return None
+
+    def _sweep(self, testset, ks, min_ks):
+        """(ks, min_ks, pred [n_k][n_m][n_q], actual_k, impossible, r_true): the grid's estimates of the test pairs from
+        one estimate_sweep, then the fallback and the clip of every cell in one predict call (it is elementwise)."""
+        ks, min_ks = sweep_options(ks, min_ks)
+        qx, qy, r_true = self._test_inputs(testset)
+        est, actual_k, imp = estimate_sweep(self.sim, self.yr, qx, qy, ks, min_ks, self._sweep_centering(), check=False)
+        pred = predict(est.view(-1), imp.view(-1), self.trainset.global_mean, self.trainset.rating_scale).view(est.shape)
+        return ks, min_ks, pred, actual_k, imp, r_true
+
+    def test_sweep(self, testset, ks, min_ks):
+        """{(k, min_k): (pred, actual_k, was_impossible)} over the grid ks x min_ks: every value what test() returns from a
+        model with that k and min_k, all from one neighbour selection at the largest k.  self.k and self.min_k play no part
+        and are not touched."""
+        ks, min_ks, pred, actual_k, imp, _ = self._sweep(testset, ks, min_ks)
+        pred, actual_k, imp = pred.cpu().numpy(), actual_k.cpu().numpy(), imp.cpu().numpy().astype(bool)
+        return {(k, m): (pred[j, n], actual_k[j], imp[j, n]) for j, k in enumerate(ks) for n, m in enumerate(min_ks)}
+
+    def accuracy_sweep(self, testset, ks, min_ks):
+        """{(k, min_k): {"rmse": ..., "mae": ...}} over the grid, in grid order: the rmse() and mae() of a model with that k
+        and min_k, from one estimate_sweep, one predict and one errors call."""
+        ks, min_ks, pred, _, _, r_true = self._sweep(testset, ks, min_ks)
+        rmse, mae = errors(pred.view(len(ks) * len(min_ks), -1), r_true)
+        cells = [(k, m) for k in ks for m in min_ks]
+        return {cell: {"rmse": float(rmse[c]), "mae": float(mae[c])} for c, cell in enumerate(cells)}
 
 
 class EccenKNN(_SymmetricKNN):
@@ -844,6 +970,9 @@ class _CenteredKNN(KNNBasic):
             raise PredictionImpossible("User and/or item is unkown.")
         est, ak, _ = self._estimate_batch(*self._queries([u], [i]))
         return float(est.item()), {"actual_k": int(ak.item())}
+
+    def _sweep_centering(self):
+        return self.centering
 
     def _top_n(self, owners, n, segments):
         return top_n_centered(self.sim, self.yr, self._seen(), self.k, self.min_k, self.trainset.rating_scale, n,
