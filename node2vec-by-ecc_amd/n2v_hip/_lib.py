@@ -229,10 +229,63 @@ def check(rc):
 
 
 def ptr(t):
-    """Device (or host) pointer of a torch tensor, None -> NULL."""
+    """Device (or host) pointer of a torch tensor the caller of this function allocated itself, None -> NULL.  A tensor that
+    comes from outside the package goes through tensor() below."""
     if t is None:
         return None
-    assert t.is_contiguous(), "non-contiguous tensor passed to the C-ABI"
+    if not t.is_contiguous():
+        raise ValueError("non-contiguous tensor passed to the C-ABI")
+    return t.data_ptr()
+
+
+def call_device(fn, name, t):
+    """The device a wrapper's call runs on: that of its first tensor argument `t`, which has to be a GPU tensor.  A CPU
+    tensor's address must never reach a kernel.  Reads t.device only."""
+    if t is None:
+        raise ValueError("%s: %s is required, got None" % (fn, name))
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor, got %s" % (fn, name, type(t).__name__))
+    if t.device.type != "cuda":
+        raise ValueError("%s: %s is on %s; the call runs on a GPU and takes device tensors" % (fn, name, t.device))
+    return t.device
+
+
+def _shape_text(shape):
+    return "[" + ", ".join("n" if s is None else str(s) for s in shape) + "]"
+
+
+def tensor(fn, name, t, dtype, device, shape=None, optional=False):
+    """The pointer of a caller-supplied tensor after the one check of the wrappers' contract: `t` is a contiguous torch
+    tensor of `dtype` on `device` (the device the call runs on), and of `shape` when one is given: an int n is a 1-D
+    tensor of n entries, a tuple is the exact shape with None for a free extent, so (None,) is any 1-D tensor.  None is
+    NULL where `optional`.  Anything else is a ValueError that names the function `fn` and the argument `name`; a
+    non-tensor is a TypeError.  Host work only: dtype, device, dim(), shape, numel() and is_contiguous() are read, nothing
+    is launched and nothing synchronises."""
+    if t is None:
+        if optional:
+            return None
+        raise ValueError("%s: %s is required, got None" % (fn, name))
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: %s must be a torch tensor, got %s" % (fn, name, type(t).__name__))
+    ok = t.dtype == dtype and t.device == device and t.is_contiguous()
+    if ok and shape is not None:                                    # written out: this runs on every call of every wrapper
+        have = t.shape
+        if shape.__class__ is tuple:
+            ok = len(have) == len(shape)
+            if ok:
+                for want, got in zip(shape, have):
+                    if want is not None and want != got:
+                        ok = False
+                        break
+        else:
+            ok = len(have) == 1 and have[0] == shape
+    if not ok:
+        if shape is not None and not isinstance(shape, tuple):
+            shape = (int(shape),)
+        raise ValueError("%s: %s must be a contiguous %s tensor%s on %s, the device the call runs on; got %s%s %s on %s"
+                         % (fn, name, str(dtype).replace("torch.", ""), "" if shape is None else " " + _shape_text(shape),
+                            device, "" if t.is_contiguous() else "non-contiguous ", str(t.dtype).replace("torch.", ""),
+                            _shape_text(tuple(t.shape)), t.device))
     return t.data_ptr()
 
 

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eccknn import Predictor, _csr_to_device, _query_count, _require_gpu, _to_device, _topn_call, row_moments, topn_options, yr_check
+from .eccknn import (Predictor, _csr_ptrs, _csr_to_device, _queries_ptrs, _query_count, _require_gpu, _to_device, _topn_call,
+                     row_moments, topn_options, yr_check)
 from .nmf import row_order
 
 MAX_CLUSTERS = 64                # n2v_cocl_max_clusters()
@@ -35,16 +36,26 @@ def check_clusters(n_cltr_u, n_cltr_i):
 # ---- C-ABI wrappers (device tensors in, device tensors out) -----------------------------------------------------------
 
 def _check_assignment(what, cltr, n_rows, n_cltr):
-    """Integers only: an int32 assignment of n_rows entries, every one in [0, n_cltr)."""
-    if cltr.dtype != torch.int32 or cltr.dim() != 1 or cltr.numel() != int(n_rows) or not cltr.is_contiguous():
-        raise ValueError("coclustering: %s must be a contiguous int32[%d]" % (what, n_rows))
+    """Integers only: every entry of an assignment in [0, n_cltr).  Its type and length are the wrappers' own check."""
     if int(cltr.min().item()) < 0 or int(cltr.max().item()) >= int(n_cltr):
         raise ValueError("coclustering: %s holds a cluster id outside [0, %d)" % (what, n_cltr))
 
 
-def _check_table(what, t, shape):
-    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError("coclustering: %s %s %s, expected contiguous fp64 %s" % (what, t.dtype, tuple(t.shape), tuple(shape)))
+def _tables(fn, avgs, user_mean, item_mean, dev=None, n_users=None, n_items=None):
+    """([avg_cltr_u, avg_cltr_i, avg_cocltr, user_mean, item_mean] pointers, n_cltr_u, n_cltr_i, n_users, n_items, device)
+    of the fp64 tables both the assignment pass and the estimates read.  dev None: the GPU of user_mean; n_users, n_items
+    None: the lengths of the two means."""
+    if not isinstance(avgs, (tuple, list)) or len(avgs) < 3:
+        raise ValueError("%s: avgs must be (avg_cltr_u, avg_cltr_i, avg_cocltr[, ...]) of averages()" % fn)
+    if dev is None:
+        dev = _lib.call_device(fn, "user_mean", user_mean)
+    p_um = _lib.tensor(fn, "user_mean", user_mean, torch.float64, dev, (n_users,))
+    p_im = _lib.tensor(fn, "item_mean", item_mean, torch.float64, dev, (n_items,))
+    p_u = _lib.tensor(fn, "avgs[0] (avg_cltr_u)", avgs[0], torch.float64, dev, (None,))
+    p_i = _lib.tensor(fn, "avgs[1] (avg_cltr_i)", avgs[1], torch.float64, dev, (None,))
+    n_cltr_u, n_cltr_i = check_clusters(avgs[0].numel(), avgs[1].numel())
+    p_cc = _lib.tensor(fn, "avgs[2] (avg_cocltr)", avgs[2], torch.float64, dev, (n_cltr_u, n_cltr_i))
+    return [p_u, p_i, p_cc, p_um, p_im], n_cltr_u, n_cltr_i, user_mean.numel(), item_mean.numel(), dev
 
 
 def _overlaps(a, b):
@@ -58,21 +69,22 @@ def averages(ur, n_items, cltr_u, cltr_i, n_cltr_u, n_cltr_i, global_mean, check
     (integers only); a malformed input is a ValueError, not a launch."""
     _require_gpu()
     n_cltr_u, n_cltr_i = check_clusters(n_cltr_u, n_cltr_i)
+    fn = "coclustering.averages"
+    p_ur, n, d = _csr_ptrs(fn, "ur", ur, None, ("ptr", "item", "r"))
     n_users, n_items = ur[0].numel() - 1, int(n_items)
+    p_cu = _lib.tensor(fn, "cltr_u", cltr_u, torch.int32, d, n_users)
+    p_ci = _lib.tensor(fn, "cltr_i", cltr_i, torch.int32, d, n_items)
     if check:
         yr_check(ur, n_items)
         _check_assignment("cltr_u", cltr_u, n_users, n_cltr_u)
         _check_assignment("cltr_i", cltr_i, n_items, n_cltr_i)
-    n = ur[1].numel()
-    d = ur[2].device
     with torch.cuda.device(d):
         part = torch.empty((n_users, n_cltr_i + 1), dtype=torch.float64, device=d)
         avg_u = torch.empty(n_cltr_u, dtype=torch.float64, device=d)
         avg_i = torch.empty(n_cltr_i, dtype=torch.float64, device=d)
         avg_cc = torch.empty((n_cltr_u, n_cltr_i), dtype=torch.float64, device=d)
         count = torch.empty((n_cltr_u, n_cltr_i), dtype=torch.int64, device=d)
-        _lib.check(_lib.load().n2v_cocl_averages(_lib.ptr(ur[0]), _lib.ptr(ur[1]) if n else None, _lib.ptr(ur[2]) if n else None,
-                                                 n_users, n_items, n, _lib.ptr(cltr_u), _lib.ptr(cltr_i), n_cltr_u, n_cltr_i,
+        _lib.check(_lib.load().n2v_cocl_averages(*p_ur, n_users, n_items, n, p_cu, p_ci, n_cltr_u, n_cltr_i,
                                                  float(global_mean), _lib.ptr(part), _lib.ptr(avg_u), _lib.ptr(avg_i),
                                                  _lib.ptr(avg_cc), _lib.ptr(count), _lib.stream_ptr(d)))
     return avg_u, avg_i, avg_cc, count
@@ -84,34 +96,26 @@ def assign(lst, user_side, cltr_u, cltr_i, avgs, user_mean, item_mean, order=Non
     written.  avgs: (avg_cltr_u, avg_cltr_i, avg_cocltr[, ...]) of averages().  order: None or an int32 permutation of the
     rows (nmf.row_order: longest lists first); it changes no bit.  check as averages(), on the side that is read."""
     _require_gpu()
-    avg_u, avg_i, avg_cc = avgs[:3]
-    n_cltr_u, n_cltr_i = check_clusters(avg_u.numel(), avg_i.numel())
+    fn = "coclustering.assign"
+    p_lst, n, d = _csr_ptrs(fn, "lst", lst, None, ("ptr", "item" if user_side else "user", "r"))
+    p_cu = _lib.tensor(fn, "cltr_u", cltr_u, torch.int32, d, (None,))
+    p_ci = _lib.tensor(fn, "cltr_i", cltr_i, torch.int32, d, (None,))
     n_users, n_items = cltr_u.numel(), cltr_i.numel()
     n_rows, n_other = (n_users, n_items) if user_side else (n_items, n_users)
-    _check_table("avg_cltr_u", avg_u, (n_cltr_u,)); _check_table("avg_cltr_i", avg_i, (n_cltr_i,))
-    _check_table("avg_cocltr", avg_cc, (n_cltr_u, n_cltr_i))
-    _check_table("user_mean", user_mean, (n_users,)); _check_table("item_mean", item_mean, (n_items,))
-    if lst[0].numel() != n_rows + 1:
-        raise ValueError("coclustering.assign: %d ptr entries for %d rows" % (lst[0].numel(), n_rows))
-    if cltr_u.dtype != torch.int32 or cltr_i.dtype != torch.int32 or not cltr_u.is_contiguous() or not cltr_i.is_contiguous():
-        raise ValueError("coclustering.assign: cltr_u and cltr_i must be contiguous int32")
+    (p_au, p_ai, p_cc, p_um, p_im), n_cltr_u, n_cltr_i, _, _, _ = _tables(fn, avgs, user_mean, item_mean, d, n_users, n_items)
+    _lib.tensor(fn, "lst[0] (int64 ptr)", lst[0], torch.int64, d, n_rows + 1)
     if _overlaps(cltr_u, cltr_i):
         raise ValueError("coclustering.assign: aliased buffers: cltr_u and cltr_i overlap, and one is read while the other is written")
-    if order is not None and (order.dtype != torch.int32 or order.numel() != n_rows):
-        raise ValueError("coclustering.assign: order must be int32[%d]" % n_rows)
+    p_order = _lib.tensor(fn, "order", order, torch.int32, d, n_rows, optional=True)
     if check:
         yr_check(lst, n_other)
         if user_side:
             _check_assignment("cltr_i", cltr_i, n_items, n_cltr_i)
         else:
             _check_assignment("cltr_u", cltr_u, n_users, n_cltr_u)
-    n = lst[1].numel()
-    d = lst[2].device
     with torch.cuda.device(d):
-        _lib.check(_lib.load().n2v_cocl_assign(_lib.ptr(lst[0]), _lib.ptr(lst[1]) if n else None, _lib.ptr(lst[2]) if n else None,
-                                               _lib.ptr(order), n_users, n_items, n, 1 if user_side else 0, n_cltr_u, n_cltr_i,
-                                               _lib.ptr(user_mean), _lib.ptr(item_mean), _lib.ptr(avg_u), _lib.ptr(avg_i),
-                                               _lib.ptr(avg_cc), _lib.ptr(cltr_u), _lib.ptr(cltr_i), _lib.stream_ptr(d)))
+        _lib.check(_lib.load().n2v_cocl_assign(*p_lst, p_order, n_users, n_items, n, 1 if user_side else 0, n_cltr_u, n_cltr_i,
+                                               p_um, p_im, p_au, p_ai, p_cc, p_cu, p_ci, _lib.stream_ptr(d)))
 
 
 def epoch(ur, ir, cltr_u, cltr_i, n_cltr_u, n_cltr_i, global_mean, user_mean, item_mean, order=(None, None), check=True):
@@ -123,31 +127,27 @@ def epoch(ur, ir, cltr_u, cltr_i, n_cltr_u, n_cltr_i, global_mean, user_mean, it
     return avgs
 
 
-def _model_args(cltr_u, cltr_i, avgs, user_mean, item_mean, check):
-    """The model's part of the two calls below after the host checks."""
-    avg_u, avg_i, avg_cc = avgs[:3]
-    n_cltr_u, n_cltr_i = check_clusters(avg_u.numel(), avg_i.numel())
-    n_users, n_items = user_mean.numel(), item_mean.numel()
-    _check_table("avg_cltr_u", avg_u, (n_cltr_u,)); _check_table("avg_cltr_i", avg_i, (n_cltr_i,))
-    _check_table("avg_cocltr", avg_cc, (n_cltr_u, n_cltr_i))
-    _check_table("user_mean", user_mean, (n_users,)); _check_table("item_mean", item_mean, (n_items,))
+def _model_args(fn, cltr_u, cltr_i, avgs, user_mean, item_mean, check):
+    """(the model's part of the two calls below after the host checks, the device of the call: user_mean's)."""
+    tables, n_cltr_u, n_cltr_i, n_users, n_items, d = _tables(fn, avgs, user_mean, item_mean)
+    p_cu = _lib.tensor(fn, "cltr_u", cltr_u, torch.int32, d, n_users)
+    p_ci = _lib.tensor(fn, "cltr_i", cltr_i, torch.int32, d, n_items)
     if check:
         _check_assignment("cltr_u", cltr_u, n_users, n_cltr_u)
         _check_assignment("cltr_i", cltr_i, n_items, n_cltr_i)
-    return [_lib.ptr(cltr_u), _lib.ptr(cltr_i), _lib.ptr(avg_u), _lib.ptr(avg_i), _lib.ptr(avg_cc), _lib.ptr(user_mean),
-            _lib.ptr(item_mean), n_users, n_items, n_cltr_u, n_cltr_i]
+    return [p_cu, p_ci] + tables + [n_users, n_items, n_cltr_u, n_cltr_i], d
 
 
 def estimate_batch(cltr_u, cltr_i, avgs, user_mean, item_mean, global_mean, qu, qi, check=True):
     """(est fp64, impossible uint8, all zero) device tensors for int32 device queries, -1 = unknown (n2v_cocl_estimate)."""
     _require_gpu()
-    n_q = _query_count(qu, qi, ("user", "item"))
-    model = _model_args(cltr_u, cltr_i, avgs, user_mean, item_mean, check)
-    d = user_mean.device
+    model, d = _model_args("coclustering.estimate_batch", cltr_u, cltr_i, avgs, user_mean, item_mean, check)
+    p_qu, p_qi = _queries_ptrs("coclustering.estimate_batch", qu, qi, d, ("qu", "qi"))
+    n_q = _query_count(qu, qi, ("user", "item"), ("qu", "qi"))
     with torch.cuda.device(d):
         est = torch.empty(n_q, dtype=torch.float64, device=d)
         imp = torch.empty(n_q, dtype=torch.uint8, device=d)
-        _lib.check(_lib.load().n2v_cocl_estimate(*model, float(global_mean), _lib.ptr(qu), _lib.ptr(qi), n_q, _lib.ptr(est),
+        _lib.check(_lib.load().n2v_cocl_estimate(*model, float(global_mean), p_qu, p_qi, n_q, _lib.ptr(est),
                                                  _lib.ptr(imp), _lib.stream_ptr(d)))
     return est, imp
 
@@ -158,9 +158,9 @@ def top_n(cltr_u, cltr_i, avgs, user_mean, item_mean, seen, global_mean, rating_
     clipped item_mean."""
     n, segments = topn_options(n, segments)
     _require_gpu()
-    model = _model_args(cltr_u, cltr_i, avgs, user_mean, item_mean, check)
+    model, d = _model_args("coclustering.top_n", cltr_u, cltr_i, avgs, user_mean, item_mean, check)
     return _topn_call(_lib.load().n2v_cocl_topn, model, [], [], seen, model[7], model[8], owners, global_mean, rating_scale, n,
-                      segments, user_mean.device)
+                      segments, d)
 
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------

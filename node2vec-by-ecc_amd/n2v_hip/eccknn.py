@@ -121,12 +121,40 @@ def _knn_options(k, min_k):
     return k, min_k
 
 
-def _query_count(qx, qy, sides=("x", "y")):
+def _query_count(qx, qy, sides=("x", "y"), names=("qx", "qy")):
     """The number of queries of an estimate call: at least one, and as many on one side as on the other."""
     n_q = qx.numel()
     if n_q == 0 or qy.numel() != n_q:
-        raise ValueError("estimate: %d %s and %d %s queries: nothing to estimate" % (n_q, sides[0], qy.numel(), sides[1]))
+        raise ValueError("estimate: %d %s (%s) and %d %s (%s) queries: nothing to estimate"
+                         % (n_q, sides[0], names[0], qy.numel(), sides[1], names[1]))
     return n_q
+
+
+def _queries_ptrs(fn, qx, qy, dev, names=("qx", "qy")):
+    """(qx pointer, qy pointer) of the int32 query pair of an estimate call, each a 1-D tensor on `dev`."""
+    return (_lib.tensor(fn, names[0], qx, torch.int32, dev, (None,)), _lib.tensor(fn, names[1], qy, torch.int32, dev, (None,)))
+
+
+def _csr_ptrs(fn, name, triple, dev=None, roles=("ptr", "ids", "r"), n_rows=None):
+    """([ptr, ids(, r)] pointers, n, dev) of a caller's CSR (int64 ptr[n_rows + 1], int32 ids[n], fp64 r[n]) on `dev`, or,
+    when dev is None, on the GPU of its last entry, which then is the device of the call.  With two roles the list has no
+    ratings, and a third entry of the tuple is not read.  n_rows None leaves ptr's length to the caller, which has its
+    own message for it.  The pointers of an empty list are NULL."""
+    kinds = list(zip(roles, (torch.int64, torch.int32, torch.float64)))
+    if not isinstance(triple, (tuple, list)) or len(triple) < len(kinds):
+        raise ValueError("%s: %s must be (%s)" % (fn, name, ", ".join("%s %s" % (str(dt).replace("torch.", ""), role)
+                                                                        for role, dt in kinds)))
+    label = ["%s[%d] (%s %s)" % (name, j, str(dt).replace("torch.", ""), role) for j, (role, dt) in enumerate(kinds)]
+    if dev is None:
+        dev = _lib.call_device(fn, label[-1], triple[len(kinds) - 1])
+    out = [_lib.tensor(fn, label[0], triple[0], torch.int64, dev, (None,) if n_rows is None else int(n_rows) + 1),
+           _lib.tensor(fn, label[1], triple[1], torch.int32, dev, (None,))]
+    n = triple[1].numel()
+    if len(kinds) == 3:
+        out.append(_lib.tensor(fn, label[2], triple[2], torch.float64, dev, n))
+    if triple[0].numel() < 2:
+        raise ValueError("%s: %s: %d ptr entries: at least one row" % (fn, label[0], triple[0].numel()))
+    return [out[0]] + [q if n else None for q in out[1:]], n, dev
 
 
 def _csr(major, minor, r, n_major):
@@ -188,6 +216,9 @@ class Trainset:
 
 
 # ---- C-ABI wrappers (device tensors in, device tensors out) -----------------------------------------------------------
+# The types the docstrings state are enforced, not converted: every tensor a caller supplies goes through _lib.tensor
+# before the first library call that takes a pointer (contiguous, the stated dtype, rank and length, on the GPU of the
+# call's first tensor argument); anything else is a ValueError naming the function and the argument.  Host work only.
 
 def densify(x, y, r, n_x, n_y):
     """(dense fp64 [n_y][n_x], mask uint8 [n_y][n_x]) of int32 / fp64 device triples."""
@@ -196,21 +227,32 @@ def densify(x, y, r, n_x, n_y):
     if n_x * n_y > int(lib.n2v_eccknn_max_dense()):
         raise ValueError("eccknn: n_x * n_y = %d x %d exceeds the dense limit of %d elements"
                          % (n_x, n_y, lib.n2v_eccknn_max_dense()))
-    dev = r.device
+    dev = _lib.call_device("eccknn.densify", "r", r)
+    p_r = _lib.tensor("eccknn.densify", "r", r, torch.float64, dev, (None,))
+    p_x = _lib.tensor("eccknn.densify", "x", x, torch.int32, dev, r.numel())
+    p_y = _lib.tensor("eccknn.densify", "y", y, torch.int32, dev, r.numel())
     with torch.cuda.device(dev):
         dense = torch.empty((n_y, n_x), dtype=torch.float64, device=dev)
         mask = torch.empty((n_y, n_x), dtype=torch.uint8, device=dev)
-        _lib.check(lib.n2v_eccknn_densify(_lib.ptr(x), _lib.ptr(y), _lib.ptr(r), r.numel(), n_x, n_y, _lib.ptr(dense),
+        _lib.check(lib.n2v_eccknn_densify(p_x, p_y, p_r, r.numel(), n_x, n_y, _lib.ptr(dense),
                                           _lib.ptr(mask), _lib.stream_ptr(dev)))
     return dense, mask
 
 
-def similarity(dense, mask, w, name, min_support=1, accumulators=False):
-    """sim fp64 [n_x][n_x]; with accumulators also a dict of the reference's arrays (freq, and prods / sqi / sqj or
-    sq_diff)."""
-    _require_gpu()
+def _dense_ptrs(fn, dense, mask):
+    """(dense pointer, mask pointer, n_x, n_y, device) of densify's pair: fp64 and uint8 [n_y][n_x] on one GPU."""
+    dev = _lib.call_device(fn, "dense", dense)
+    p_dense = _lib.tensor(fn, "dense", dense, torch.float64, dev, (None, None))
     n_y, n_x = dense.shape
-    dev = dense.device
+    return p_dense, _lib.tensor(fn, "mask", mask, torch.uint8, dev, (n_y, n_x)), n_x, n_y, dev
+
+
+def similarity(dense, mask, w, name, min_support=1, accumulators=False):
+    """sim fp64 [n_x][n_x] from densify's pair (dense fp64, mask uint8, both [n_y][n_x]) and the weights w fp64[n_y]; with
+    accumulators also a dict of the reference's arrays (freq, and prods / sqi / sqj or sq_diff)."""
+    _require_gpu()
+    p_dense, p_mask, n_x, n_y, dev = _dense_ptrs("eccknn.similarity", dense, mask)
+    p_w = _lib.tensor("eccknn.similarity", "w", w, torch.float64, dev, n_y)
     lib = _lib.load()
     with torch.cuda.device(dev):
         sim = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
@@ -219,7 +261,7 @@ def similarity(dense, mask, w, name, min_support=1, accumulators=False):
             acc["freq"] = torch.empty((n_x, n_x), dtype=torch.int32, device=dev)
             for nm in (("prods", "sqi", "sqj") if name == "cosine" else ("sq_diff",)):
                 acc[nm] = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
-        _lib.check(lib.n2v_eccknn_sim(_lib.ptr(dense), _lib.ptr(mask), n_x, n_y, _lib.ptr(w), _METHOD[name], int(min_support),
+        _lib.check(lib.n2v_eccknn_sim(p_dense, p_mask, n_x, n_y, p_w, _METHOD[name], int(min_support),
                                       _lib.ptr(sim), _lib.ptr(acc.get("freq")), _lib.ptr(acc.get("prods")),
                                       _lib.ptr(acc.get("sqi")), _lib.ptr(acc.get("sqj")), _lib.ptr(acc.get("sq_diff")),
                                       _lib.stream_ptr(dev)))
@@ -255,12 +297,12 @@ def csr_by_x(x, y, r, n_x, n_y=None):
 def csr_check(xr, n_y):
     """Raises ValueError when the x-major CSR is malformed (n2v_eccknn_csr_check); one read-back of an int32."""
     _require_gpu()
+    (p_ptr, p_ys), _, dev = _csr_ptrs("eccknn.csr_check", "xr", xr, None, ("ptr", "y"))
     ptr_, ys = xr[0], xr[1]
-    dev = ptr_.device
     lib = _lib.load()
     with torch.cuda.device(dev):
         status = torch.zeros(1, dtype=torch.int32, device=dev)
-        _lib.check(lib.n2v_eccknn_csr_check(_lib.ptr(ptr_), _lib.ptr(ys), ptr_.numel() - 1, int(n_y), ys.numel(),
+        _lib.check(lib.n2v_eccknn_csr_check(p_ptr, p_ys, ptr_.numel() - 1, int(n_y), ys.numel(),
                                             _lib.ptr(status), _lib.stream_ptr(dev)))
         bits = int(status.item())
     if bits:
@@ -271,14 +313,11 @@ def similarity_sparse(xr, w, n_y, name, min_support=1, accumulators=False):
     """similarity() from the x-major CSR xr = (xr_ptr, xr_y, xr_r) of csr_by_x: the same return value, the same bytes, and
     no n_x * n_y limit.  The CSR is checked first; a malformed one is a ValueError."""
     _require_gpu()
-    if len(xr) != 3 or xr[0].dtype != torch.int64 or xr[1].dtype != torch.int32 or xr[2].dtype != torch.float64:
-        raise ValueError("similarity_sparse: xr must be (int64 ptr, int32 y, fp64 r)")
-    n_x, n = xr[0].numel() - 1, xr[1].numel()
-    if n_x < 1 or xr[2].numel() != n or w.numel() != int(n_y):
-        raise ValueError("similarity_sparse: %d rows, %d y, %d r, %d weights for n_y = %d"
-                         % (n_x, n, xr[2].numel(), w.numel(), n_y))
+    fn = "eccknn.similarity_sparse"
+    p_xr, n, dev = _csr_ptrs(fn, "xr", xr, None, ("ptr", "y", "r"))
+    n_x = xr[0].numel() - 1
+    p_w = _lib.tensor(fn, "w", w, torch.float64, dev, int(n_y))
     csr_check(xr, n_y)
-    dev = xr[2].device
     lib = _lib.load()
     with torch.cuda.device(dev):
         sim = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
@@ -287,8 +326,7 @@ def similarity_sparse(xr, w, n_y, name, min_support=1, accumulators=False):
             acc["freq"] = torch.empty((n_x, n_x), dtype=torch.int32, device=dev)
             for nm in (("prods", "sqi", "sqj") if name == "cosine" else ("sq_diff",)):
                 acc[nm] = torch.empty((n_x, n_x), dtype=torch.float64, device=dev)
-        _lib.check(lib.n2v_eccknn_sim_sparse(_lib.ptr(xr[0]), _lib.ptr(xr[1]) if n else None, _lib.ptr(xr[2]) if n else None,
-                                             n_x, int(n_y), n, _lib.ptr(w), _METHOD[name], int(min_support), _lib.ptr(sim),
+        _lib.check(lib.n2v_eccknn_sim_sparse(*p_xr, n_x, int(n_y), n, p_w, _METHOD[name], int(min_support), _lib.ptr(sim),
                                              _lib.ptr(acc.get("freq")), _lib.ptr(acc.get("prods")), _lib.ptr(acc.get("sqi")),
                                              _lib.ptr(acc.get("sqj")), _lib.ptr(acc.get("sq_diff")), _lib.stream_ptr(dev)))
     return (sim, acc) if accumulators else sim
@@ -339,13 +377,16 @@ def _pearson_outputs(name, n_x, dev, accumulators):
     return sim, acc, [_lib.ptr(sim), _lib.ptr(acc.get("freq")), _lib.ptr(acc.get("prods"))] + a[:4]
 
 
-def _pearson_inputs(name, n_x, n_y, w, bx, by):
+def _pearson_inputs(fn, name, n_x, n_y, w, bx, by, dev):
+    """(w, bx, by) pointers: fp64 w[n_y] or None, and fp64 bx[n_x], by[n_y], which pearson_baseline needs and pearson
+    does not read."""
     if name not in _PEARSON_KIND:
         raise NameError("Wrong sim name " + str(name) + ". Allowed values are " + ", ".join(_PEARSON_KIND) + ".")
-    if w is not None and w.numel() != int(n_y):
-        raise ValueError("similarity_pearson: %d weights for n_y = %d" % (w.numel(), n_y))
-    if name == "pearson_baseline" and (bx is None or by is None or bx.numel() != int(n_x) or by.numel() != int(n_y)):
+    ptrs = [_lib.tensor(fn, "w (the weights)", w, torch.float64, dev, int(n_y), optional=True)]
+    if name == "pearson_baseline" and (bx is None or by is None):
         raise ValueError("similarity_pearson: pearson_baseline needs bx[%d] and by[%d]" % (n_x, n_y))
+    return ptrs + [_lib.tensor(fn, "bx", bx, torch.float64, dev, int(n_x), optional=True),
+                   _lib.tensor(fn, "by", by, torch.float64, dev, int(n_y), optional=True)]
 
 
 def similarity_pearson(dense, mask, name, w=None, min_support=1, global_mean=0.0, bx=None, by=None, shrinkage=100,
@@ -353,14 +394,13 @@ def similarity_pearson(dense, mask, name, w=None, min_support=1, global_mean=0.0
     """similarity() for "pearson" and "pearson_baseline" (n2v_eccknn_pearson).  w None: no weights.  The accumulators are
     freq, prods and sqi / sqj / si / sj, or sq_diff_i / sq_diff_j.  pearson_baseline needs global_mean, bx[n_x], by[n_y]."""
     _require_gpu()
-    n_y, n_x = dense.shape
-    _pearson_inputs(name, n_x, n_y, w, bx, by)
-    dev = dense.device
+    p_dense, p_mask, n_x, n_y, dev = _dense_ptrs("eccknn.similarity_pearson", dense, mask)
+    p_w, p_bx, p_by = _pearson_inputs("eccknn.similarity_pearson", name, n_x, n_y, w, bx, by, dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
         sim, acc, outs = _pearson_outputs(name, n_x, dev, accumulators)
-        _lib.check(lib.n2v_eccknn_pearson(_lib.ptr(dense), _lib.ptr(mask), n_x, n_y, _lib.ptr(w), _PEARSON_KIND[name],
-                                          int(min_support), float(global_mean), _lib.ptr(bx), _lib.ptr(by), float(shrinkage),
+        _lib.check(lib.n2v_eccknn_pearson(p_dense, p_mask, n_x, n_y, p_w, _PEARSON_KIND[name],
+                                          int(min_support), float(global_mean), p_bx, p_by, float(shrinkage),
                                           *outs, _lib.stream_ptr(dev)))
     return (sim, acc) if accumulators else sim
 
@@ -370,21 +410,17 @@ def similarity_pearson_sparse(xr, n_y, name, w=None, min_support=1, global_mean=
     """similarity_pearson() from the x-major CSR of csr_by_x: the same bytes, no n_x * n_y limit.  The CSR is checked
     first; a malformed one is a ValueError."""
     _require_gpu()
-    if len(xr) != 3 or xr[0].dtype != torch.int64 or xr[1].dtype != torch.int32 or xr[2].dtype != torch.float64:
-        raise ValueError("similarity_pearson_sparse: xr must be (int64 ptr, int32 y, fp64 r)")
-    n_x, n = xr[0].numel() - 1, xr[1].numel()
-    if n_x < 1 or xr[2].numel() != n:
-        raise ValueError("similarity_pearson_sparse: %d rows, %d y, %d r" % (n_x, n, xr[2].numel()))
-    _pearson_inputs(name, n_x, n_y, w, bx, by)
+    fn = "eccknn.similarity_pearson_sparse"
+    p_xr, n, dev = _csr_ptrs(fn, "xr", xr, None, ("ptr", "y", "r"))
+    n_x = xr[0].numel() - 1
+    p_w, p_bx, p_by = _pearson_inputs(fn, name, n_x, n_y, w, bx, by, dev)
     csr_check(xr, n_y)
-    dev = xr[2].device
     lib = _lib.load()
     with torch.cuda.device(dev):
         sim, acc, outs = _pearson_outputs(name, n_x, dev, accumulators)
-        _lib.check(lib.n2v_eccknn_pearson_sparse(_lib.ptr(xr[0]), _lib.ptr(xr[1]) if n else None,
-                                                 _lib.ptr(xr[2]) if n else None, n_x, int(n_y), n, _lib.ptr(w),
-                                                 _PEARSON_KIND[name], int(min_support), float(global_mean), _lib.ptr(bx),
-                                                 _lib.ptr(by), float(shrinkage), *outs, _lib.stream_ptr(dev)))
+        _lib.check(lib.n2v_eccknn_pearson_sparse(*p_xr, n_x, int(n_y), n, p_w, _PEARSON_KIND[name], int(min_support),
+                                                 float(global_mean), p_bx, p_by, float(shrinkage), *outs,
+                                                 _lib.stream_ptr(dev)))
     return (sim, acc) if accumulators else sim
 
 
@@ -401,15 +437,17 @@ def row_moments(ptr, r, zero_sigma=None):
     population sigma, both sums sequential in list order (n2v_eccknn_row_moments).  An empty row is NaN.  zero_sigma: what
     replaces a sigma equal to 0.0; None leaves it.  surprise's overall sigma is row_moments(tensor([0, n]), r)[1]."""
     _require_gpu()
-    if ptr.dtype != torch.int64 or r.dtype != torch.float64 or ptr.dim() != 1 or r.dim() != 1 or ptr.numel() < 2:
+    dev = _lib.call_device("eccknn.row_moments", "r", r)
+    p_r = _lib.tensor("eccknn.row_moments", "r", r, torch.float64, dev, (None,))
+    p_ptr = _lib.tensor("eccknn.row_moments", "ptr", ptr, torch.int64, dev, (None,))
+    if ptr.numel() < 2:
         raise ValueError("row_moments: ptr must be int64[n_rows + 1] with n_rows >= 1, r fp64[n]")
-    dev = r.device
     lib = _lib.load()
     n_rows, n = ptr.numel() - 1, r.numel()
     with torch.cuda.device(dev):
         mu = torch.empty(n_rows, dtype=torch.float64, device=dev)
         sd = torch.empty(n_rows, dtype=torch.float64, device=dev)
-        _lib.check(lib.n2v_eccknn_row_moments(_lib.ptr(ptr), _lib.ptr(r) if n else None, n_rows, n,
+        _lib.check(lib.n2v_eccknn_row_moments(p_ptr, p_r if n else None, n_rows, n,
                                               float("nan") if zero_sigma is None else float(zero_sigma), _lib.ptr(mu),
                                               _lib.ptr(sd), _lib.stream_ptr(dev)))
     return mu, sd
@@ -422,18 +460,15 @@ class Centering(collections.namedtuple("Centering", "mode user_based global_mean
     __slots__ = ()
 
 
-def _centering_args(c, n_x, n_y):
-    """(code, tx, sd, by pointers) after the host checks; a table the mode reads must be there and of the right length."""
+def _centering_args(c, n_x, n_y, fn="centering", dev=None):
+    """(code, tx, sd, by pointers) after the host checks; a table the mode reads must be there, fp64, on `dev` and of the
+    right length.  A table the mode does not read is not passed on."""
     if not isinstance(c, Centering) or c.mode not in CENTERINGS:
         raise ValueError("centering: a Centering whose mode is one of %s" % ", ".join(CENTERINGS))
     need = {"means": (("tx", n_x),), "zscore": (("tx", n_x), ("sd", n_x)), "baseline": (("tx", n_x), ("by", n_y))}[c.mode]
-    for name, length in need:
-        t = getattr(c, name)
-        if t is None or t.dtype != torch.float64 or t.numel() != int(length):
-            raise ValueError("centering %s: %s must be a device fp64 tensor of %d entries" % (c.mode, name, length))
-    used = dict(need)
-    return (CENTERINGS[c.mode], _lib.ptr(c.tx), _lib.ptr(c.sd) if "sd" in used else None,
-            _lib.ptr(c.by) if "by" in used else None)
+    used = {name: _lib.tensor(fn, "centering.%s (mode %s)" % (name, c.mode), getattr(c, name), torch.float64, dev, int(length))
+            for name, length in need}
+    return CENTERINGS[c.mode], used["tx"], used.get("sd"), used.get("by")
 
 
 def yr_check(yr, n_x):
@@ -441,39 +476,46 @@ def yr_check(yr, n_x):
     estimates index their tables with yr's x ids.  The lists are in training order, not ascending, so csr_check does not
     apply; a minimum and a maximum on the device are enough."""
     _require_gpu()
-    if len(yr) != 3 or yr[0].dtype != torch.int64 or yr[1].dtype != torch.int32 or yr[2].dtype != torch.float64:
-        raise ValueError("yr must be (int64 ptr, int32 x, fp64 r)")
+    _, n, _ = _csr_ptrs("eccknn.yr_check", "yr", yr, None, ("ptr", "x", "r"))
     ptr_, xs, rs = yr
-    n = xs.numel()
-    if ptr_.numel() < 2 or rs.numel() != n:
-        raise ValueError("yr: %d ptr entries, %d x, %d r" % (ptr_.numel(), n, rs.numel()))
     if int(ptr_[0].item()) != 0 or int(ptr_[-1].item()) != n or bool((ptr_[1:] < ptr_[:-1]).any().item()):
         raise ValueError("yr: malformed lists: ptr is not monotone from 0 to %d" % n)
     if n and (int(xs.min().item()) < 0 or int(xs.max().item()) >= int(n_x)):
         raise ValueError("yr: malformed lists: an x outside [0, %d)" % n_x)
 
 
+def _knn_model(fn, sim, yr):
+    """([sim, n_x, yr_ptr, yr_x, yr_r, n_y] as the k-NN entry points take them, n_x, n_y, device): sim fp64 [n_x][n_x] on a
+    GPU, which is the device of the call, and the rating lists yr on it."""
+    dev = _lib.call_device(fn, "sim", sim)
+    n_x = sim.shape[0] if sim.dim() else 0
+    p_sim = _lib.tensor(fn, "sim", sim, torch.float64, dev, (n_x, n_x))
+    p_yr, _, _ = _csr_ptrs(fn, "yr", yr, dev, ("ptr", "x", "r"))
+    n_y = yr[0].numel() - 1
+    return [p_sim, n_x] + p_yr + [n_y], n_x, n_y, dev
+
+
 def _estimate_batch(sim, yr, qx, qy, k, min_k, centering, check):
     """The one body of estimate_batch (centering _PLAIN: n2v_eccknn_estimate) and estimate_batch_centered."""
     _require_gpu()
     k, min_k = _knn_options(k, min_k)
+    fn = "eccknn.estimate_batch" if centering is _PLAIN else "eccknn.estimate_batch_centered"
+    model, n_x, n_y, dev = _knn_model(fn, sim, yr)
+    p_qx, p_qy = _queries_ptrs(fn, qx, qy, dev)
     n_q = _query_count(qx, qy)
-    n_x, n_y = sim.shape[0], yr[0].numel() - 1
-    model = [_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y, _lib.ptr(qx), _lib.ptr(qy), n_q, k,
-             min_k]
+    model += [p_qx, p_qy, n_q, k, min_k]
     if centering is not _PLAIN:
-        code, tx, sd, by = _centering_args(centering, n_x, n_y)
+        code, tx, sd, by = _centering_args(centering, n_x, n_y, fn, dev)
         if check:
             yr_check(yr, n_x)
         model += [code, 1 if centering.user_based else 0, float(centering.global_mean), tx, sd, by]
-    dev = sim.device
     lib = _lib.load()
     with torch.cuda.device(dev):
         est = torch.empty(n_q, dtype=torch.float64, device=dev)
         actual_k = torch.empty(n_q, dtype=torch.int32, device=dev)
         imp = torch.empty(n_q, dtype=torch.uint8, device=dev)
-        fn = lib.n2v_eccknn_estimate if centering is _PLAIN else lib.n2v_eccknn_estimate_centered
-        _lib.check(fn(*model, _lib.ptr(est), _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
+        entry = lib.n2v_eccknn_estimate if centering is _PLAIN else lib.n2v_eccknn_estimate_centered
+        _lib.check(entry(*model, _lib.ptr(est), _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
     return est, actual_k, imp
 
 
@@ -485,14 +527,19 @@ def estimate_batch_centered(sim, yr, qx, qy, k, min_k, centering, check=True):
 
 
 def predict(est, impossible, global_mean, rating_scale, r_true=None):
-    """pred (device fp64), and the rmse (a Python float) when r_true is given."""
+    """pred (device fp64), and the rmse (a Python float) when r_true is given.  est: device fp64 [n]; impossible: device
+    uint8 [n], the type the estimate calls return (a bool tensor is refused although it has the same bytes: pass
+    impossible.view(torch.uint8)); r_true: device fp64 [n] or None."""
     _require_gpu()
-    dev = est.device
+    dev = _lib.call_device("eccknn.predict", "est", est)
+    p_est = _lib.tensor("eccknn.predict", "est", est, torch.float64, dev, (None,))
+    p_imp = _lib.tensor("eccknn.predict", "impossible", impossible, torch.uint8, dev, est.numel())
+    p_true = _lib.tensor("eccknn.predict", "r_true", r_true, torch.float64, dev, est.numel(), optional=True)
     lib = _lib.load()
     with torch.cuda.device(dev):
         pred = torch.empty_like(est)
         out = torch.zeros(1, dtype=torch.float64, device=dev) if r_true is not None else None
-        _lib.check(lib.n2v_eccknn_predict(_lib.ptr(est), _lib.ptr(impossible), _lib.ptr(r_true), est.numel(), float(global_mean),
+        _lib.check(lib.n2v_eccknn_predict(p_est, p_imp, p_true, est.numel(), float(global_mean),
                                           float(rating_scale[0]), float(rating_scale[1]), _lib.ptr(pred), _lib.ptr(out),
                                           _lib.stream_ptr(dev)))
     return (pred, float(out.item())) if r_true is not None else pred
@@ -531,23 +578,23 @@ def estimate_sweep(sim, yr, qx, qy, ks, min_ks, centering=None, check=True):
     is checked first as there; check False: the caller has run yr_check on these lists."""
     ks, min_ks = sweep_options(ks, min_ks)
     _require_gpu()
+    model, n_x, n_y, dev = _knn_model("eccknn.estimate_sweep", sim, yr)
+    p_qx, p_qy = _queries_ptrs("eccknn.estimate_sweep", qx, qy, dev)
     n_q = _query_count(qx, qy)
-    n_x, n_y = sim.shape[0], yr[0].numel() - 1
     n_k, n_m = len(ks), len(min_ks)
     tail = []
     if centering is not None:
-        code, tx, sd, by = _centering_args(centering, n_x, n_y)
+        code, tx, sd, by = _centering_args(centering, n_x, n_y, "eccknn.estimate_sweep", dev)
         if check:
             yr_check(yr, n_x)
         tail = [code, 1 if centering.user_based else 0, float(centering.global_mean), tx, sd, by]
-    dev = sim.device
     lib = _lib.load()
     with torch.cuda.device(dev):
         est = torch.empty((n_k, n_m, n_q), dtype=torch.float64, device=dev)
         actual_k = torch.empty((n_k, n_q), dtype=torch.int32, device=dev)
         imp = torch.empty((n_k, n_m, n_q), dtype=torch.uint8, device=dev)
         fn = lib.n2v_eccknn_estimate_sweep if centering is None else lib.n2v_eccknn_estimate_sweep_centered
-        _lib.check(fn(_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y, _lib.ptr(qx), _lib.ptr(qy), n_q,
+        _lib.check(fn(*model, p_qx, p_qy, n_q,
                       (_lib.C.c_int32 * n_k)(*ks), n_k, (_lib.C.c_int32 * n_m)(*min_ks), n_m, *tail, _lib.ptr(est),
                       _lib.ptr(actual_k), _lib.ptr(imp), _lib.stream_ptr(dev)))
     return est, actual_k, imp
@@ -558,17 +605,18 @@ def errors(pred, r_true):
     against r_true, device fp64 [n_q] (n2v_eccknn_errors): both sums in query order, the rmse of a column the bits
     predict() gives for it."""
     _require_gpu()
-    if pred.dim() == 1:
+    dev = _lib.call_device("eccknn.errors", "pred", pred)
+    if pred.dim() == 1 and pred.is_contiguous():
         pred = pred.view(1, -1)
-    if pred.dim() != 2 or pred.dtype != torch.float64 or r_true.dtype != torch.float64 or pred.numel() == 0 \
-            or r_true.dim() != 1 or r_true.numel() != pred.shape[1]:
+    p_pred = _lib.tensor("eccknn.errors", "pred", pred, torch.float64, dev, (None, None))
+    p_true = _lib.tensor("eccknn.errors", "r_true", r_true, torch.float64, dev, pred.shape[1])
+    if pred.numel() == 0:
         raise ValueError("errors: pred must be fp64 [n_cols][n_q] or [n_q] and r_true fp64 [n_q], n_q >= 1")
-    dev = pred.device
     lib = _lib.load()
     n_cols, n_q = pred.shape
     with torch.cuda.device(dev):
         out = torch.empty((2, n_cols), dtype=torch.float64, device=dev)
-        _lib.check(lib.n2v_eccknn_errors(_lib.ptr(pred), _lib.ptr(r_true), n_q, n_cols, _lib.ptr(out[0]), _lib.ptr(out[1]),
+        _lib.check(lib.n2v_eccknn_errors(p_pred, p_true, n_q, n_cols, _lib.ptr(out[0]), _lib.ptr(out[1]),
                                          _lib.stream_ptr(dev)))
         out = out.cpu().numpy()
     return out[0].copy(), out[1].copy()
@@ -602,9 +650,11 @@ def threshold_option(threshold):
 
 
 def _topn_inputs(seen, n_users, n_items, owners, dev):
-    """The checked seen CSR and the int32 owners on `dev` (every user when owners is None)."""
-    if len(seen) < 2 or seen[0].dtype != torch.int64 or seen[1].dtype != torch.int32:
+    """(the pointers of the checked seen CSR, its length, the int32 owners on `dev` (every user when owners is None))."""
+    if not isinstance(seen, (tuple, list)) or len(seen) < 2 or getattr(seen[0], "dtype", None) != torch.int64 \
+            or getattr(seen[1], "dtype", None) != torch.int32:
         raise ValueError("top_n: seen must be (int64 ptr, int32 item[, r]), the CSR of csr_by_x(u, i, r, n_users, n_items)")
+    p_seen, n_seen, _ = _csr_ptrs("top_n", "seen", seen, dev, ("ptr", "item"))
     if seen[0].numel() != int(n_users) + 1:
         raise ValueError("top_n: seen has %d rows for %d users" % (seen[0].numel() - 1, n_users))
     csr_check(seen, n_items)
@@ -613,23 +663,23 @@ def _topn_inputs(seen, n_users, n_items, owners, dev):
     owners = torch.as_tensor(owners).to(device=dev, dtype=torch.int32).contiguous()
     if owners.dim() != 1 or owners.numel() == 0:
         raise ValueError("top_n: owners must be a non-empty list of inner user ids")
-    return owners
+    return p_seen, n_seen, owners
 
 
 def _topn_call(fn, head, mid, tail, seen, n_users, n_items, owners, global_mean, rating_scale, n, segments, dev):
     """What the top_n of every predictor does after its own checks: the checked seen CSR and owners, the segment count,
     the buffers, and the one C call fn(*head, seen, owners, *mid, fallback, scale, n, S, *tail, buffers, stream),
     where fn is the library's function and head, mid and tail are the model's own arguments.  n and segments are topn_options'."""
-    owners = _topn_inputs(seen, n_users, n_items, owners, dev)
+    p_seen, n_seen, owners = _topn_inputs(seen, n_users, n_items, owners, dev)
     lib = _lib.load()
-    n_owners, n_seen = owners.numel(), seen[1].numel()
+    n_owners = owners.numel()
     S = segments or int(lib.n2v_topn_segments(n_owners, n_items))
     with torch.cuda.device(dev):
         part_score = torch.empty((n_owners, S, n), dtype=torch.float64, device=dev)
         part_pos = torch.empty((n_owners, S, n), dtype=torch.int32, device=dev)
         items = torch.empty((n_owners, n), dtype=torch.int32, device=dev)
         score = torch.empty((n_owners, n), dtype=torch.float64, device=dev)
-        _lib.check(fn(*head, _lib.ptr(seen[0]), _lib.ptr(seen[1]) if n_seen else None, n_seen, _lib.ptr(owners), n_owners,
+        _lib.check(fn(*head, *p_seen, n_seen, _lib.ptr(owners), n_owners,
                       *mid, float(global_mean), float(rating_scale[0]), float(rating_scale[1]), n, S, *tail,
                       _lib.ptr(part_score), _lib.ptr(part_pos), _lib.ptr(items), _lib.ptr(score), _lib.stream_ptr(dev)))
     return items, score
@@ -640,18 +690,19 @@ def _top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, ow
     n, segments = topn_options(n, segments)
     _require_gpu()
     k, min_k = _knn_options(k, min_k)
-    n_x, n_y = sim.shape[0], yr[0].numel() - 1
+    name = "eccknn.top_n" if centering is _PLAIN else "eccknn.top_n_centered"
+    model, n_x, n_y, dev = _knn_model(name, sim, yr)
     tail = []
     if centering is not _PLAIN:
-        tail = list(_centering_args(centering, n_x, n_y))
+        tail = list(_centering_args(centering, n_x, n_y, name, dev))
         user_based, global_mean = bool(centering.user_based), centering.global_mean
         if check:
             yr_check(yr, n_x)
     n_users, n_items = (n_x, n_y) if user_based else (n_y, n_x)
-    head = [_lib.ptr(sim), n_x, _lib.ptr(yr[0]), _lib.ptr(yr[1]), _lib.ptr(yr[2]), n_y, 1 if user_based else 0]
+    head = model + [1 if user_based else 0]
     fn = _lib.load().n2v_eccknn_topn if centering is _PLAIN else _lib.load().n2v_eccknn_topn_centered
     return _topn_call(fn, head, [k, min_k], tail, seen, n_users, n_items, owners, global_mean, rating_scale, n, segments,
-                      sim.device)
+                      dev)
 
 
 def top_n(sim, yr, seen, user_based, k, min_k, global_mean, rating_scale, n, owners=None, segments=None):

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .eccknn import PredictionImpossible  # noqa: F401  (what estimate raises)
-from .eccknn import _csr_to_device, _require_gpu, _to_device
+from .eccknn import _csr_ptrs, _csr_to_device, _require_gpu, _to_device
 from .svd import MAX_FACTORS, SVD
 
 LISTS_BAD = ((1, "a ptr does not start at 0, is not monotone or leaves [0, n]"), (2, "a ptr does not end at n"),
@@ -33,13 +33,11 @@ LISTS_BAD = ((1, "a ptr does not start at 0, is not monotone or leaves [0, n]"),
 # ---- C-ABI wrappers (device tensors in, device tensors out) -----------------------------------------------------------
 
 def _check_triple(what, triple):
-    """What the host can see of a list: types and lengths.  Returns n."""
-    p, ids, r = triple
-    if p.dtype != torch.int64 or ids.dtype != torch.int32 or r.dtype != torch.float64:
+    """What the host can see of a list: a tuple of three GPU tensors of the types above, ids and r of one length.
+    Returns n."""
+    if not isinstance(triple, (tuple, list)) or len(triple) != 3:
         raise ValueError("nmf: the %s list must be (int64 ptr, int32 ids, fp64 r)" % what)
-    if r.numel() != ids.numel() or p.numel() < 2:
-        raise ValueError("nmf: the %s list has %d ptr entries, %d ids and %d ratings" % (what, p.numel(), ids.numel(), r.numel()))
-    return ids.numel()
+    return _csr_ptrs("nmf", {"user-major": "ur", "item-major": "ir"}[what], triple)[1]
 
 
 def item_major(ur, n_items):
@@ -80,12 +78,18 @@ class Lists:
         if n < 1 or n_users < 1 or n_items < 1 or ur[0].numel() != n_users + 1 or ir[0].numel() != n_items + 1:
             raise ValueError("nmf: %d ratings, %d user ptr entries for %d users, %d item ptr entries for %d items"
                              % (n, ur[0].numel(), n_users, ir[0].numel(), n_items))
-        dev = ur[2].device
+        p_ur, _, dev = _csr_ptrs("nmf.Lists", "ur", ur)
+        p_ir, _, _ = _csr_ptrs("nmf.Lists", "ir", ir, dev)
+        if not isinstance(order, str):
+            if not isinstance(order, (tuple, list)) or len(order) != 2:
+                raise ValueError("nmf: order tables must be int32[n_users] and int32[n_items]")
+            for j, k in enumerate((n_users, n_items)):
+                _lib.tensor("nmf.Lists", "order[%d]" % j, order[j], torch.int32, dev, k, optional=True)
         lib = _lib.load()
         with torch.cuda.device(dev):
             status = torch.zeros(1, dtype=torch.int32, device=dev)
             scratch = torch.empty(n_users + n_items, dtype=torch.int32, device=dev)
-            _lib.check(lib.n2v_nmf_lists_check(_lib.ptr(ur[0]), _lib.ptr(ur[1]), _lib.ptr(ir[0]), _lib.ptr(ir[1]), n_users,
+            _lib.check(lib.n2v_nmf_lists_check(p_ur[0], p_ur[1], p_ir[0], p_ir[1], n_users,
                                                n_items, n, _lib.ptr(scratch), _lib.ptr(status), _lib.stream_ptr(dev)))
             bits = int(status.item())
             if bits:
@@ -94,8 +98,6 @@ class Lists:
                 order = (row_order(ur[0]), row_order(ir[0]))
             elif order == "identity":
                 order = (None, None)
-            elif any(o is not None and (o.dtype != torch.int32 or o.numel() != k) for o, k in zip(order, (n_users, n_items))):
-                raise ValueError("nmf: order tables must be int32[n_users] and int32[n_items]")
         self.ur, self.ir, self.order = tuple(ur), tuple(ir), tuple(order)
         self.n_users, self.n_items, self.n = n_users, n_items, n
 
@@ -121,19 +123,20 @@ def epoch(lists_, reg_pu, reg_qi, pu, qi, pu_out, qi_out):
     _require_gpu()
     if not isinstance(lists_, Lists):
         raise TypeError("nmf.epoch: lists must be a checked nmf.Lists")
+    dev = _lib.call_device("nmf.epoch", "pu", pu)
+    if lists_.ur[2].device != dev:
+        raise ValueError("nmf.epoch: lists are on %s, pu on %s" % (lists_.ur[2].device, dev))
+    tables = [_lib.tensor("nmf.epoch", "pu", pu, torch.float64, dev, (lists_.n_users, None))]
     n_factors = pu.shape[1]
-    for name, t, rows in (("pu", pu, lists_.n_users), ("qi", qi, lists_.n_items), ("pu_out", pu_out, lists_.n_users),
-                          ("qi_out", qi_out, lists_.n_items)):
-        if t.dtype != torch.float64 or tuple(t.shape) != (rows, n_factors) or not t.is_contiguous():
-            raise ValueError("nmf.epoch: %s %s %s, expected contiguous fp64 (%d, %d)" % (name, t.dtype, tuple(t.shape), rows, n_factors))
+    tables += [_lib.tensor("nmf.epoch", name, t, torch.float64, dev, (rows, n_factors))
+               for name, t, rows in (("qi", qi, lists_.n_items), ("pu_out", pu_out, lists_.n_users), ("qi_out", qi_out, lists_.n_items))]
     if any(_overlaps(o, t) for o in (pu_out, qi_out) for t in (pu, qi)) or _overlaps(pu_out, qi_out):
         raise ValueError("nmf.epoch: aliased tables: an output table overlaps an input table or the other output")
-    dev = pu.device
     lib = _lib.load()
     with torch.cuda.device(dev):
         _lib.check(lib.n2v_nmf_epoch(*[_lib.ptr(t) for t in lists_.ur + lists_.ir + lists_.order], lists_.n_users,
-                                     lists_.n_items, lists_.n, int(n_factors), float(reg_pu), float(reg_qi), _lib.ptr(pu),
-                                     _lib.ptr(qi), _lib.ptr(pu_out), _lib.ptr(qi_out), _lib.stream_ptr(dev)))
+                                     lists_.n_items, lists_.n, int(n_factors), float(reg_pu), float(reg_qi), *tables,
+                                     _lib.stream_ptr(dev)))
 
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------

@@ -18,8 +18,9 @@ Everything is fp64.  There is no CPU fallback.
 import torch
 
 from . import _lib
-from .eccknn import (PredictionImpossible, Predictor, _csr_to_device, _query_count, _require_gpu, _to_device, _topn_call,
-                     choose_form, csr_by_x, csr_check, densify, row_moments, topn_options, yr_check, FORMS)
+from .eccknn import (PredictionImpossible, Predictor, _csr_ptrs, _csr_to_device, _dense_ptrs, _queries_ptrs, _query_count,
+                     _require_gpu, _to_device, _topn_call, choose_form, csr_by_x, csr_check, densify, row_moments,
+                     topn_options, yr_check, FORMS)
 
 MAX_TABLE = 1 << 31              # elements of dev: n_items * n_items
 
@@ -44,13 +45,13 @@ def _table(n_items, dev_, accumulators):
 def deviations(dense, mask, accumulators=False):
     """(dev fp64, freq int32) [n_items][n_items] from eccknn.densify(items, users, r, n_items, n_users)
     (n2v_slopeone_dev); with accumulators also acc, the raw sums."""
-    n_users, n_items = dense.shape
-    check_items(n_items)
+    if isinstance(dense, torch.Tensor) and dense.dim() == 2:
+        check_items(dense.shape[1])                             # host arithmetic, before the GPU is asked for
     _require_gpu()
-    d = dense.device
+    p_dense, p_mask, n_items, n_users, d = _dense_ptrs("slopeone.deviations", dense, mask)
     with torch.cuda.device(d):
         dev, freq, acc = _table(n_items, d, accumulators)
-        _lib.check(_lib.load().n2v_slopeone_dev(_lib.ptr(dense), _lib.ptr(mask), n_items, n_users, _lib.ptr(dev), _lib.ptr(freq),
+        _lib.check(_lib.load().n2v_slopeone_dev(p_dense, p_mask, n_items, n_users, _lib.ptr(dev), _lib.ptr(freq),
                                                 _lib.ptr(acc), _lib.stream_ptr(d)))
     return (dev, freq, acc) if accumulators else (dev, freq)
 
@@ -58,50 +59,48 @@ def deviations(dense, mask, accumulators=False):
 def deviations_sparse(xr, n_users, accumulators=False):
     """deviations() from the item-major CSR xr = eccknn.csr_by_x(items, users, r, n_items, n_users): the same bytes, no
     n_items * n_users limit (n2v_slopeone_dev_sparse).  The CSR is checked first; a malformed one is a ValueError."""
-    if len(xr) != 3 or xr[0].dtype != torch.int64 or xr[1].dtype != torch.int32 or xr[2].dtype != torch.float64:
-        raise ValueError("deviations_sparse: xr must be (int64 ptr, int32 user, fp64 r)")
-    n_items, n = xr[0].numel() - 1, xr[1].numel()
-    check_items(n_items)
-    if xr[2].numel() != n:
-        raise ValueError("deviations_sparse: %d rows, %d users, %d r" % (n_items, n, xr[2].numel()))
+    if isinstance(xr, (tuple, list)) and len(xr) == 3 and isinstance(xr[0], torch.Tensor):
+        check_items(xr[0].numel() - 1)                          # host arithmetic, before the GPU is asked for
     _require_gpu()
+    p_xr, n, d = _csr_ptrs("slopeone.deviations_sparse", "xr", xr, None, ("ptr", "user", "r"))
+    n_items = xr[0].numel() - 1
     csr_check(xr, n_users)
-    d = xr[2].device
     with torch.cuda.device(d):
         dev, freq, acc = _table(n_items, d, accumulators)
-        _lib.check(_lib.load().n2v_slopeone_dev_sparse(_lib.ptr(xr[0]), _lib.ptr(xr[1]) if n else None,
-                                                       _lib.ptr(xr[2]) if n else None, n_items, int(n_users), n, _lib.ptr(dev),
+        _lib.check(_lib.load().n2v_slopeone_dev_sparse(*p_xr, n_items, int(n_users), n, _lib.ptr(dev),
                                                        _lib.ptr(freq), _lib.ptr(acc), _lib.stream_ptr(d)))
     return (dev, freq, acc) if accumulators else (dev, freq)
 
 
-def _model_args(dev, freq, ur, user_mean, check):
+def _model_args(fn, dev, freq, ur, user_mean, check):
     """The model's part of the two calls below after the host checks; ur = (ptr int64[n_users + 1], item int32, r fp64) in
     training order.  check: eccknn.yr_check on ur (integers only): a malformed list is a ValueError, not a launch."""
-    n_items, n_users = dev.shape[0], ur[0].numel() - 1
+    d = _lib.call_device(fn, "dev", dev)
+    n_items = dev.shape[0] if dev.dim() else 0
+    p_dev = _lib.tensor(fn, "dev", dev, torch.float64, d, (n_items, n_items))
     check_items(n_items)
-    if tuple(dev.shape) != (n_items, n_items) or tuple(freq.shape) != (n_items, n_items) or dev.dtype != torch.float64 \
-            or freq.dtype != torch.int32 or user_mean.dtype != torch.float64 or user_mean.numel() != n_users:
-        raise ValueError("slopeone: dev fp64 and freq int32 must be [n_items][n_items], user_mean fp64[n_users = %d]" % n_users)
+    p_freq = _lib.tensor(fn, "freq", freq, torch.int32, d, (n_items, n_items))
+    p_ur, n, _ = _csr_ptrs(fn, "ur", ur, d, ("ptr", "item", "r"))
+    n_users = ur[0].numel() - 1
+    p_mean = _lib.tensor(fn, "user_mean", user_mean, torch.float64, d, n_users)
     if check:
         yr_check(ur, n_items)
-    n = ur[1].numel()
-    return [_lib.ptr(dev), _lib.ptr(freq), n_items, _lib.ptr(ur[0]), _lib.ptr(ur[1]) if n else None, n_users, n,
-            _lib.ptr(user_mean)]
+    return [p_dev, p_freq, n_items, p_ur[0], p_ur[1], n_users, n, p_mean]
 
 
 def estimate_batch(dev, freq, ur, user_mean, qu, qi, check=True):
     """(est fp64, n_deviations int32, impossible uint8) device tensors for int32 device queries, -1 = unknown
     (n2v_slopeone_estimate)."""
     _require_gpu()
-    n_q = _query_count(qu, qi, ("user", "item"))
-    model = _model_args(dev, freq, ur, user_mean, check)
+    model = _model_args("slopeone.estimate_batch", dev, freq, ur, user_mean, check)
     d = dev.device
+    p_qu, p_qi = _queries_ptrs("slopeone.estimate_batch", qu, qi, d, ("qu", "qi"))
+    n_q = _query_count(qu, qi, ("user", "item"), ("qu", "qi"))
     with torch.cuda.device(d):
         est = torch.empty(n_q, dtype=torch.float64, device=d)
         n_dev = torch.empty(n_q, dtype=torch.int32, device=d)
         imp = torch.empty(n_q, dtype=torch.uint8, device=d)
-        _lib.check(_lib.load().n2v_slopeone_estimate(*model, _lib.ptr(qu), _lib.ptr(qi), n_q, _lib.ptr(est), _lib.ptr(n_dev),
+        _lib.check(_lib.load().n2v_slopeone_estimate(*model, p_qu, p_qi, n_q, _lib.ptr(est), _lib.ptr(n_dev),
                                                      _lib.ptr(imp), _lib.stream_ptr(d)))
     return est, n_dev, imp
 
@@ -111,7 +110,7 @@ def top_n(dev, freq, ur, user_mean, seen, global_mean, rating_scale, n, owners=N
     predictions, each the bits of estimate_batch + eccknn.predict for that pair."""
     n, segments = topn_options(n, segments)
     _require_gpu()
-    model = _model_args(dev, freq, ur, user_mean, check)
+    model = _model_args("slopeone.top_n", dev, freq, ur, user_mean, check)
     return _topn_call(_lib.load().n2v_slopeone_topn, model, [], [], seen, model[5], model[2], owners, global_mean, rating_scale, n,
                       segments, dev.device)
 

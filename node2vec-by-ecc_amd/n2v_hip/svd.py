@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .eccknn import PredictionImpossible, Predictor, _query_count, _require_gpu, _to_device, _topn_call, topn_options
+from .eccknn import (PredictionImpossible, Predictor, _queries_ptrs, _query_count, _require_gpu, _to_device, _topn_call,
+                     topn_options)
 
 MAX_FACTORS = 256                # n2v_svd_max_factors()
 MAX_STRATA = 32768               # n2v_svd_max_strata()
@@ -81,20 +82,24 @@ class Blocks:
 
     def __init__(self, lists, n_users, n_items, n_strata):
         _require_gpu()
-        ptr_, bu_, bi_, br_ = lists
-        if ptr_.dtype != torch.int64 or bu_.dtype != torch.int32 or bi_.dtype != torch.int32 or br_.dtype != torch.float64:
+        if not isinstance(lists, (tuple, list)) or len(lists) != 4:
             raise ValueError("svd: block lists must be (int64 blk_ptr, int32 blk_u, int32 blk_i, fp64 blk_r)")
+        ptr_, bu_, bi_, br_ = lists
+        dev = _lib.call_device("svd.Blocks", "lists[3] (float64 blk_r)", br_)
+        p_ptr, p_u, p_i, _ = [_lib.tensor("svd.Blocks", "lists[%d] (%s blk_%s)" % (j, str(dt).replace("torch.", ""), role), t, dt,
+                                          dev, (None,))
+                              for j, (role, t, dt) in enumerate((("ptr", ptr_, torch.int64), ("u", bu_, torch.int32),
+                                                                 ("i", bi_, torch.int32), ("r", br_, torch.float64)))]
         P, n = int(n_strata), bu_.numel()
         if not 1 <= P <= MAX_STRATA:
             raise ValueError("n_strata %d outside [1, %d]" % (P, MAX_STRATA))
         if n < 1 or bi_.numel() != n or br_.numel() != n or ptr_.numel() != P * P + 1:
             raise ValueError("svd: %d blk_ptr entries for n_strata = %d, %d u, %d i, %d r"
                              % (ptr_.numel(), P, n, bi_.numel(), br_.numel()))
-        dev = br_.device
         lib = _lib.load()
         with torch.cuda.device(dev):
             status = torch.zeros(1, dtype=torch.int32, device=dev)
-            _lib.check(lib.n2v_svd_blocks_check(_lib.ptr(ptr_), _lib.ptr(bu_), _lib.ptr(bi_), P, int(n_users), int(n_items), n,
+            _lib.check(lib.n2v_svd_blocks_check(p_ptr, p_u, p_i, P, int(n_users), int(n_items), n,
                                                 _lib.ptr(status), _lib.stream_ptr(dev)))
             bits = int(status.item())
         if bits:
@@ -103,39 +108,48 @@ class Blocks:
         self.n_users, self.n_items, self.n_strata, self.n = int(n_users), int(n_items), P, n
 
 
+def _model_ptrs(fn, biased, bu, bi, pu, qi, n_users=None, n_items=None):
+    """([bu, bi, pu, qi] pointers, n_users, n_items, n_factors, device) of a factor model: fp64 pu[n_users][n_factors] on
+    a GPU, which is the device of the call, qi[n_items][n_factors], bu[n_users] and bi[n_items]; the biases may be None
+    when not biased.  n_users, n_items None: the rows of pu and qi."""
+    dev = _lib.call_device(fn, "pu", pu)
+    p_pu = _lib.tensor(fn, "pu", pu, torch.float64, dev, (n_users, None))
+    n_users, n_factors = pu.shape
+    p_qi = _lib.tensor(fn, "qi", qi, torch.float64, dev, (n_items, n_factors))
+    n_items = qi.shape[0]
+    p_bu = _lib.tensor(fn, "bu", bu, torch.float64, dev, n_users, optional=not biased)
+    p_bi = _lib.tensor(fn, "bi", bi, torch.float64, dev, n_items, optional=not biased)
+    return [p_bu, p_bi, p_pu, p_qi], n_users, n_items, n_factors, dev
+
+
 def epoch(blocks, mu, biased, rates, bu, bi, pu, qi):
     """One epoch in place (n2v_svd_epoch).  rates: the eight values lr_bu, lr_bi, lr_pu, lr_qi, reg_bu, reg_bi, reg_pu,
     reg_qi.  bu / bi may be None when not biased."""
     _require_gpu()
     if not isinstance(blocks, Blocks):
         raise TypeError("svd.epoch: blocks must be a checked svd.Blocks")
-    n_factors = pu.shape[1]
-    if tuple(pu.shape) != (blocks.n_users, n_factors) or tuple(qi.shape) != (blocks.n_items, n_factors):
-        raise ValueError("svd.epoch: pu %s, qi %s for %d users and %d items"
-                         % (tuple(pu.shape), tuple(qi.shape), blocks.n_users, blocks.n_items))
-    if biased and (bu.numel() != blocks.n_users or bi.numel() != blocks.n_items):
-        raise ValueError("svd.epoch: bu[%d], bi[%d] for %d users and %d items"
-                         % (bu.numel(), bi.numel(), blocks.n_users, blocks.n_items))
-    dev = pu.device
+    tables, _, _, n_factors, dev = _model_ptrs("svd.epoch", biased, bu, bi, pu, qi, blocks.n_users, blocks.n_items)
+    if blocks.r.device != dev:
+        raise ValueError("svd.epoch: blocks are on %s, pu on %s" % (blocks.r.device, dev))
     lib = _lib.load()
     with torch.cuda.device(dev):
         _lib.check(lib.n2v_svd_epoch(_lib.ptr(blocks.ptr), _lib.ptr(blocks.u), _lib.ptr(blocks.i), _lib.ptr(blocks.r),
                                      blocks.n_strata, blocks.n_users, blocks.n_items, blocks.n, int(n_factors), float(mu),
-                                     1 if biased else 0, *[float(v) for v in rates], _lib.ptr(bu), _lib.ptr(bi), _lib.ptr(pu),
-                                     _lib.ptr(qi), _lib.stream_ptr(dev)))
+                                     1 if biased else 0, *[float(v) for v in rates], *tables, _lib.stream_ptr(dev)))
 
 
 def estimate_batch(mu, biased, bu, bi, pu, qi, qu, qi_ids):
     """(est fp64, impossible uint8) device tensors for int32 device queries, -1 = unknown (n2v_svd_estimate)."""
     _require_gpu()
-    n_q = _query_count(qu, qi_ids, ("user", "item"))
-    dev = pu.device
+    tables, n_users, n_items, n_factors, dev = _model_ptrs("svd.estimate_batch", biased, bu, bi, pu, qi)
+    p_qu, p_qi = _queries_ptrs("svd.estimate_batch", qu, qi_ids, dev, ("qu", "qi_ids"))
+    n_q = _query_count(qu, qi_ids, ("user", "item"), ("qu", "qi_ids"))
     lib = _lib.load()
     with torch.cuda.device(dev):
         est = torch.empty(n_q, dtype=torch.float64, device=dev)
         imp = torch.empty(n_q, dtype=torch.uint8, device=dev)
-        _lib.check(lib.n2v_svd_estimate(_lib.ptr(bu), _lib.ptr(bi), _lib.ptr(pu), _lib.ptr(qi), pu.shape[0], qi.shape[0],
-                                        pu.shape[1], float(mu), 1 if biased else 0, _lib.ptr(qu), _lib.ptr(qi_ids), n_q,
+        _lib.check(lib.n2v_svd_estimate(*tables, n_users, n_items,
+                                        n_factors, float(mu), 1 if biased else 0, p_qu, p_qi, n_q,
                                         _lib.ptr(est), _lib.ptr(imp), _lib.stream_ptr(dev)))
     return est, imp
 
@@ -146,11 +160,10 @@ def top_n(mu, biased, bu, bi, pu, qi, seen, global_mean, rating_scale, n, owners
     mu the model's (0.0 when not biased)."""
     n, segments = topn_options(n, segments)
     _require_gpu()
-    n_users, n_items = pu.shape[0], qi.shape[0]
-    head = [_lib.ptr(bu), _lib.ptr(bi), _lib.ptr(pu), _lib.ptr(qi), n_users, n_items, pu.shape[1], float(mu),
-            1 if biased else 0]
+    tables, n_users, n_items, n_factors, dev = _model_ptrs("svd.top_n", biased, bu, bi, pu, qi)
+    head = tables + [n_users, n_items, n_factors, float(mu), 1 if biased else 0]
     return _topn_call(_lib.load().n2v_svd_topn, head, [], [], seen, n_users, n_items, owners, global_mean, rating_scale, n, segments,
-                      pu.device)
+                      dev)
 
 
 # ---- the algorithm ----------------------------------------------------------------------------------------------------
