@@ -108,6 +108,11 @@ def learn_embeddings(walks, **overrides):
         b, _ = _sgns.shard_bounds(overrides["n_starts"], ctx.world, ctx.rank)
         _dist.train_sharded(model, corpus.walks, corpus.lens, ctx, n_walks_global=int(tot.item()),
                             shard_offset=b * overrides["num_walks"], epochs=epochs, merge=overrides.get("merge", "tsum"))
+    return _result(corpus, model)
+
+
+def _result(corpus, model):
+    """The trained model as what learn_embeddings returns: the vectors keyed by str(node id), in gensim's order."""
     wv = _sgns.KeyedVectors(corpus.labels, model.counts, model.vectors().cpu().numpy())
     return _sgns.Word2VecResult(wv, model, model.pairs_trained())
 
@@ -126,8 +131,7 @@ def _learn_embeddings_cbow(corpus, dim, window, epochs, seed, overrides):
                             device=corpus.walks.device)
     model.build_vocab(sentences.counts)
     _cbow.train(model, sentences, epochs=epochs)
-    wv = _sgns.KeyedVectors(corpus.labels, model.counts, model.vectors().cpu().numpy())
-    return _sgns.Word2VecResult(wv, model, model.pairs_trained())
+    return _result(corpus, model)
 
 
 def main(args_):

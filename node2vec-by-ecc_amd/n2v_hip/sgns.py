@@ -136,61 +136,58 @@ def _row_stride(dim):
     raise ValueError("dimensions > 512 are not supported by the wave-per-pair kernel")
 
 
-class SgnsModel:
-    """Embedding tables + vocabulary statistics of one training run, on one device."""
+def check_window_negative(window, negative):
+    """The sizes the ragged trainers' kernels (n2v_cbow_train, n2v_sgns_csr_train) stage a window and a target group at."""
+    if int(window) < 1 or not 0 <= int(negative) <= 64:
+        raise ValueError("window must be >= 1, negative in [0, 64]")
 
-    def __init__(self, n_words, dim=128, window=10, negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3,
-                 seed=1, device=None, update_mode="auto", share_negatives=False, allow_out_of_band=False):
-        if update_mode not in ("auto",) + tuple(UPDATE_MODES):
-            raise ValueError("update_mode must be 'auto', 'atomic', 'agent' or 'plain'")
-        check_share_negatives(share_negatives, allow_out_of_band)
+
+class W2vTables:
+    """Embedding tables + vocabulary statistics of one word2vec training run, on one device: what the walk-matrix
+    trainer below and the two trainers over ragged sentences (n2v_hip/cbow.py: RaggedModel) share."""
+
+    def __init__(self, what, n_words, dim, window, negative, alpha, min_alpha, sample, seed, device):
         if not torch.cuda.is_available():
-            raise RuntimeError("n2v_hip: no GPU visible; the SGNS trainer has no CPU fallback")
+            raise RuntimeError("n2v_hip: no GPU visible; the %s trainer has no CPU fallback" % what)
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         self.n_words, self.dim = int(n_words), int(dim)
         self.stride = _row_stride(self.dim)
         self.window, self.negative = int(window), int(negative)
         self.alpha, self.min_alpha, self.sample, self.seed = float(alpha), float(min_alpha), sample, int(seed)
-        self._auto_mode = update_mode == "auto"     # resolved by build_vocab, which knows the corpus size
-        self.allow_out_of_band = bool(allow_out_of_band)
-        self._share = 4 if share_negatives else 0   # N2V_SGNS_SHARE_NEGATIVES
-        self._set_mode("atomic" if self._auto_mode else update_mode)
         d = self.device
         self.syn0 = torch.empty((self.n_words, self.stride), dtype=torch.float32, device=d)
         self.syn1neg = torch.empty((self.n_words, self.stride), dtype=torch.float32, device=d)
         self.pair_count = torch.zeros(1, dtype=torch.int64, device=d)
-        # in-order hand-out of the sentences to the wavefronts (n2v_sgns_train's work_counter); None: static grid stride
+        # in-order hand-out of the sentences to the wavefronts (the kernels' work_counter); None: static grid stride
         self.work_counter = torch.zeros(1, dtype=torch.int64, device=d)
         self.counts = None
         self.sample_int = self.cum_table = self.lut = None
         self.reset_weights()
 
-    def _set_mode(self, name):
-        self.update_mode_name = name
-        self.update_mode = UPDATE_MODES[name] | self._share
-
     def _stream(self):
         return _lib.stream_ptr(self.device)
 
+    def _tables(self):
+        """The table-and-vocabulary block every training entry point of the C-ABI takes, in its order: syn0, syn1neg,
+        n_words, dim, row_stride, window, negative, sample_int, cum_table, lut, lut_bits, alpha, min_alpha."""
+        return (_lib.ptr(self.syn0), _lib.ptr(self.syn1neg), self.n_words, self.dim, self.stride, self.window,
+                self.negative, _lib.ptr(self.sample_int), _lib.ptr(self.cum_table), _lib.ptr(self.lut), LUT_BITS,
+                self.alpha, self.min_alpha)
+
+    def _seed64(self):
+        """The seed as the C-ABI's uint64_t."""
+        return self.seed & (2**64 - 1)
+
     def reset_weights(self):
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.n2v_sgns_init(_lib.ptr(self.syn0), _lib.ptr(self.syn1neg), self.n_words, self.dim,
-                                              self.stride, self.seed & (2**64 - 1), self._stream()))
+            _lib.check(self.lib.n2v_sgns_init(*self._tables()[:5], self._seed64(), self._stream()))
 
-    def build_vocab(self, walks=None, counts=None):
-        """Word counts from a device corpus (int32 [W, L], -1 padded) or given directly."""
+    def _set_vocab(self, counts):
+        """The statistics of `counts` (int64[n_words], numpy) on the device, and the negative-draw look-up table."""
+        self.counts = counts
+        sample_int, cum = vocab_tables(counts, self.sample)
         d = self.device
-        if counts is None:
-            flat = walks.reshape(-1)
-            flat = flat[flat >= 0].long()
-            counts_t = torch.bincount(flat, minlength=self.n_words)
-        else:
-            counts_t = torch.as_tensor(counts, dtype=torch.int64, device=d)
-        self.counts = counts_t.cpu().numpy()
-        self._set_mode(resolve_update_mode("auto" if self._auto_mode else self.update_mode_name, self.n_words,
-                                           float(self.counts.sum()), self.allow_out_of_band))
-        sample_int, cum = vocab_tables(self.counts, self.sample)
         self.sample_int = None if sample_int is None else torch.from_numpy(sample_int.view(np.int32)).to(d)
         self.cum_table = torch.from_numpy(cum.view(np.int32)).to(d)
         self.lut = torch.empty((1 << LUT_BITS) + 1, dtype=torch.int32, device=d)
@@ -198,17 +195,64 @@ class SgnsModel:
             _lib.check(self.lib.n2v_build_neg_lut(_lib.ptr(self.cum_table), self.n_words, LUT_BITS,
                                                   _lib.ptr(self.lut), self._stream()))
 
+    def pairs_trained(self):
+        """What the kernels counted so far: (centre, context) pairs for the skip-gram trainers, centres for CBOW (a centre
+        without context trains nothing and is not counted)."""
+        return int(self.pair_count.item())
+
+    def vectors(self):
+        """syn0 without the padding columns (device view)."""
+        return self.syn0[:, :self.dim]
+
+
+class SgnsModel(W2vTables):
+    """Embedding tables + vocabulary statistics of one training run over a walk matrix, on one device."""
+
+    def __init__(self, n_words, dim=128, window=10, negative=5, alpha=0.025, min_alpha=1e-4, sample=1e-3,
+                 seed=1, device=None, update_mode="auto", share_negatives=False, allow_out_of_band=False):
+        if update_mode not in ("auto",) + tuple(UPDATE_MODES):
+            raise ValueError("update_mode must be 'auto', 'atomic', 'agent' or 'plain'")
+        check_share_negatives(share_negatives, allow_out_of_band)
+        W2vTables.__init__(self, "SGNS", n_words, dim, window, negative, alpha, min_alpha, sample, seed, device)
+        self._auto_mode = update_mode == "auto"     # resolved by build_vocab, which knows the corpus size
+        self.allow_out_of_band = bool(allow_out_of_band)
+        self._share = 4 if share_negatives else 0   # N2V_SGNS_SHARE_NEGATIVES
+        self._set_mode("atomic" if self._auto_mode else update_mode)
+
+    def _set_mode(self, name):
+        self.update_mode_name = name
+        self.update_mode = UPDATE_MODES[name] | self._share
+
+    def build_vocab(self, walks=None, counts=None):
+        """Word counts from a device corpus (int32 [W, L], -1 padded) or given directly."""
+        if counts is None:
+            flat = walks.reshape(-1)
+            flat = flat[flat >= 0].long()
+            counts_t = torch.bincount(flat, minlength=self.n_words)
+        else:
+            counts_t = torch.as_tensor(counts, dtype=torch.int64, device=self.device)
+        counts = counts_t.cpu().numpy()
+        self._set_mode(resolve_update_mode("auto" if self._auto_mode else self.update_mode_name, self.n_words,
+                                           float(counts.sum()), self.allow_out_of_band))
+        self._set_vocab(counts)
+
+    def _walks(self, fn, walks, lens):
+        """(walks pointer, lens pointer or NULL, n, L) of a caller's walk matrix, held to what the kernels read: int32
+        [n, L] and int32 [n], contiguous, on the model's device.  A ValueError names `fn` and the argument."""
+        wp = _lib.tensor(fn, "walks", walks, torch.int32, self.device, (None, None))
+        n, L = int(walks.shape[0]), int(walks.shape[1])
+        return wp, _lib.tensor(fn, "lens", lens, torch.int32, self.device, n, optional=True), n, L
+
     def train_pass(self, walks, lens, sentences_base, sentences_total, walk_id_base, sentences_step=1,
                    max_blocks=0, splits=1):
         """One kernel launch over `walks` (device int32 [n, L]); asynchronous.  splits: wavefronts per walk ("auto":
         as many as it takes to put ~8 192 wavefronts on the chip, for the short launches of the tiered merges)."""
-        assert walks.dtype == torch.int32 and walks.is_contiguous() and walks.device == self.device
-        n, L = int(walks.shape[0]), int(walks.shape[1])
+        wp, lp, n, L = self._walks("SgnsModel.train_pass", walks, lens)
         if n == 0:
             return
         with torch.cuda.device(self.device):
-            self._launch(_lib.ptr(walks), _lib.ptr(lens), n, L, sentences_base, sentences_step, sentences_total,
-                         walk_id_base, max_blocks, splits, self._stream())
+            self._launch(wp, lp, n, L, sentences_base, sentences_step, sentences_total, walk_id_base, max_blocks, splits,
+                         self._stream())
 
     def _launch(self, walks_ptr, lens_ptr, n, L, sentences_base, sentences_step, sentences_total, walk_id_base,
                 max_blocks, splits, stream):
@@ -216,24 +260,15 @@ class SgnsModel:
             splits = auto_splits(self.n_words, n, L)
         mode = launch_update_mode(self.update_mode, self._auto_mode, splits, self.allow_out_of_band)
         _lib.check(self.lib.n2v_sgns_train(
-            walks_ptr, lens_ptr, n, L, _lib.ptr(self.syn0), _lib.ptr(self.syn1neg), self.n_words,
-            self.dim, self.stride, self.window, self.negative, _lib.ptr(self.sample_int),
-            _lib.ptr(self.cum_table), _lib.ptr(self.lut), LUT_BITS, self.alpha, self.min_alpha,
-            int(sentences_base), int(sentences_step), int(sentences_total), max(1, MAX_WORDS_IN_BATCH // L),
-            self.seed & (2**64 - 1),
-            int(walk_id_base), _lib.ptr(self.pair_count), mode, int(max_blocks), int(splits),
-            _lib.ptr(self.work_counter), stream))
+            walks_ptr, lens_ptr, n, L, *self._tables(), int(sentences_base), int(sentences_step), int(sentences_total),
+            max(1, MAX_WORDS_IN_BATCH // L), self._seed64(), int(walk_id_base), _lib.ptr(self.pair_count), mode,
+            int(max_blocks), int(splits), _lib.ptr(self.work_counter), stream))
 
     def span_trainer(self, walks, lens, sentences_total, sentences_step, splits="auto"):
         """-> launch(b, e, sentences_base, walk_id_base): train_pass over walks[b:e] without building tensor views —
-        for drivers that issue thousands of short launches per pass (the tiered merges).  The caller holds
-        torch.cuda.device(self.device) and keeps `walks` / `lens` alive."""
-        assert walks.dtype == torch.int32 and walks.is_contiguous() and walks.device == self.device
-        L = int(walks.shape[1])
-        wp = walks.data_ptr()
-        lp = None if lens is None else lens.data_ptr()
-        if lens is not None:
-            assert lens.dtype == torch.int32 and lens.is_contiguous()
+        for drivers that issue thousands of short launches per pass (the tiered merges).  The tensors are checked
+        here, once; the caller holds torch.cuda.device(self.device) and keeps `walks` / `lens` alive."""
+        wp, lp, _, L = self._walks("SgnsModel.span_trainer", walks, lens)
         dev = self.device
 
         def launch(b, e, sentences_base, walk_id_base):
@@ -246,10 +281,10 @@ class SgnsModel:
                       shard_offset, splits):
         """-> launch(sub_index): n2v_sgns_train_span over this rank's whole shard — the walk range comes from the device
         word pair `interval_state` (int64[2]: base interval index, sentences of earlier epochs), so a captured launch
-        can be replayed for every base interval of a pass (the graph path of the tiered merges)."""
-        assert walks.dtype == torch.int32 and walks.is_contiguous() and walks.device == self.device
-        assert interval_state.dtype == torch.int64 and interval_state.numel() == 2 and interval_state.device == self.device
-        n_local, L = int(walks.shape[0]), int(walks.shape[1])
+        can be replayed for every base interval of a pass (the graph path of the tiered merges).  The tensors are
+        checked here, once."""
+        _, _, n_local, L = self._walks("SgnsModel.span_launcher", walks, lens)
+        _lib.tensor("SgnsModel.span_launcher", "interval_state", interval_state, torch.int64, self.device, 2)
         max_walks = -(-n_local // int(n_sub_total))
         if splits == "auto":
             splits = auto_splits(self.n_words, max_walks, L)
@@ -258,20 +293,11 @@ class SgnsModel:
 
         def launch(sub_index):
             _lib.check(self.lib.n2v_sgns_train_span(
-                _lib.ptr(walks), _lib.ptr(lens), n_local, L, _lib.ptr(self.syn0), _lib.ptr(self.syn1neg), self.n_words,
-                self.dim, self.stride, self.window, self.negative, _lib.ptr(self.sample_int), _lib.ptr(self.cum_table),
-                _lib.ptr(self.lut), LUT_BITS, self.alpha, self.min_alpha, int(sentences_step), int(sentences_total),
-                max(1, MAX_WORDS_IN_BATCH // L), self.seed & (2**64 - 1), _lib.ptr(self.pair_count), mode, 0, int(splits),
+                _lib.ptr(walks), _lib.ptr(lens), n_local, L, *self._tables(), int(sentences_step), int(sentences_total),
+                max(1, MAX_WORDS_IN_BATCH // L), self._seed64(), _lib.ptr(self.pair_count), mode, 0, int(splits),
                 _lib.ptr(interval_state), int(sub_index), int(subs_per_interval), int(n_sub_total), int(shard_offset),
                 _lib.ptr(self.work_counter), _lib.stream_ptr(dev)))
         return launch
-
-    def pairs_trained(self):
-        return int(self.pair_count.item())
-
-    def vectors(self):
-        """syn0 without the padding columns (device view)."""
-        return self.syn0[:, :self.dim]
 
 
 class _ProcessGroupComm:
@@ -302,12 +328,33 @@ from .merge import (  # noqa: F401
     TSUM_TIERS, TSUM_RATIO, SumTierPlan, TieredSumMerger, auto_syncs, chunk_plan, shard_bounds)
 
 
+def _clamp_chunks(n_chunks, n_walks_global, world):
+    """At least one interval per pass and at most one per walk of a shard, by the GLOBAL walk count: the same number on
+    every rank."""
+    return max(1, min(n_chunks, max(1, n_walks_global // world)))
+
+
+def walk_schedule(ep, b, n_walks_global, world=1, shard_offset=0):
+    """(sentences_base, walk_id_base) of a launch that starts at local walk `b` of pass `ep`.  All replicas advance
+    together, so `b` local sentences are b * world global ones on the learning-rate schedule; a walk's id (the seed of
+    its draws) is its global index."""
+    return ep * n_walks_global + b * world, ep * n_walks_global + shard_offset + b
+
+
+def _train_chunk(model, walks, lens, b, e, ep, n_walks_global, world, shard_offset, total, splits):
+    """train_pass over the local walks [b, e) of pass `ep`, one replica of `world`."""
+    if e > b:
+        sentences_base, walk_id_base = walk_schedule(ep, b, n_walks_global, world, shard_offset)
+        model.train_pass(walks[b:e], None if lens is None else lens[b:e], sentences_base=sentences_base,
+                         sentences_step=world, sentences_total=total, walk_id_base=walk_id_base, splits=splits)
+
+
 def _merge_setup(model, L, n_walks_global, world, syncs_per_epoch, merge, cold_delay):
     """(n_chunks, MergePlan) — everything that decides how many collectives run is derived from GLOBAL quantities,
     never from a rank's shard size."""
     n_chunks = (auto_syncs(n_walks_global * L, model.n_words, world) if syncs_per_epoch == "auto"
                 else int(syncs_per_epoch))
-    n_chunks = max(1, min(n_chunks, max(1, n_walks_global // world)))
+    n_chunks = _clamp_chunks(n_chunks, n_walks_global, world)
     plan = MergePlan(model.counts, n_walks_global * L / n_chunks, world, model.window, model.negative, model.device,
                      mode=merge, cold_delay=cold_delay)
     return n_chunks, plan
@@ -316,7 +363,7 @@ def _merge_setup(model, L, n_walks_global, world, syncs_per_epoch, merge, cold_d
 def _tsum_setup(model, L, n_walks_global, world, syncs_per_epoch):
     n_chunks = (max(1, int(np.ceil(n_walks_global * L * (world - 1) / (TSUM_STALENESS_BUDGET * max(model.n_words, 1)))))
                 if syncs_per_epoch == "auto" else int(syncs_per_epoch))
-    n_chunks = max(1, min(n_chunks, max(1, n_walks_global // world)))
+    n_chunks = _clamp_chunks(n_chunks, n_walks_global, world)
     plan = SumTierPlan(model.counts, n_walks_global * L / n_chunks, world, model.window, model.negative, model.device)
     return n_chunks, plan
 
@@ -354,7 +401,7 @@ def _train_tsum(model, walks, lens, epochs, comm, n_walks_global, shard_offset, 
     with (torch.cuda.device(model.device) if model.device.type == "cuda" else contextlib.nullcontext()):
         for ep in range(epochs):
             for c, (b, e) in enumerate(subs):
-                launch(b, e, ep * n_walks_global + b * world, ep * n_walks_global + shard_offset + b)
+                launch(b, e, *walk_schedule(ep, b, n_walks_global, world, shard_offset))
                 if due[c] is not None:
                     merger.merge(due[c])
     return merger
@@ -424,8 +471,9 @@ def train(model, walks, lens, epochs=1, comm=None, n_walks_global=None, shard_of
     world = comm.world if comm is not None else 1
     if world == 1:
         for ep in range(epochs):
-            model.train_pass(walks, lens, sentences_base=ep * n_walks_global, sentences_step=1,
-                             sentences_total=total, walk_id_base=ep * n_walks_global + shard_offset)
+            sentences_base, walk_id_base = walk_schedule(ep, 0, n_walks_global, 1, shard_offset)
+            model.train_pass(walks, lens, sentences_base=sentences_base, sentences_step=1, sentences_total=total,
+                             walk_id_base=walk_id_base)
         return None
     check_merge_in_band(merge, model.n_words, getattr(model, "allow_out_of_band", False))
     if merge == "tsum":
@@ -436,11 +484,7 @@ def train(model, walks, lens, epochs=1, comm=None, n_walks_global=None, shard_of
     chunks = chunk_plan(n_local, n_chunks, exact=True)
     for ep in range(epochs):
         for i, (b, e) in enumerate(chunks):
-            if e > b:
-                # all replicas advance together: `b` local sentences = b * world global ones
-                model.train_pass(walks[b:e], None if lens is None else lens[b:e],
-                                 sentences_base=ep * n_walks_global + b * world, sentences_step=world,
-                                 sentences_total=total, walk_id_base=ep * n_walks_global + shard_offset + b, splits="auto")
+            _train_chunk(model, walks, lens, b, e, ep, n_walks_global, world, shard_offset, total, "auto")
             merger.end_interval(last=(ep + 1 == epochs and i + 1 == len(chunks)))
     return merger
 
@@ -487,21 +531,21 @@ def train_simulated_replicas(models, shards, n_walks_global, syncs_per_epoch="au
     on a one-GPU box.  Returns the number of merges per pass."""
     G = len(models)
     L = int(shards[0][0].shape[1])
+    group = _SimGroup(G, wire_dtype)
+    total = epochs * n_walks_global
+
+    def train_interval(plans, ep, c):
+        for m, (w, l, off), chunks in zip(models, shards, plans):       # the replicas of one process: one after the other
+            b, e = chunks[c]
+            _train_chunk(m, w, l, b, e, ep, n_walks_global, G, off, total, splits)
+
     if merge == "tsum":
         n_chunks, plan = _tsum_setup(models[0], L, n_walks_global, G, syncs_per_epoch)
-        group = _SimGroup(G, wire_dtype)
         mergers = [TieredSumMerger([m.syn0, m.syn1neg], plan, group.comm()) for m in models]
         subs = [chunk_plan(int(w.shape[0]), n_chunks * plan.sub, exact=True) for w, _, _ in shards]
-        total = epochs * n_walks_global
         for ep in range(epochs):
             for c in range(n_chunks * plan.sub):
-                for r, m in enumerate(models):
-                    w, l, off = shards[r]
-                    b, e = subs[r][c]
-                    if e > b:
-                        m.train_pass(w[b:e], None if l is None else l[b:e], sentences_base=ep * n_walks_global + b * G,
-                                     sentences_step=G, sentences_total=total, walk_id_base=ep * n_walks_global + off + b,
-                                     splits=splits)
+                train_interval(subs, ep, c)
                 level = plan.level_due(c)
                 if level is None:
                     continue
@@ -512,19 +556,11 @@ def train_simulated_replicas(models, shards, n_walks_global, syncs_per_epoch="au
                     mg.apply(level, v)
         return n_chunks
     n_chunks, plan = _merge_setup(models[0], L, n_walks_global, G, syncs_per_epoch, merge, cold_delay)
-    group = _SimGroup(G, wire_dtype)
     mergers = [ReplicaMerger([m.syn0, m.syn1neg], plan, group.comm()) for m in models]
     plans = [chunk_plan(int(w.shape[0]), n_chunks, exact=True) for w, _, _ in shards]
-    total = epochs * n_walks_global
     for ep in range(epochs):
         for c in range(n_chunks):
-            for r, m in enumerate(models):
-                w, l, off = shards[r]
-                b, e = plans[r][c]
-                if e > b:
-                    m.train_pass(w[b:e], None if l is None else l[b:e], sentences_base=ep * n_walks_global + b * G,
-                                 sentences_step=G, sentences_total=total, walk_id_base=ep * n_walks_global + off + b,
-                                     splits=splits)
+            train_interval(plans, ep, c)
             for mg in mergers:
                 mg.snapshot()
             if mergers[0].hot_wire is not None:

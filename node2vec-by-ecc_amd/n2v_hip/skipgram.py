@@ -1,7 +1,7 @@
 """Host side of the skip-gram / negative-sampling trainer over a ragged ``SentenceCorpus`` (gensim's
 ``Word2Vec(sentences, sg=1)``) on MI355X: every row update runs in the HIP kernel ``n2v_sgns_csr_train``
-(csrc/n2v_sgns_csr.hip).  The tables, the vocabulary statistics and the schedule are the CBOW trainer's
-(n2v_hip/cbow.py: ``RaggedModel``); the update rule per (centre, context) pair is the walk-matrix trainer's
+(csrc/n2v_sgns_csr.hip).  ``RaggedModel`` (n2v_hip/cbow.py) owns the tables and the vocabulary statistics, and the
+schedule is the CBOW trainer's; the update rule per (centre, context) pair is the walk-matrix trainer's
 (csrc/n2v_sgns.hip), so a -1-padded walk matrix seen through ``SentenceCorpus.from_walks`` trains the same streams.
 Parity with gensim is UNPINNED, as for both of those.  Rows are changed by float atomic adds only, on one GPU.
 
@@ -9,7 +9,6 @@ Work items: with ``chunk == 0`` a sentence is one item on one wavefront.  With `
 tokens is dealt to ``ceil(n_s / chunk)`` items of at most ``chunk`` centres each; a wavefront's LDS slot is then
 ``chunk + 2 * window`` tokens instead of the corpus' longest sentence, and no item is longer than ``chunk`` centres.
 """
-import numpy as np
 import torch
 
 from . import _lib
@@ -70,8 +69,7 @@ class SkipGramModel(_cbow.RaggedModel):
                  device=None):
         if int(n_words) < 1:
             raise ValueError("empty vocabulary")
-        if int(window) < 1 or not 0 <= int(negative) <= 64:
-            raise ValueError("window must be >= 1, negative in [0, 64]")
+        _sgns.check_window_negative(window, negative)
         _cbow.RaggedModel.__init__(self, n_words, dim=dim, window=window, negative=negative, alpha=alpha,
                                    min_alpha=min_alpha, sample=sample, seed=seed, device=device, what="skip-gram")
 
@@ -95,16 +93,10 @@ class SkipGramModel(_cbow.RaggedModel):
         with torch.cuda.device(self.device):
             _lib.check(self.lib.n2v_sgns_csr_train(
                 _lib.ptr(corpus.tokens), _lib.ptr(corpus.offsets), corpus.n_sentences, corpus.n_tokens, corpus.max_len,
-                _lib.ptr(item_off), chunk, first_item, n_items, _lib.ptr(self.syn0), _lib.ptr(self.syn1neg),
-                self.n_words, self.dim, self.stride, self.window, self.negative, _lib.ptr(self.sample_int),
-                _lib.ptr(self.cum_table), _lib.ptr(self.lut), _sgns.LUT_BITS, self.alpha, self.min_alpha,
-                int(sentences_base), int(sentences_step), int(sentences_total), int(alpha_batch),
-                self.seed & (2**64 - 1), int(sentence_id_base) & (2**64 - 1), _lib.ptr(self.pair_count), UPDATE_MODE,
-                int(max_blocks), _lib.ptr(self.work_counter), self._stream()))
-
-    def pairs_trained(self):
-        """(centre, context) pairs trained so far."""
-        return int(self.pair_count.item())
+                _lib.ptr(item_off), chunk, first_item, n_items, *self._tables(), int(sentences_base),
+                int(sentences_step), int(sentences_total), int(alpha_batch), self._seed64(),
+                int(sentence_id_base) & (2**64 - 1), _lib.ptr(self.pair_count), UPDATE_MODE, int(max_blocks),
+                _lib.ptr(self.work_counter), self._stream()))
 
 
 def train(model, corpus, epochs=5, chunk="auto", sequential=False, max_blocks=0):
@@ -125,10 +117,6 @@ def train(model, corpus, epochs=5, chunk="auto", sequential=False, max_blocks=0)
         if not sequential:
             model.train_pass(corpus, max_blocks=max_blocks, **kw)
             continue
-        if chunk == 0:
-            lens = (corpus.offsets[1:] - corpus.offsets[:-1]).cpu().numpy()
-            todo = np.nonzero(lens > 1)[0].tolist()             # a sentence of one word trains nothing
-        else:
-            todo = range(n_items(corpus, chunk))
+        todo = _cbow.trainable_sentences(corpus) if chunk == 0 else range(n_items(corpus, chunk))
         for item in todo:
             model.train_pass(corpus, first_item=item, item_count=1, max_blocks=1, **kw)

@@ -448,6 +448,44 @@ def test_out_of_band_modes_are_fenced():
     assert n2v_main.parse_args(["--input", "x", "--allow-out-of-band", "--merge", "hot"]).allow_out_of_band is True
 
 
+def test_caller_tensors_are_refused_before_any_launch():
+    """train_pass, span_trainer and span_launcher hold `walks`, `lens` and `interval_state` to what the kernels read
+    (int32 / int64, contiguous, on the model's device, the stated shape) with a ValueError that names the argument — not
+    with an assert, which `python -O` strips.  Nothing is launched: every function of the library fails the test."""
+    from n2v_hip import sgns
+
+    class _NoLaunch:
+        def __getattr__(self, name):
+            pytest.fail("the library's %s was called" % name)
+
+    m = object.__new__(sgns.SgnsModel)
+    m.device, m.lib = torch.device("cpu"), _NoLaunch()
+    good = torch.zeros((2, 4), dtype=torch.int32)
+    lens = torch.full((2,), 4, dtype=torch.int32)
+    state = torch.zeros(2, dtype=torch.int64)
+
+    def calls(walks=good, lens=lens, state=state):
+        return (lambda: m.train_pass(walks, lens, sentences_base=0, sentences_total=2, walk_id_base=0),
+                lambda: m.span_trainer(walks, lens, sentences_total=2, sentences_step=1),
+                lambda: m.span_launcher(walks, lens, 2, 1, state, 1, 1, 0, 1))
+
+    bad_walks = (good.long(), torch.zeros((4, 2), dtype=torch.int32).t(), torch.zeros((2, 4), dtype=torch.int32, device="meta"))
+    assert not bad_walks[1].is_contiguous() and bad_walks[1].shape == good.shape
+    for walks in bad_walks:
+        for call in calls(walks=walks):
+            with pytest.raises(ValueError, match="SgnsModel.*walks"):
+                call()
+    for bad in (lens.long(), torch.zeros(4, dtype=torch.int32)[::2], torch.zeros(2, dtype=torch.int32, device="meta"),
+                torch.zeros(3, dtype=torch.int32)):
+        for call in calls(lens=bad):
+            with pytest.raises(ValueError, match="SgnsModel.*lens"):
+                call()
+    for bad in (torch.zeros(3, dtype=torch.int64), state.int(), torch.zeros(4, dtype=torch.int64)[::2],
+                torch.zeros(2, dtype=torch.int64, device="meta")):
+        with pytest.raises(ValueError, match="SgnsModel.span_launcher: interval_state"):
+            calls(state=bad)[2]()
+
+
 def test_default_grid_is_whole_workgroups_per_cu():
     """n2v_sgns_train's default grid (include/n2v_hip.h): at most one wavefront per 64 vocabulary rows, never more than 3 072 workgroups, and a whole number of workgroups per CU once there is
     more than one — 1 561 workgroups on a 399 846-row table cost 0.004 of AUC."""
