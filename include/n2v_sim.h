@@ -655,6 +655,97 @@ int n2v_ecccons_features(const int64_t* rows, int64_t n_kept, const int64_t* use
                          int64_t n_users, int64_t n_items, const double* profile, int32_t n_bins, const int32_t* vec_slot,
                          const float* vec, int64_t n_vec, int32_t d, const double* item_value, double* X, void* stream);
 
+/* ---- Random forests on binned features (csrc/n2v_forest.hip) -----
+ * The regressor and the entropy classifier of src/main_ecc.py:160-202 on the rows n2v_ecccons_features writes.  The
+ * definition is tests/forest_reference.py: fp64 features go to uint8 bins, a tree grows level by level
+ * from per-(node, feature) histograms whose channels are integers (draw counts, counts times round(y * 2^y_bits), class
+ * counts), and the score of a split is computed from those integers in a stated fp64 order.  Workgroups meet only through
+ * integer atomic adds and at launch boundaries, so two fits give the same bytes.  Samples stay partitioned by node:
+ * order[p] is the sample at position p and the frontier node m of a level owns the positions seg[m] .. seg[m + 1); no
+ * segment is empty.  Node ids are breadth first inside a tree; left[v] is -1 at a leaf and the right child is left[v] + 1.
+ * Limits, refused with N2V_ERR_INVALID before anything is launched: n < 2^31, features <= N2V_FOREST_MAX_FEATURES, bins
+ * 2 .. N2V_FOREST_MAX_BINS, classes 2 .. N2V_FOREST_MAX_CLASSES (0: the regressor), depth <= N2V_FOREST_MAX_DEPTH.  The
+ * kernels trust bins < n_bins, classes < n_classes and the tree tables: the check functions below tell the caller, through
+ * the bits of one int32 device word, that a value is outside its range, and the caller runs them first.               */
+#define N2V_FOREST_MAX_FEATURES 4096
+#define N2V_FOREST_MAX_BINS 256
+#define N2V_FOREST_MAX_CLASSES 32
+#define N2V_FOREST_MAX_DEPTH 32
+#define N2V_FOREST_PIECE 2048                        /* positions per workgroup of the histogram kernel             */
+#define N2V_FOREST_HIST_LDS 65536                    /* bytes of LDS a histogram workgroup may take                 */
+#define N2V_FOREST_STREAM_BOOT 0                     /* last Philox counter word: bootstrap draws / feature keys    */
+#define N2V_FOREST_STREAM_FEAT 1
+#define N2V_FOREST_BAD_NAN 1                         /* status bits                                                 */
+#define N2V_FOREST_BAD_BIN 2
+#define N2V_FOREST_BAD_CLASS 4
+#define N2V_FOREST_BAD_FEATURE 8
+#define N2V_FOREST_BAD_CHILD 16
+#define N2V_FOREST_BAD_TARGET 32
+
+/* Features per histogram workgroup: the largest power of two <= 64 whose tile x n_bins cells fit N2V_FOREST_HIST_LDS
+ * (a cell: int32 count + int64 sum, or n_classes int32 counts).  0 for an argument outside its range.               */
+int32_t n2v_forest_feature_tile(int32_t n_bins, int32_t n_classes);
+/* HOST: table[a] = a * log(a) by the host's libm, table[0] = 0, a < len.                                             */
+int n2v_forest_glog_table(int64_t len, double* table);
+/* *status |= BAD_NAN for a NaN in x[count]; BAD_BIN for a bin >= n_bins; BAD_CLASS for a class outside 0 .. n_classes - 1. */
+int n2v_forest_check_x(const double* x, int64_t count, int32_t* status, void* stream);
+int n2v_forest_check_bins(const uint8_t* bins, int64_t count, int32_t n_bins, int32_t* status, void* stream);
+int n2v_forest_check_classes(const int32_t* cls, int64_t count, int32_t n_classes, int32_t* status, void* stream);
+/* The tables of n_trees trees, tree t at tree_ptr[t] .. tree_ptr[t + 1) (the caller has checked tree_ptr on the host).  At
+ * every node with left != -1: BAD_CHILD unless node < left and left + 1 < the tree's size, BAD_FEATURE unless feature is in
+ * 0 .. n_features - 1, BAD_BIN unless threshold is in 0 .. n_bins - 1.                                                */
+int n2v_forest_check_tree(const int32_t* feature, const int32_t* threshold, const int32_t* left, const int64_t* tree_ptr,
+                          int32_t n_trees, int64_t n_nodes, int32_t n_features, int32_t n_bins, int32_t* status, void* stream);
+/* xs: fp64[n_features][n], every row sorted ascending, no NaN.  edges: fp64[n_features][n_bins - 1], the first
+ * n_edges[f] of row f ascending: the distinct values but the first when there are at most n_bins, else the distinct ones
+ * among xs[(b * n) / n_bins], b = 1 .. n_bins - 1.                                                                    */
+int n2v_forest_edges(const double* xs, int64_t n, int32_t n_features, int32_t n_bins, double* edges, int32_t* n_edges, void* stream);
+/* bins[i][f] = the number of edges of f that are <= x[i][f] (uint8[n][n_features]); a NaN sets BAD_NAN and bin 0.      */
+int n2v_forest_bin(const double* x, int64_t n, int32_t n_features, int32_t n_bins, const double* edges, const int32_t* n_edges,
+                   uint8_t* bins, int32_t* status, void* stream);
+/* w[i] = the draws k < n of tree `tree` with (philox4x32_10(seed; k lo, k hi, tree, STREAM_BOOT)[0] * n) >> 32 == i.    */
+int n2v_forest_bootstrap(uint64_t seed, int32_t tree, int64_t n, int32_t* w, void* stream);
+/* yq[i] = (int64) rint(y[i] * 2^y_bits), *max_abs = the largest |yq| (one int64 device word); BAD_TARGET for a y that
+ * is not finite or whose yq reaches 2^53.                                                                            */
+int n2v_forest_quantise(const double* y, int64_t n, int32_t y_bits, int64_t* yq, int64_t* max_abs, int32_t* status, void* stream);
+/* keys[m][j] = (philox4x32_10(seed; node_id0 + m, j, tree, STREAM_FEAT)[0] << 12) | j, int64[nodes][n_features]: sorted
+ * along a row, the max_features-th smallest is the key_limit of n2v_forest_split.                                     */
+int n2v_forest_feature_keys(uint64_t seed, int32_t tree, int32_t node_id0, int32_t nodes, int32_t n_features, int64_t* keys,
+                            void* stream);
+/* The histograms of the frontier nodes node0 .. node1 - 1 over the features 0 .. f_count - 1 (zeroed first):
+ * regressor (n_classes == 0) int64[node][feature][bin][2] = (sum of w, sum of w * yq); classifier
+ * int32[node][feature][bin][class] = sum of w.  bins: uint8[n][n_features]; n_positions = seg[node1] - seg[node0].     */
+int n2v_forest_hist(const uint8_t* bins, int64_t n, int32_t n_features, int32_t f_count, int32_t n_bins, int32_t n_classes,
+                    const int32_t* order, const int32_t* seg, int32_t node0, int32_t node1, int64_t n_positions, const int32_t* w,
+                    const int64_t* yq, const int32_t* cls, void* hist, void* stream);
+/* The best split of each of `nodes` nodes from their histograms, node m having the id node_id0 + m: writes feature /
+ * threshold (-1 at a leaf), left = -1, value (fp64[id] or fp64[id][n_classes]) and split[m] = 1 where the node splits.
+ * key_limit: NULL for every feature, else int64[nodes].  leaf_only: every node is a leaf (f_count may then be 1).
+ * best_score / best_thr: scratch [nodes][f_count]; node_count / node_parent: scratch [nodes].                         */
+int n2v_forest_split(const void* hist, int32_t nodes, int32_t f_count, int32_t n_bins, int32_t n_classes, int32_t min_samples_split,
+                     int32_t min_samples_leaf, int32_t leaf_only, const double* gtab, int64_t gtab_len, uint64_t seed, int32_t tree,
+                     int32_t node_id0, const int64_t* key_limit, int32_t y_bits, double* best_score, int32_t* best_thr,
+                     int64_t* node_count, double* node_parent, int32_t* feature, int32_t* threshold, int32_t* left, double* value,
+                     int32_t* split, void* stream);
+/* flags: int32[2][n_positions]: flags[0][p] = 1 where position p belongs to a splitting node and goes left,
+ * flags[1][p] = 1 where it goes right.                                                                                */
+int n2v_forest_route_flags(const uint8_t* bins, int64_t n, int32_t n_features, const int32_t* order, const int32_t* seg, int32_t n_seg,
+                           int64_t n_positions, const int32_t* split, const int32_t* feature, const int32_t* threshold,
+                           int32_t node_id0, int32_t* flags, void* stream);
+/* sums: the inclusive scan of flags along each row; rank: the inclusive scan of split; n_split its total, n_next the
+ * number of flagged positions.  Writes the stable partition of every splitting node's segment to new_order, the children's
+ * segments to new_seg[2 * n_split + 1] and left[node_id0 + m] = next_id0 + 2 * (rank[m] - 1).                         */
+int n2v_forest_route_scatter(const int32_t* order, const int32_t* seg, int32_t n_seg, int64_t n_positions, const int32_t* split,
+                             const int32_t* rank, const int32_t* flags, const int32_t* sums, int32_t node_id0, int32_t next_id0,
+                             int32_t n_split, int64_t n_next, int32_t* left, int32_t* new_order, int32_t* new_seg, void* stream);
+/* out[i][c] = (the sum over the trees, in ascending order from +0.0, of value[leaf of i][c]) / n_trees; width: 1 or the
+ * number of classes; a walk takes at most max_depth steps.  The tables have passed n2v_forest_check_tree.             */
+int n2v_forest_predict(const uint8_t* bins, int64_t n, int32_t n_features, const int32_t* feature, const int32_t* threshold,
+                       const int32_t* left, const double* value, const int64_t* tree_ptr, int32_t n_trees, int32_t width,
+                       int32_t max_depth, double* out, void* stream);
+/* out[i] = the first maximum of proba[i][0 .. n_classes).                                                             */
+int n2v_forest_argmax(const double* proba, int64_t n, int32_t n_classes, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

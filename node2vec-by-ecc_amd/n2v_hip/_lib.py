@@ -195,6 +195,25 @@ SIGNATURES = {
     "n2v_ecccons_feature_rows": (C.c_int, [_ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "n2v_ecccons_features": (C.c_int, [_ptr, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _i32, _ptr, _ptr, _i64, _i32, _ptr, _ptr,
                                        _ptr]),
+    "n2v_forest_feature_tile": (C.c_int32, [_i32, _i32]),
+    "n2v_forest_glog_table": (C.c_int, [_i64, _ptr]),
+    "n2v_forest_check_x": (C.c_int, [_ptr, _i64, _ptr, _ptr]),
+    "n2v_forest_check_bins": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr]),
+    "n2v_forest_check_classes": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr]),
+    "n2v_forest_check_tree": (C.c_int, [_ptr, _ptr, _ptr, _ptr, _i32, _i64, _i32, _i32, _ptr, _ptr]),
+    "n2v_forest_edges": (C.c_int, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr]),
+    "n2v_forest_bin": (C.c_int, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_forest_bootstrap": (C.c_int, [_u64, _i32, _i64, _ptr, _ptr]),
+    "n2v_forest_quantise": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_forest_feature_keys": (C.c_int, [_u64, _i32, _i32, _i32, _i32, _ptr, _ptr]),
+    "n2v_forest_hist": (C.c_int, [_ptr, _i64, _i32, _i32, _i32, _i32, _ptr, _ptr, _i32, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_forest_split": (C.c_int, [_ptr, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _ptr, _i64, _u64, _i32, _i32, _ptr, _i32, _ptr,
+                                   _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "n2v_forest_route_flags": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr, _i32, _i64, _ptr, _ptr, _ptr, _i32, _ptr, _ptr]),
+    "n2v_forest_route_scatter": (C.c_int, [_ptr, _ptr, _i32, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _i64, _ptr, _ptr, _ptr,
+                                           _ptr]),
+    "n2v_forest_predict": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _ptr, _ptr]),
+    "n2v_forest_argmax": (C.c_int, [_ptr, _i64, _i32, _ptr, _ptr]),
 }
 
 _lib = None
