@@ -1,26 +1,109 @@
 """Device-side walk engine: CSR + alias tables resident in HBM as torch tensors, every
 arithmetic step done by the HIP kernels behind the C-ABI (include/n2v_hip.h).
 
-torch is used for memory, streams and index plumbing (prefix sums, size-order sort);
-the alias arithmetic and the walk are never done in torch and there is no CPU path.
+torch is used for memory, streams and index plumbing (prefix sums, gathers, searches; nothing is sorted: the table
+kernel takes its tables from a shared counter); the alias arithmetic and the walk are never done in torch and there is
+no CPU path.  What is pure host arithmetic — the memory plan of the tables (plan_tables), the frame of a walk launch
+(walk_frame), the rng names (rng_mode) — is a module-level function that needs no GPU.
 """
+import collections
+import os
 import time
 
 import numpy as np
 import torch
 
 from . import _lib
-from .csr import CsrGraph
+from .csr import CsrGraph, degree_cut_for_budget, popwalk_exempt_flags
 
 SLOT_BYTES = 16  # sizeof(n2v_alias_slot)
 FAT_BYTES = 32   # sizeof(n2v_fat_slot)
+
+_RNG_MODES = {"philox": _lib.RNG_PHILOX, "uniforms": _lib.RNG_UNIFORMS, "uniforms_tiled": _lib.RNG_UNIFORMS_TILED}
 
 
 def _require_gpu(device):
     if not torch.cuda.is_available():
         raise RuntimeError("n2v_hip: no GPU visible (torch.cuda.is_available() is False); "
                            "this engine has no CPU fallback")
-    return torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+    d = torch.device(device if device is not None else "cuda")
+    # with its index, as tensors report their device: a caller's `out` is compared against it (walk_frame)
+    return d if d.index is not None or d.type != "cuda" else torch.device("cuda", torch.cuda.current_device())
+
+
+def edge_table_slots(csr):
+    """Slots of all (src -> dst) edge tables: the sum over CSR entries of deg(dst).  Host arithmetic on the CSR: see
+    WalkEngine._alloc_edge_tables on why no device reduction / scan / sort may run before the big table allocation."""
+    if csr.nnz == 0:
+        return 0
+    hdeg = np.diff(csr.row_ptr).astype(np.int64)
+    if csr.directed:
+        return int((np.bincount(csr.col, minlength=csr.n_nodes).astype(np.int64) * hdeg).sum())
+    return int((hdeg ** 2).sum())
+
+
+TablePlan = collections.namedtuple("TablePlan", "total partial stored_degree_cut want_thin want_fat")
+
+
+def plan_tables(csr, first_order, fat, budget_bytes, free, edge_slots=None):
+    """The memory plan of WalkEngine.preprocess: how many edge-table slots are stored (`total`), whether only the
+    tables of entries with deg(dst) <= `stored_degree_cut` are (`partial`), and in which layouts.  `free`: the bytes
+    the tables may take from; `edge_slots`: edge_table_slots(csr) where the caller has it already.  MemoryError when
+    the layouts asked for do not fit."""
+    total = csr.nnz if first_order else (edge_table_slots(csr) if edge_slots is None else edge_slots)
+    partial, cut = False, None
+    if not first_order:
+        if budget_bytes is None and fat == "auto" and total * SLOT_BYTES > free - (1 << 30):
+            # not even the thin tables fit: keep the tables that do and let the walk rebuild the others per step
+            # (the reference's answer is to rebuild ALL of them, src/settings.py:18) instead of giving up
+            budget_bytes = max(0, free - (8 << 30))
+        if budget_bytes is not None and total * FAT_BYTES > int(budget_bytes):
+            cut, total = degree_cut_for_budget(csr, budget_bytes, FAT_BYTES)
+            partial, fat = True, True
+    if fat == "auto":
+        fat = (csr.nnz + (0 if first_order else total)) * FAT_BYTES < free - (8 << 30)
+    want_thin, want_fat = fat in (False, "both"), fat in (True, "both")
+    need = 0 if first_order else total * ((SLOT_BYTES if want_thin else 0) + (FAT_BYTES if want_fat else 0))
+    if need > free - (1 << 30):
+        raise MemoryError("edge alias tables need %.1f GB (sum of deg^2 = %d slots), %.1f GB free"
+                          % (need / 1e9, total, free / 1e9))
+    return TablePlan(total, partial, cut, want_thin, want_fat)
+
+
+def rng_mode(rng, tiled_ok):
+    """The RNG_* constant of a walk launch's `rng` name; `tiled_ok`: the kernel about to run reads the tiled layout."""
+    mode = _RNG_MODES.get(rng)
+    if mode is None:
+        raise ValueError("rng must be 'philox', 'uniforms' or 'uniforms_tiled', got %r" % (rng,))
+    if mode == _lib.RNG_UNIFORMS_TILED and not tiled_ok:
+        raise ValueError("the tiled uniform layout is read by the fat-table walk kernel only")
+    return mode
+
+
+def walk_frame(n_starts, pos_begin, pos_count, num_rounds, L, out, device):
+    """The frame every walk launch shares: (pos_count, n_local, walks, lens).  pos_count defaults to the starts from
+    pos_begin on; the results are int32[n_local, L] and int32[n_local] on `device`, allocated here or the caller's
+    `out` (slices of a larger buffer are contiguous) — which is checked before its pointers reach a kernel."""
+    if L < 1:
+        raise ValueError("walk_length must be >= 1")
+    if pos_count is None:
+        pos_count = n_starts - pos_begin
+    n_local = pos_count * num_rounds
+    device = torch.device(device)
+    if out is None:
+        return (pos_count, n_local, torch.empty((n_local, L), dtype=torch.int32, device=device),
+                torch.empty(n_local, dtype=torch.int32, device=device))
+    walks, lens = out
+    _lib.tensor("walk", "out[0] (walks)", walks, torch.int32, device, (n_local, L))
+    _lib.tensor("walk", "out[1] (lens)", lens, torch.int32, device, n_local)
+    return pos_count, n_local, walks, lens
+
+
+def _check_status(status, ignore=0):
+    """Read a build's or a walk's status word back (the call's one synchronising read): a table that sums to zero
+    is the reference's ZeroDivisionError."""
+    if int(status.item()) & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP) & ~ignore:
+        raise ZeroDivisionError("float division by zero")
 
 
 class WalkEngine:
@@ -41,30 +124,29 @@ class WalkEngine:
         self.w = None if (csr.w is None or unit) else torch.from_numpy(csr.w).to(d)
         self.start_order = torch.from_numpy(csr.start_order).to(d)
         self.deg = (self.row_ptr[1:] - self.row_ptr[:-1])
-        hdeg = np.diff(csr.row_ptr)
-        self.max_degree = int(hdeg.max()) if csr.n_nodes else 0     # host arithmetic: see preprocess() on why no device
-        # reduction / scan / sort may run before the big table allocation
-        if csr.nnz == 0:
-            self.total_edge_slots = 0
-        elif csr.directed:
-            self.total_edge_slots = int((np.bincount(csr.col, minlength=csr.n_nodes).astype(np.int64) * hdeg).sum())
-        else:
-            self.total_edge_slots = int((hdeg.astype(np.int64) ** 2).sum())   # sum over entries of deg(col[e])
-        self.node_slots = None
-        self.edge_slots = None
-        self.edge_off = None
-        self.recs = None
-        self.node_fat = self.edge_fat = None
+        self.max_degree = int(np.diff(csr.row_ptr).max()) if csr.n_nodes else 0     # host arithmetic, like the next
+        self.total_edge_slots = edge_table_slots(csr)
+        self._reset_tables()
         self.first_order = False
-        self.partial = False          # tables under a memory budget: only entries with deg(dst) <= stored_degree_cut
         self.pop_tables = False       # the stored node tables are the popularity-biased ones (preprocess(pop=True))
+        self.timings = {}             # seconds per preprocess phase, filled when N2V_TIMING is set (_phase_timer)
+        self.alloc_seconds = 0.0      # host time of the last preprocess's table allocation
         self._plain = None
+        self._otf_scratch = None      # the on-the-fly walk's scratch rows, grown on demand
+        self._csr_keys = None         # thin_view's search keys over the CSR, computed once
+
+    def _reset_tables(self):
+        """No table set: what a preprocess() builds, and what it drops before it builds anew."""
+        self.node_slots = self.edge_slots = self.edge_off = self.recs = self.node_fat = self.edge_fat = None
+        self.total_slots = 0          # stored edge-table slots
+        self.partial = False          # tables under a memory budget: only entries with deg(dst) <= stored_degree_cut
+        self.stored_degree_cut = None
+        self.stored_mask = None       # partial: bool[nnz] on the device, the entries whose table is stored
 
     @property
     def plain(self):
         """uint8[N] on the device: the nodes the popularity rule exempts (csr.popwalk_exempt_flags), computed once."""
         if self._plain is None:
-            from .csr import popwalk_exempt_flags
             self._plain = torch.from_numpy(popwalk_exempt_flags(self.csr.labels)).to(self.device)
         return self._plain
 
@@ -90,139 +172,139 @@ class WalkEngine:
         only the tables of entries (src -> dst) with deg(dst) <= D are stored (D = the largest cut that fits: every
         table is visited equally often per byte, but a rebuilt table costs a fixed latency on top of its slots, so the
         small ones are the ones to keep); the walk (n2v_walk_hybrid) rebuilds the others per step.  Same walks."""
-        csr, d = self.csr, self.device
-        N, nnz = csr.n_nodes, csr.nnz
+        d = self.device
         self.timings = {}
         tick = self._phase_timer()
-        self.node_slots = self.edge_slots = self.recs = self.node_fat = self.edge_fat = None
+        self._reset_tables()
         self.pop_tables = bool(pop)
-        plain_node_slots = None       # pop and first order: the tables the records point at
+        self.first_order = bool(first_order_shortcut and self.p == 1.0 and self.q == 1.0)
         with torch.cuda.device(d):
-            self.first_order = bool(first_order_shortcut and self.p == 1.0 and self.q == 1.0)
-            total = nnz if self.first_order else self.total_edge_slots
-            self.partial, self.stored_degree_cut, stored_entries = False, None, None
             free, _ = torch.cuda.mem_get_info(d)
             free += torch.cuda.memory_reserved(d) - torch.cuda.memory_allocated(d)    # the allocator's cache is ours to reuse
-            if (budget_bytes is None and fat == "auto" and not self.first_order
-                    and total * SLOT_BYTES > free - (1 << 30)):
-                # not even the thin tables fit: keep the tables that do and let the walk rebuild the others per step
-                # (the reference's answer is to rebuild ALL of them, src/settings.py:18) instead of giving up
-                budget_bytes = max(0, free - (8 << 30))
-            if budget_bytes is not None and not self.first_order and total * FAT_BYTES > int(budget_bytes):
-                # host arithmetic (no device reduction before the big allocation)
-                from .csr import degree_cut_for_budget
-                self.stored_degree_cut, total = degree_cut_for_budget(csr, budget_bytes, FAT_BYTES)
-                self.partial, fat = True, True
-            self.total_slots = total
-            if fat == "auto":
-                fat = (nnz + (0 if self.first_order else total)) * FAT_BYTES < free - (8 << 30)
-            want_thin = fat in (False, "both")
-            want_fat = fat in (True, "both")
-            need = 0 if self.first_order else total * ((SLOT_BYTES if want_thin else 0) + (FAT_BYTES if want_fat else 0))
-            if need > free - (1 << 30):
-                raise MemoryError("edge alias tables need %.1f GB (sum of deg^2 = %d slots), %.1f GB free"
-                                  % (need / 1e9, total, free / 1e9))
-            # The big buffers FIRST, before any device scan / sort / reduction of this call: on this stack a fresh
-            # multi-GB allocation that follows such a kernel takes seconds (tools/alloc_probe.py: 58 GB in 0.000 s
-            # as the first thing, 3.06 s after a torch.argsort of 2e7 keys; round 1's preprocess spent 1.5-2.4 s of
-            # its 2.76 s there).  The slot count comes from host arithmetic on the CSR for the same reason.
-            t_alloc = time.perf_counter()
-            if not self.first_order:
-                if want_thin:
-                    self.edge_slots = torch.empty((max(total, 1), 2), dtype=torch.int64, device=d)
-                if want_fat:
-                    self.edge_fat = torch.empty((max(total, 1), 4), dtype=torch.int64, device=d)
-            # host time of the table allocation (hipMalloc blocks the host when the driver has to hand out memory another
-            # allocation has just released: 65-80 ms per GiB, tools/alloc_probe2.py; ~0 from the allocator's cache or
-            # from memory that was never used) — reported separately from the kernels by bench.py
-            self.alloc_seconds = time.perf_counter() - t_alloc
+            plan = plan_tables(self.csr, self.first_order, fat, budget_bytes, free, self.total_edge_slots)
+            self.total_slots, self.partial, self.stored_degree_cut = plan[:3]
+            self._alloc_edge_tables(plan)
             tick("alloc")
             status = torch.zeros(1, dtype=torch.int32, device=d)
-            self.node_slots = torch.zeros((max(nnz, 1), 2), dtype=torch.int64, device=d)
-            if pop and nnz > 0:
-                _lib.check(self.lib.n2v_build_node_tables_pop(
-                    0, N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(self.plain),
-                    _lib.ptr(self.node_slots), _lib.ptr(status), self._stream()))
-            if not pop or self.first_order:
-                plain_node_slots = torch.zeros_like(self.node_slots) if pop else self.node_slots
-                _lib.check(self.lib.n2v_build_node_tables(
-                    N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(plain_node_slots),
-                    _lib.ptr(status), self._stream()))
+            plain_node_slots = self._build_node_tables(pop, status)
             tick("node_tables")
-            rec_off = None
-            if self.first_order:
-                self.edge_off = None
-            else:
-                kdst = self.deg[self.col.long()]
-                if self.partial:
-                    stored = kdst <= self.stored_degree_cut
-                    kdst = kdst * stored
-                    stored_entries = torch.nonzero(stored).flatten().to(torch.int32).contiguous()
-                self.edge_off = torch.zeros(nnz + 1, dtype=torch.int64, device=d)
-                torch.cumsum(kdst, 0, out=self.edge_off[1:])
-                assert int(self.edge_off[-1].item()) == total, "host and device slot counts differ"
-                rec_off = self.edge_off
-                if self.partial:      # a negative offset marks an entry without a stored table (N2V_NO_TABLE)
-                    rec_off = torch.where(stored, self.edge_off[:-1], torch.full_like(self.edge_off[:-1], -1)).contiguous()
-                    self.stored_mask = stored
-            # walk records first: they depend on the table OFFSETS only, and the fat slots embed them
-            self.recs = torch.empty((max(nnz, 1), 4), dtype=torch.int32, device=d)
-            _lib.check(self.lib.n2v_build_edge_recs(
-                N, nnz, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(rec_off), 0,
-                self.max_degree, total, _lib.ptr(self.recs), self._stream()))
+            stored_entries = self._build_offsets_and_recs()
             tick("offsets_recs")
             if self.first_order:
                 self.edge_slots = plain_node_slots
             else:
-                # nothing is sorted here: the wave kernel takes its tables from a shared counter instead of a
-                # size-ordered list
-                src_of = torch.repeat_interleave(torch.arange(N, dtype=torch.int32, device=d), self.deg)
-                sym = 0 if csr.directed else 1
-                work = torch.zeros(2, dtype=torch.int64, device=d)
-                # per-wave stacks of the tables that do not fit the wave's LDS slots (C3: 0.8 GB for max degree 16 614)
-                built_max = self.stored_degree_cut if self.partial else self.max_degree
-                n_build = int(stored_entries.numel()) if self.partial else nnz
-                sbytes = int(self.lib.n2v_edge_tables_wave_scratch_bytes(built_max))
-                scratch = torch.empty(max(sbytes, 64) // 8, dtype=torch.int64, device=d)
-                tick("src_of")
-                if want_thin:
-                    _lib.check(self.lib.n2v_build_edge_tables_wave(
-                        N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
-                        self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(stored_entries), 0, n_build, None,
-                        _lib.ptr(self.edge_slots), None, _lib.ptr(status), work[0:].data_ptr(), built_max,
-                        _lib.ptr(scratch), sbytes, self._stream()))
-                    tick("edge_tables_thin")
-                if want_fat:
-                    _lib.check(self.lib.n2v_build_edge_tables_wave(
-                        N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(src_of),
-                        self.p, self.q, sym, _lib.ptr(self.edge_off), _lib.ptr(stored_entries), 0, n_build,
-                        _lib.ptr(self.recs), None, _lib.ptr(self.edge_fat), _lib.ptr(status), work[1:].data_ptr(),
-                        built_max, _lib.ptr(scratch), sbytes, self._stream()))
-                    tick("edge_tables_fat")
-                del src_of, kdst, scratch
-            if want_fat and nnz > 0:
-                self.node_fat = torch.empty((max(nnz, 1), 4), dtype=torch.int64, device=d)
-                _lib.check(self.lib.n2v_build_fat_slots(
-                    N, _lib.ptr(self.row_ptr), None, _lib.ptr(self.row_ptr), _lib.ptr(self.node_slots),
-                    _lib.ptr(self.recs), _lib.ptr(self.node_fat), self._stream()))
-                if self.first_order:
-                    self.edge_fat = self.node_fat
-                    if pop:
-                        self.edge_fat = torch.empty_like(self.node_fat)
-                        _lib.check(self.lib.n2v_build_fat_slots(
-                            N, _lib.ptr(self.row_ptr), None, _lib.ptr(self.row_ptr), _lib.ptr(plain_node_slots),
-                            _lib.ptr(self.recs), _lib.ptr(self.edge_fat), self._stream()))
-            st = int(status.item())
+                self._build_edge_tables(plan, stored_entries, status, tick)
+            if plan.want_fat and self.csr.nnz > 0:
+                self.node_fat = self._fat_slots(self.node_slots)
+                if self.first_order:      # the "edge tables" are the plain node tables
+                    self.edge_fat = self._fat_slots(plain_node_slots) if pop else self.node_fat
+            try:
+                _check_status(status)
+            except ZeroDivisionError:
+                self._reset_tables()
+                raise
             tick("node_fat")
-        if st & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP):
-            self.node_slots = self.edge_slots = self.recs = self.node_fat = self.edge_fat = None
-            raise ZeroDivisionError("float division by zero")
+
+    def _alloc_edge_tables(self, plan):
+        """The big buffers FIRST, before any device scan / sort / reduction of this call: on this stack a fresh
+        multi-GB allocation that follows such a kernel takes seconds (tools/alloc_probe.py: 58 GB in 0.000 s as the
+        first thing, 3.06 s after a torch.argsort of 2e7 keys; round 1's preprocess spent 1.5-2.4 s of its 2.76 s
+        there).  The slot count comes from host arithmetic on the CSR for the same reason.
+        alloc_seconds: host time of this allocation (hipMalloc blocks the host when the driver has to hand out memory
+        another allocation has just released: 65-80 ms per GiB, tools/alloc_probe2.py; ~0 from the allocator's cache
+        or from memory that was never used) — reported separately from the kernels by bench.py."""
+        t_alloc = time.perf_counter()
+        if not self.first_order:
+            rows = max(plan.total, 1)
+            if plan.want_thin:
+                self.edge_slots = torch.empty((rows, 2), dtype=torch.int64, device=self.device)
+            if plan.want_fat:
+                self.edge_fat = torch.empty((rows, 4), dtype=torch.int64, device=self.device)
+        self.alloc_seconds = time.perf_counter() - t_alloc
+
+    def _build_node_tables(self, pop, status):
+        """node_slots (pop: the popularity-biased ones); returns the plain node tables where they are built — they
+        are node_slots themselves without pop, and with pop they exist beside them in first order only, where the
+        records point at them — else None."""
+        N, nnz = self.csr.n_nodes, self.csr.nnz
+        self.node_slots = torch.zeros((max(nnz, 1), 2), dtype=torch.int64, device=self.device)
+        if pop and nnz > 0:
+            _lib.check(self.lib.n2v_build_node_tables_pop(
+                0, N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(self.plain),
+                _lib.ptr(self.node_slots), _lib.ptr(status), self._stream()))
+        if pop and not self.first_order:
+            return None
+        plain_node_slots = torch.zeros_like(self.node_slots) if pop else self.node_slots
+        _lib.check(self.lib.n2v_build_node_tables(
+            N, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), _lib.ptr(plain_node_slots),
+            _lib.ptr(status), self._stream()))
+        return plain_node_slots
+
+    def _build_offsets_and_recs(self):
+        """edge_off (and stored_mask when partial), then the walk records: they depend on the table OFFSETS only, and
+        the fat slots embed them.  Returns the int32 list of the entries whose table is stored when partial, else None."""
+        N, nnz, d = self.csr.n_nodes, self.csr.nnz, self.device
+        stored_entries = rec_off = None
+        if not self.first_order:
+            kdst = self.deg[self.col.long()]
+            if self.partial:
+                stored = kdst <= self.stored_degree_cut
+                kdst = kdst * stored
+                stored_entries = torch.nonzero(stored).flatten().to(torch.int32).contiguous()
+            self.edge_off = torch.zeros(nnz + 1, dtype=torch.int64, device=d)
+            torch.cumsum(kdst, 0, out=self.edge_off[1:])
+            assert int(self.edge_off[-1].item()) == self.total_slots, "host and device slot counts differ"
+            rec_off = self.edge_off
+            if self.partial:      # a negative offset marks an entry without a stored table (N2V_NO_TABLE)
+                rec_off = torch.where(stored, self.edge_off[:-1], torch.full_like(self.edge_off[:-1], -1)).contiguous()
+                self.stored_mask = stored
+        self.recs = torch.empty((max(nnz, 1), 4), dtype=torch.int32, device=d)
+        _lib.check(self.lib.n2v_build_edge_recs(
+            N, nnz, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(rec_off), 0,
+            self.max_degree, self.total_slots, _lib.ptr(self.recs), self._stream()))
+        return stored_entries
+
+    def _edge_tables_wave(self, src_of, edge_off, order, n_build, built_max, scratch, sbytes, status, work=None,
+                          recs=None, thin=None, fat=None):
+        """n2v_build_edge_tables_wave over the n_build entries of `order` (None: all, in CSR order) into thin slots, or
+        with `recs` into fat ones.  src_of, edge_off and work are raw addresses: build_one_edge_table shifts the first
+        two, the stored builds pass one counter each of a shared tensor."""
+        _lib.check(self.lib.n2v_build_edge_tables_wave(
+            self.csr.n_nodes, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), src_of, self.p, self.q,
+            0 if self.csr.directed else 1, edge_off, _lib.ptr(order), 0, n_build, _lib.ptr(recs), _lib.ptr(thin),
+            _lib.ptr(fat), _lib.ptr(status), work, built_max, _lib.ptr(scratch), sbytes, self._stream()))
+
+    def _build_edge_tables(self, plan, stored_entries, status, tick):
+        """The stored (src -> dst) tables, in each layout the plan asks for.  Nothing is sorted here: the wave kernel
+        takes its tables from a shared counter instead of a size-ordered list."""
+        d = self.device
+        src_of = torch.repeat_interleave(torch.arange(self.csr.n_nodes, dtype=torch.int32, device=d), self.deg)
+        work = torch.zeros(2, dtype=torch.int64, device=d)
+        # per-wave stacks of the tables that do not fit the wave's LDS slots (C3: 0.8 GB for max degree 16 614)
+        built_max = self.stored_degree_cut if self.partial else self.max_degree
+        n_build = int(stored_entries.numel()) if self.partial else self.csr.nnz
+        sbytes = int(self.lib.n2v_edge_tables_wave_scratch_bytes(built_max))
+        scratch = torch.empty(max(sbytes, 64) // 8, dtype=torch.int64, device=d)
+        tick("src_of")
+        common = (src_of.data_ptr(), self.edge_off.data_ptr(), stored_entries, n_build, built_max, scratch, sbytes, status)
+        if plan.want_thin:
+            self._edge_tables_wave(*common, work=work[0:].data_ptr(), thin=self.edge_slots)
+            tick("edge_tables_thin")
+        if plan.want_fat:
+            self._edge_tables_wave(*common, work=work[1:].data_ptr(), recs=self.recs, fat=self.edge_fat)
+            tick("edge_tables_fat")
+
+    def _fat_slots(self, node_slots):
+        """The fat (32-B, record-embedding) form of a set of node tables."""
+        out = torch.empty((max(self.csr.nnz, 1), 4), dtype=torch.int64, device=self.device)
+        _lib.check(self.lib.n2v_build_fat_slots(
+            self.csr.n_nodes, _lib.ptr(self.row_ptr), None, _lib.ptr(self.row_ptr), _lib.ptr(node_slots),
+            _lib.ptr(self.recs), _lib.ptr(out), self._stream()))
+        return out
 
     def _phase_timer(self):
         """Wall time per preprocess phase into self.timings when N2V_TIMING is set (syncs the device after each
         phase, so only for diagnosis: tools/preprocess_probe.py)."""
-        import os
-        import time
         if not os.environ.get("N2V_TIMING"):
             return lambda name: None
         t = [time.perf_counter()]
@@ -247,10 +329,13 @@ class WalkEngine:
     def slots_J(slots):
         return slots.view(torch.int32)[:, 2]
 
+    @classmethod
+    def host_table(cls, slots):
+        """(J int64, q float64) numpy arrays of a run of thin slots, as the reference's alias_setup returns them."""
+        return (cls.slots_J(slots).cpu().numpy().astype(np.int64), cls.slots_q(slots).cpu().numpy())
+
     def node_table(self, dense):
-        b, e = int(self.csr.row_ptr[dense]), int(self.csr.row_ptr[dense + 1])
-        s = self.node_slots[b:e]
-        return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
+        return self.host_table(self.node_slots[int(self.csr.row_ptr[dense]):int(self.csr.row_ptr[dense + 1])])
 
     def edge_index(self, du, dv):
         """CSR entry of (du -> dv) or -1."""
@@ -263,8 +348,7 @@ class WalkEngine:
     def edge_table(self, e):
         if self.first_order:
             dense = int(self.csr.col[e])      # edge_slots ARE the plain node tables (also after preprocess(pop=True))
-            s = self.edge_slots[int(self.csr.row_ptr[dense]):int(self.csr.row_ptr[dense + 1])]
-            return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
+            return self.host_table(self.edge_slots[int(self.csr.row_ptr[dense]):int(self.csr.row_ptr[dense + 1])])
         if self.partial and not bool(self.stored_mask[e].item()):
             return self.build_one_edge_table(e)         # not stored under the memory budget: built on demand
         off = self.edge_off[e:e + 2].cpu().tolist()
@@ -297,11 +381,10 @@ class WalkEngine:
             node = torch.full_like(slot_idx, int(table_node))
         # position of (node, alias_dst) in the CSR = global search over the keys row * N + col (ascending)
         n = self.csr.n_nodes
-        keys = getattr(self, "_csr_keys", None)
-        if keys is None:
+        if self._csr_keys is None:
             src_of = torch.repeat_interleave(torch.arange(n, device=self.device), self.deg)
-            keys = self._csr_keys = src_of * n + self.col.long()
-        e2 = torch.searchsorted(keys, node * n + alias_dst)
+            self._csr_keys = src_of * n + self.col.long()
+        e2 = torch.searchsorted(self._csr_keys, node * n + alias_dst)
         return e2 - self.row_ptr[node], q
 
     def build_one_node_table(self, dense, pop=False):
@@ -322,10 +405,8 @@ class WalkEngine:
                 w = None if self.w is None else self.w[b:e].contiguous()
                 _lib.check(self.lib.n2v_build_node_tables(1, _lib.ptr(rp), self.col[b:].data_ptr() if e > b else None,
                                                           _lib.ptr(w), _lib.ptr(slots), _lib.ptr(status), self._stream()))
-            if int(status.item()) & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP):
-                raise ZeroDivisionError("float division by zero")
-        s = slots[: e - b]
-        return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
+            _check_status(status)
+        return self.host_table(slots[: e - b])
 
     def build_one_edge_table(self, e, pop=False):
         """get_alias_edge (src/node2vec.py:133-152; pop: get_alias_edge_pop, :154-174) for one CSR entry e = (src -> dst), built on demand by the
@@ -350,14 +431,10 @@ class WalkEngine:
                     self.p, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1, _lib.ptr(slots), _lib.ptr(status), K,
                     _lib.ptr(scratch), sbytes, self._stream()))
             else:
-                _lib.check(self.lib.n2v_build_edge_tables_wave(
-                    self.csr.n_nodes, _lib.ptr(self.row_ptr), _lib.ptr(self.col), _lib.ptr(self.w), src_of.data_ptr() - 4 * e,
-                    self.p, self.q, 0 if self.csr.directed else 1, off.data_ptr() - 8 * e, _lib.ptr(order), 0, 1, None,
-                    _lib.ptr(slots), None, _lib.ptr(status), None, K, _lib.ptr(scratch), sbytes, self._stream()))
-            if int(status.item()) & (_lib.N2V_STATUS_ZERO_NORM | _lib.N2V_STATUS_ZERO_POP):
-                raise ZeroDivisionError("float division by zero")
-        s = slots[:K]
-        return (self.slots_J(s).cpu().numpy().astype(np.int64), self.slots_q(s).cpu().numpy())
+                self._edge_tables_wave(src_of.data_ptr() - 4 * e, off.data_ptr() - 8 * e, order, 1, K, scratch, sbytes,
+                                       status, thin=slots)
+            _check_status(status)
+        return self.host_table(slots[:K])
 
     # ------------------------------------------------------------------ walks
     def walk(self, starts, num_rounds, walk_length, rng="philox", seed=0, uniforms=None, walk_uoff=None,
@@ -369,30 +446,14 @@ class WalkEngine:
         if not self.ready:
             raise RuntimeError("preprocess() first")
         if self.partial:          # stored tables for part of the entries: the hybrid kernel rebuilds the others per step
-            if rng == "uniforms_tiled":
-                raise ValueError("the tiled uniform layout is read by the fat-table walk kernel only")
             return self.walk_on_the_fly(starts, num_rounds, walk_length, rng=rng, seed=seed, uniforms=uniforms,
                                         walk_uoff=walk_uoff, pos_begin=pos_begin, pos_count=pos_count,
                                         round_begin=round_begin, out=out, uoff_round_stride=uoff_round_stride, hybrid=True)
-        d = self.device
-        L = int(walk_length)
-        if L < 1:
-            raise ValueError("walk_length must be >= 1")
-        n_starts = int(starts.numel())
-        if pos_count is None:
-            pos_count = n_starts - pos_begin
-        n_local = pos_count * num_rounds
-        with torch.cuda.device(d):
-            if out is None:
-                walks = torch.empty((n_local, L), dtype=torch.int32, device=d)
-                lens = torch.empty(n_local, dtype=torch.int32, device=d)
-            else:
-                walks, lens = out
-                assert walks.shape == (n_local, L) and walks.dtype == torch.int32 and walks.is_contiguous()
-            mode = {"uniforms": _lib.RNG_UNIFORMS, "uniforms_tiled": _lib.RNG_UNIFORMS_TILED}.get(rng, _lib.RNG_PHILOX)
-            use_fat = self.edge_fat is not None if layout is None else (layout == "fat")
-            if mode == _lib.RNG_UNIFORMS_TILED and not use_fat:
-                raise ValueError("the tiled uniform layout is read by the fat-table walk kernel only")
+        use_fat = self.edge_fat is not None if layout is None else (layout == "fat")
+        mode = rng_mode(rng, tiled_ok=use_fat)
+        L, n_starts = int(walk_length), int(starts.numel())
+        pos_count, n_local, walks, lens = walk_frame(n_starts, pos_begin, pos_count, num_rounds, L, out, self.device)
+        with torch.cuda.device(self.device):
             if not use_fat and self.edge_slots is None:
                 raise RuntimeError("thin tables were not built (preprocess(fat=False) or fat='both')")
             if use_fat:
@@ -425,22 +486,13 @@ class WalkEngine:
         numpy-stream resolution walks some walks from guessed stream offsets first: only a failure at the true offset
         counts)."""
         d = self.device
-        L = int(walk_length)
-        if L < 1:
-            raise ValueError("walk_length must be >= 1")
+        mode = rng_mode(rng, tiled_ok=False)
+        L, n_starts = int(walk_length), int(starts.numel())
+        pos_count, n_local, walks, lens = walk_frame(n_starts, pos_begin, pos_count, num_rounds, L, out, d)
         if self.p == 0 or (self.q == 0 and not pop):
             raise ZeroDivisionError("float division by zero")
-        n_starts = int(starts.numel())
-        if pos_count is None:
-            pos_count = n_starts - pos_begin
-        n_local = pos_count * num_rounds
         with torch.cuda.device(d):
-            if out is None:
-                walks = torch.empty((n_local, L), dtype=torch.int32, device=d)
-                lens = torch.empty(n_local, dtype=torch.int32, device=d)
-            else:
-                walks, lens = out
-            scratch = getattr(self, "_otf_scratch", None)
+            scratch = self._otf_scratch
             if self.max_degree > int(self.lib.n2v_walk_otf_lds_slots()):
                 # one scratch row per resident wavefront; grown when a later call launches more waves than the
                 # call that first allocated it (a single node2vec_walk_on_the_fly must not pin later launches
@@ -450,7 +502,6 @@ class WalkEngine:
                     scratch = self._otf_scratch = torch.empty((n_waves * self.max_degree, 2), dtype=torch.int64,
                                                               device=d)
             status = torch.zeros(1, dtype=torch.int32, device=d)
-            mode = _lib.RNG_UNIFORMS if rng == "uniforms" else _lib.RNG_PHILOX
             if uoff_round_stride and walk_uoff is not None:
                 walk_uoff = expand_round_offsets(walk_uoff, num_rounds, uoff_round_stride)
             tail = (_lib.ptr(starts), n_starts, pos_begin, pos_count, round_begin, num_rounds, L, mode,
@@ -466,9 +517,7 @@ class WalkEngine:
                 _lib.check(self.lib.n2v_walk_on_the_fly_pop(*head, _lib.ptr(self.plain), *tail))
             else:
                 _lib.check(self.lib.n2v_walk_on_the_fly(*head, *tail))
-            st = int(status.item())
-            if st & _lib.N2V_STATUS_ZERO_NORM or (st & _lib.N2V_STATUS_ZERO_POP and not defer_failures):
-                raise ZeroDivisionError("float division by zero")
+            _check_status(status, ignore=_lib.N2V_STATUS_ZERO_POP if defer_failures else 0)
         return walks, lens
 
 

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from n2v_hip import csr as _csr
+from n2v_hip import merge as _merge
 from n2v_hip import mt19937 as _mt
 from n2v_hip.engine import WalkEngine
 
@@ -190,6 +191,13 @@ class _AliasEdges:
 
 
 class Graph():
+    # Knobs beyond the reference's surface: class defaults, set on an instance by whoever wants another value.
+    host_rng = False              # rng="numpy": take the uniforms from numpy on the host instead of the device generator
+    linear_uniforms = False       # rng="numpy": never lay the uniforms out in the fat walk kernel's tiled order
+    uniform_chunk_rounds = None   # rng="numpy": rounds of walks per generated chunk of uniforms (None: sized by free memory)
+    force_on_the_fly = False      # simulate_walks_on_the_fly: rebuild the tables per step even where stored ones exist
+    table_budget_bytes = None     # preprocess_transition_probs*: the default of their budget_bytes
+
     def __init__(self, nx_G, is_directed, p, q, popwalk="none", device=None, rng="numpy", seed=0):
         self.G = nx_G
         self.is_directed = is_directed
@@ -201,6 +209,7 @@ class Graph():
         self.seed = seed
         self._csr_cache = None
         self._engine = None
+        self.stream_passes = 0        # launches the last numpy-stream resolution of early-ending walks took
 
     # construction without networkx for graphs too large for a dict-of-dict container
     @classmethod
@@ -255,7 +264,7 @@ class Graph():
             self._engine = eng = None
             eng = WalkEngine(self._csr, self.p, self.q, device=self.device)
         if budget_bytes is None:
-            budget_bytes = getattr(self, "table_budget_bytes", None)
+            budget_bytes = self.table_budget_bytes
         eng.preprocess(budget_bytes=budget_bytes, pop=pop)    # every table is rebuilt, in the flavour asked for
         self._engine = eng
         self.alias_nodes = _AliasNodes(self)
@@ -309,13 +318,8 @@ class Graph():
         '''
         Repeatedly simulate random walks from each node.
         '''
-        if self._engine is None or not self._engine.ready:
-            raise AttributeError("'Graph' object has no attribute 'alias_nodes'")  # as the reference would
-        if verbose:
-            for walk_iter in range(num_walks):
-                print(str(walk_iter + 1), '/', str(num_walks))
-        walks, lens = self._simulate(num_walks, walk_length, self._starts(nodes))
-        return WalkCorpus(walks, lens, self._csr.labels)
+        self._ready_engine()
+        return self._simulate(num_walks, walk_length, self._starts(nodes), verbose=verbose)
 
     # src/node2vec.py:97-111 — identical output to simulate_walks for popwalk == "none".
     # Needs no preprocess_transition_probs(): the (prev, cur) table is rebuilt at every step
@@ -324,13 +328,8 @@ class Graph():
     # popwalk == "pop" is NOT the walk of preprocess_transition_probs_popularity (that one keeps the plain edge
     # tables): every step after the first draws from get_alias_edge_pop, so stored tables are never used.
     def simulate_walks_on_the_fly(self, num_walks, walk_length, nodes=None, verbose=False):
-        self._pop()
-        if verbose:
-            for walk_iter in range(num_walks):
-                print(str(walk_iter + 1), '/', str(num_walks))
         otf = self._otf_engine()
-        walks, lens = self._simulate(num_walks, walk_length, self._starts(nodes), otf=otf)
-        return WalkCorpus(walks, lens, self._csr.labels)
+        return self._simulate(num_walks, walk_length, self._starts(nodes), otf=otf, verbose=verbose)
 
     def _graph_engine(self):
         """The engine with the graph on the device (tables or not)."""
@@ -338,50 +337,58 @@ class Graph():
             self._engine = WalkEngine(self._csr, self.p, self.q, device=self.device)
         return self._engine
 
+    def _ready_engine(self):
+        """The engine with its tables built; without them the error the reference would raise."""
+        if self._engine is None or not self._engine.ready:
+            raise AttributeError("'Graph' object has no attribute 'alias_nodes'")
+        return self._engine
+
     def _otf_engine(self):
         """True if the on-the-fly kernel has to (or is asked to) run; makes sure an engine
         (graph on the device, no tables) exists."""
-        if self._pop():               # never the stored tables: they hold the plain edge rule
-            self._graph_engine()
-            return True
-        if (self._engine is not None and self._engine.ready and not self._engine.pop_tables
-                and not getattr(self, "force_on_the_fly", False)):
-            return False
-        if self._engine is None:
-            self._engine = WalkEngine(self._csr, self.p, self.q, device=self.device)
-        return True
+        pop = self._pop()             # never the stored tables: they hold the plain edge rule
+        eng = self._graph_engine()
+        return bool(pop or not eng.ready or eng.pop_tables or self.force_on_the_fly)
 
     # src/node2vec.py:55-79
     def node2vec_walk(self, walk_length, start_node):
-        if self._engine is None or not self._engine.ready:
-            raise AttributeError("'Graph' object has no attribute 'alias_nodes'")
-        walks, lens = self._simulate(1, walk_length, self._csr.dense_of([start_node]))
-        return WalkCorpus(walks, lens, self._csr.labels)[0]
+        self._ready_engine()
+        return self._simulate(1, walk_length, self._csr.dense_of([start_node]))[0]
 
     def node2vec_walk_on_the_fly(self, walk_length, start_node):
         otf = self._otf_engine()
-        walks, lens = self._simulate(1, walk_length, self._csr.dense_of([start_node]), otf=otf)
-        return WalkCorpus(walks, lens, self._csr.labels)[0]
+        return self._simulate(1, walk_length, self._csr.dense_of([start_node]), otf=otf)[0]
 
     # ------------------------------------------------------------------ internals
-    def _simulate(self, num_walks, walk_length, starts_host, otf=False):
+    def _walk_entry(self, mode):
+        """The engine entry point of a walk mode: "stored" (the table-driven walk), "otf" (tables rebuilt per step) or
+        "pop" (the same under the popularity rule).  The mode is decided once per call, by _simulate, and handed down."""
         eng = self._engine
-        self._walk = eng.walk_on_the_fly if otf else eng.walk
-        self._walk_pop = bool(otf and self._pop())
-        if self._walk_pop:
-            self._walk = functools.partial(eng.walk_on_the_fly, pop=True)
-        d = eng.device
+        if mode == "stored":
+            return eng.walk
+        return functools.partial(eng.walk_on_the_fly, pop=True) if mode == "pop" else eng.walk_on_the_fly
+
+    def _simulate(self, num_walks, walk_length, starts_host, otf=False, verbose=False):
+        """The WalkCorpus of num_walks rounds from the dense ids `starts_host`, by the stored-table walk or (otf) the
+        on-the-fly one."""
+        if verbose:
+            for walk_iter in range(num_walks):
+                print(str(walk_iter + 1), '/', str(num_walks))
+        mode = "stored" if not otf else "pop" if self._pop() else "otf"
+        d = self._engine.device
         L = max(int(walk_length), 1)  # walk = [start] even for walk_length <= 1 (:63-65)
         num_walks = int(num_walks)
         starts = torch.from_numpy(np.ascontiguousarray(starts_host, dtype=np.int32)).to(d)
         n = int(starts.numel())
         if n * num_walks == 0:
-            return (torch.empty((0, L), dtype=torch.int32, device=d), torch.empty(0, dtype=torch.int32, device=d))
-        if self.rng == "philox":
-            return self._walk(starts, num_walks, L, rng="philox", seed=self.seed)
-        if self.rng != "numpy":
+            walks, lens = torch.empty((0, L), dtype=torch.int32, device=d), torch.empty(0, dtype=torch.int32, device=d)
+        elif self.rng == "philox":
+            walks, lens = self._walk_entry(mode)(starts, num_walks, L, rng="philox", seed=self.seed)
+        elif self.rng == "numpy":
+            walks, lens = self._simulate_numpy_stream(starts, n, num_walks, L, mode)
+        else:
             raise ValueError("rng must be 'numpy' or 'philox'")
-        return self._simulate_numpy_stream(starts, n, num_walks, L)
+        return WalkCorpus(walks, lens, self._csr.labels)
 
     def simulate_walks_shard(self, num_walks, walk_length, rank, world):
         """The walks one of `world` GPUs owns: all rounds over the rank's
@@ -390,16 +397,13 @@ class Graph():
         Philox mode because the counter is the global walk index, in numpy mode because every
         rank jumps numpy's global MT19937 stream to the offsets its walks own — and leaves the
         global state where the full, single-process call would have left it."""
-        if self._engine is None or not self._engine.ready:
-            raise AttributeError("'Graph' object has no attribute 'alias_nodes'")
-        eng = self._engine
+        eng = self._ready_engine()
         d = eng.device
         L = max(int(walk_length), 1)
         num_walks = int(num_walks)
         n = int(eng.start_order.numel())
-        per = -(-n // int(world))
-        b = min(int(rank) * per, n)
-        cnt = min(b + per, n) - b
+        b, end = _merge.shard_bounds(n, int(world), int(rank))
+        cnt = end - b
         if self.rng == "philox":
             walks, lens = eng.walk(eng.start_order, num_walks, L, rng="philox", seed=self.seed, pos_begin=b, pos_count=cnt)
             return WalkCorpus(walks, lens, self._csr.labels)
@@ -420,7 +424,6 @@ class Graph():
         walks = torch.empty((cnt * num_walks, L), dtype=torch.int32, device=d)
         lens = torch.empty(cnt * num_walks, dtype=torch.int32, device=d)
         st0 = np.random.get_state()
-        self._walk = eng.walk
         tiled = self._tiled_uniforms_ok(L)
         for it in range(num_walks):
             if cnt == 0:
@@ -439,19 +442,19 @@ class Graph():
         """The next n doubles of numpy's global MT19937 stream as a device tensor: generated on
         the GPU by jump-ahead (default) or by numpy on the host (`host_rng = True`).  tiled_pairs = L-1: in the
         fat walk kernel's tiled layout (n2v_hip/mt19937.py)."""
-        if getattr(self, "host_rng", False):
+        if self.host_rng:
             assert not tiled_pairs and out is None
             return torch.from_numpy(np.random.random_sample(n)).to(device)
         return _mt.global_uniforms_device(n, device, tiled_pairs=tiled_pairs, out=out)
 
-    def _tiled_uniforms_ok(self, L):
-        """Tiled uniforms need the fat-table kernel, device-side generation and walks that cannot end early (the
-        callers check the last)."""
+    def _tiled_uniforms_ok(self, L, mode="stored"):
+        """Tiled uniforms need the fat-table kernel (the stored-table walk of an engine that is not partial),
+        device-side generation and walks that cannot end early (the callers check the last)."""
         eng = self._engine
-        return bool(L > 1 and not getattr(self, "host_rng", False) and not getattr(self, "linear_uniforms", False)
-                    and getattr(self, "_walk", None) == eng.walk and eng.edge_fat is not None and not eng.partial)
+        return bool(L > 1 and not self.host_rng and not self.linear_uniforms
+                    and mode == "stored" and eng.edge_fat is not None and not eng.partial)
 
-    def _resolve_stream_offsets(self, starts, n, num_walks, L, active):
+    def _resolve_stream_offsets(self, starts, n, num_walks, L, active, mode):
         """Directed graph with reachable sinks: a walk that ends early consumes fewer uniforms, so the position
         of walk w in numpy's stream depends on the lengths of all walks before it (src/node2vec.py:76-77 stops
         without drawing).  The chain is resolved on the device window by window: the window's first walk has an
@@ -461,8 +464,9 @@ class Graph():
         a pass finalises 1 / P(a re-walked walk changes its length) walks on average (round 1 re-walked ALL
         walks per pass).  The uniforms are generated as the chain advances (a sliding piece of numpy's stream of
         at least 2^24 doubles), not for all walks at once."""
-        eng = self._engine
-        d = eng.device
+        d = self._engine.device
+        walk = self._walk_entry(mode)
+        kw = {"defer_failures": True} if mode == "pop" else {}
         W = n * num_walks
         walks = torch.empty((W, L), dtype=torch.int32, device=d)
         lens = torch.empty(W, dtype=torch.int32, device=d)
@@ -483,9 +487,8 @@ class Graph():
                 have_end = max(u_base + U.numel(), exact_off)
                 U = torch.cat([keep, self._global_uniforms(max(need_end - have_end, 1 << 24), d)])
                 u_base = exact_off
-            kw = {"defer_failures": True} if getattr(self, "_walk_pop", False) else {}
-            w_win, l_win = self._walk(starts_all[done:hi].contiguous(), 1, L, rng="uniforms", uniforms=U,
-                                      walk_uoff=(off - u_base).contiguous(), **kw)
+            w_win, l_win = walk(starts_all[done:hi].contiguous(), 1, L, rng="uniforms", uniforms=U,
+                                walk_uoff=(off - u_base).contiguous(), **kw)
             failed = l_win < 0            # pop walk: met a neighbour without out-edges (only final walks count, below)
             l_win = l_win.abs()
             used = (l_win.to(torch.int64) - 1) * 2
@@ -505,10 +508,11 @@ class Graph():
             window = max(1024, min(1 << 18, 4 * first if first < m else 2 * window))
         return walks, lens
 
-    def _simulate_numpy_stream(self, starts, n, num_walks, L):
+    def _simulate_numpy_stream(self, starts, n, num_walks, L, mode):
         """Parity mode.  Walk w = it*n + pos owns the uniforms the sequential reference
         loop would have handed it: offset 2 * sum_{w' < w} (len(w') - 1)."""
         eng = self._engine
+        walk = self._walk_entry(mode)
         d = eng.device
         W = n * num_walks
         step = 2 * (L - 1)
@@ -516,8 +520,8 @@ class Graph():
         per_round = active.to(torch.int64) * step
         per = int(per_round.sum().item())                   # uniforms one round consumes when no walk ends early
         if per == 0:
-            return self._walk(starts, num_walks, L, rng="uniforms", uniforms=torch.zeros(2, dtype=torch.float64, device=d),
-                              walk_uoff=torch.zeros(W, dtype=torch.int64, device=d))
+            return walk(starts, num_walks, L, rng="uniforms", uniforms=torch.zeros(2, dtype=torch.float64, device=d),
+                        walk_uoff=torch.zeros(W, dtype=torch.int64, device=d))
         # a walk can end early only at a node without out-neighbours that is reachable,
         # i.e. never on an undirected graph (every visited node has the edge it came by)
         may_end_early = bool(self._csr.directed) and bool((eng.deg == 0).any().item())
@@ -532,23 +536,22 @@ class Graph():
             uoff_round = None if per == n * step else (torch.cumsum(per_round, 0) - per_round).contiguous()
             walks = torch.empty((W, L), dtype=torch.int32, device=d)
             lens = torch.empty(W, dtype=torch.int32, device=d)
-            host = getattr(self, "host_rng", False)
-            tiled = self._tiled_uniforms_ok(L)
-            rounds_per_chunk = getattr(self, "uniform_chunk_rounds", None)
+            tiled = self._tiled_uniforms_ok(L, mode)
+            rounds_per_chunk = self.uniform_chunk_rounds
             if rounds_per_chunk is None:
                 free = torch.cuda.mem_get_info(d)[0]
-                budget = (1 << 27) if host else max(1 << 27, min(1 << 32, free // 32))   # doubles per chunk (<= 32 GiB)
+                budget = (1 << 27) if self.host_rng else max(1 << 27, min(1 << 32, free // 32))   # doubles per chunk (<= 32 GiB)
                 rounds_per_chunk = budget // max(per, 1)
             rounds_per_chunk = int(max(1, min(num_walks, rounds_per_chunk)))
             for it in range(0, num_walks, rounds_per_chunk):
                 k = min(rounds_per_chunk, num_walks - it)
                 U = self._global_uniforms(per * k, d, L - 1 if tiled else None)
-                self._walk(starts, k, L, rng="uniforms_tiled" if tiled else "uniforms", uniforms=U, walk_uoff=uoff_round,
-                           uoff_round_stride=per, round_begin=it, out=(walks[it * n:(it + k) * n], lens[it * n:(it + k) * n]))
+                walk(starts, k, L, rng="uniforms_tiled" if tiled else "uniforms", uniforms=U, walk_uoff=uoff_round,
+                     uoff_round_stride=per, round_begin=it, out=(walks[it * n:(it + k) * n], lens[it * n:(it + k) * n]))
                 del U
             return walks, lens
         state = np.random.get_state()
-        walks, lens = self._resolve_stream_offsets(starts, n, num_walks, L, active)
+        walks, lens = self._resolve_stream_offsets(starts, n, num_walks, L, active, mode)
         used = int(((lens.to(torch.int64) - 1) * 2).sum().item())
         np.random.set_state(state)
         _mt.advance_global_state(used)  # leave the global stream where the reference would
